@@ -6,6 +6,7 @@ test/runbenchmarks.jl:120): precompute(ϕ) + 1 inverse flow + 1 
 the Fourier-diagonal / mask / reduction work, LenseFlow n = 7 RK4 steps, fp32, inputs resident in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--nside 1024] [--pol P] [--nbatch B] [--config {2,3,5}] [--no-cpu-baseline]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--config C` runs BASELINE.json's configuration C (2: 512² QU fp32; 3: 1024² T+QU fp32; 5: 2048² QU fp64 n=10) with the same step and
@@ -328,8 +329,10 @@ def dry_run(args, torch, dist, rank, world, local, seeds):
         time.sleep(1e-3)
         return [float(seeds[0])]
     def barrier():
+        # an all-reduce of a host tensor, not dist.barrier(): that one initialises the GPU runtime even over gloo, and the rehearsal's
+        # N processes must not hold a device open
         if dist is not None:
-            dist.barrier()
+            dist.all_reduce(torch.zeros(1))
     for _ in range(args.warmup):
         step()
     barrier(); t0 = time.perf_counter()
@@ -358,6 +361,35 @@ def dry_run(args, torch, dist, rank, world, local, seeds):
                           "logpdf": lps, "collective": coll}, ensure_ascii=False))
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60 << 20      # --dump-outputs: the sampled data; with the .npy headers the files stay under 64 MB (10^6 bytes) in all
+DUMP_SEED = 20240917       # fixed: the same arguments sample the same elements in every run
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES, seed=DUMP_SEED):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy in float32 / float64 (complex as a trailing (re, im) axis), so that two builds
+    can be compared output for output.  If together they exceed `budget`, each array is cut to its share of it by a fixed sample of its
+    elements (flat indices drawn without replacement by a generator seeded with `seed`, in increasing order) and stored 1-D.
+    Returns {name: {"shape": shape of the full array, "sampled": elements kept or None}}."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        if np.iscomplexobj(a):
+            a = np.stack([a.real, a.imag], axis=-1)
+        host[name] = np.ascontiguousarray(a, dtype=a.dtype if a.dtype in (np.float32, np.float64) else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    info = {}
+    for name, a in host.items():
+        keep = a.size if total <= budget else max(1, a.size * budget // total)
+        info[name] = {"shape": list(a.shape), "sampled": None}
+        if keep < a.size:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+            info[name]["sampled"] = int(keep)
+        np.save(os.path.join(path, name + ".npy"), a)
+    return info
 
 
 def clock_ramp(step, sync, block=5, tol=0.01, max_blocks=60):
@@ -398,7 +430,14 @@ def main():
                     help="dress rehearsal of the N-GPU run on a box without the GPUs: the self-launch, rank -> device assignment (N mocked devices), "
                          "per-rank seeds, barriers, MAX-over-ranks timing, the result gather and the collective report all run (gloo, CPU); the "
                          "step itself is a stand-in.  The line carries \"dry_run\": true and is never a measurement")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all: a fixed, seeded sample of larger outputs); rank 0 writes")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dry_run_ranks and args.dump_outputs:
+        ap.error("--dump-outputs needs the real step (not --dry-run-ranks)")
     dry = args.dry_run_ranks > 0
     if dry:
         args.gpus, args.dist_backend = args.dry_run_ranks, "gloo"
@@ -451,15 +490,18 @@ def main():
     fo, po = ds.mix(sim["f"], sim["phi"])
 
     if args.only == "cg":
-        # one unit = one CG iteration: a fixed-length solve (tol = 0) of steps + warmup iterations in total
-        def run_all():
-            return ds.argmaxf_logpdf(sim["phi"], tol=0.0, nsteps=args.steps + args.warmup)
+        # one unit = one CG iteration: an untimed fixed-length solve (tol = 0) of `warmup` iterations, then a timed one of `steps`
+        if args.warmup:
+            ds.argmaxf_logpdf(sim["phi"], tol=0.0, nsteps=args.warmup)
         torch.cuda.synchronize(); t0 = time.perf_counter()
-        run_all()
+        fw, hist = ds.argmaxf_logpdf(sim["phi"], tol=0.0, nsteps=args.steps)
         torch.cuda.synchronize(); dt = time.perf_counter() - t0
-        print(json.dumps({"metric": "Wiener-filter CG iterations/s (profiling aid)", "value": (args.steps + args.warmup) / dt, "unit": "iterations/s",
-                          "ms_per_step": dt / (args.steps + args.warmup) * 1e3, "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-                          "config": {"workload": f"{N}² {pol} Wiener CG iteration"}}, ensure_ascii=False))
+        out = {"metric": "Wiener-filter CG iterations/s (profiling aid)", "value": args.steps / dt, "unit": "iterations/s",
+               "ms_per_step": dt / args.steps * 1e3, "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+               "config": {"workload": f"{N}² {pol} Wiener CG iteration"}}
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, {"wiener_f": fw.arr, "cg_residuals": np.array([h for _, h in hist])})
+        print(json.dumps(out, ensure_ascii=False))
         return
 
     def step():
@@ -498,6 +540,10 @@ def main():
     else:
         lps = np.asarray(lp)
     assert np.all(np.isfinite(lps)), lps
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step receives from its last call: logpdf (every rank's chains), ∇f° [MAP], ∇ϕ° [FOURIER] of this rank
+        dumped = dump_outputs(args.dump_outputs, {"logpdf": np.asarray(lps, dtype=np.float64), "grad_f": gf.arr, "grad_phi": gp.arr})
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
 
@@ -521,6 +567,8 @@ def main():
     }
     if rccl is not None:
         out["collective"] = rccl
+    if dumped is not None:
+        out["dump_outputs"] = dumped
 
     if rank == 0 and world == 1 and not args.no_roofline:
         # (N > 1: no rank does extra work after the timed region, so none idles at destroy_process_group while rank 0 profiles)

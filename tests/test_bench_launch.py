@@ -93,3 +93,31 @@ def test_dry_run_refuses_fewer_devices_than_ranks():
     env = dict(os.environ, WORLD_SIZE="4", RANK="3", LOCAL_RANK="3", MASTER_ADDR="127.0.0.1", MASTER_PORT="29999")
     r = subprocess.run([sys.executable, "bench.py", "--dry-run-ranks", "2", "--gpus", "4"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "only 2 GPU" in r.stderr, r.stderr[-2000:]
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """--dump-outputs: float32 / float64 .npy per output, complex as (re, im) pairs; over the budget a fixed sample, the same every run"""
+    import numpy as np
+    rng = np.random.default_rng(0)
+    arrays = {"logpdf": np.array([-1.5, 2.0]), "grad_f": rng.standard_normal((1, 2, 64, 32)).astype(np.float32),
+              "grad_phi": (rng.standard_normal((1, 1, 64, 17)) + 1j * rng.standard_normal((1, 1, 64, 17))).astype(np.complex64)}
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in arrays}
+    assert got["logpdf"].dtype == np.float64 and np.array_equal(got["logpdf"], arrays["logpdf"])
+    assert got["grad_f"].dtype == np.float32 and np.array_equal(got["grad_f"], arrays["grad_f"])
+    assert got["grad_phi"].dtype == np.float32 and got["grad_phi"].shape == (1, 1, 64, 17, 2)
+    assert np.array_equal(got["grad_phi"][..., 0] + 1j * got["grad_phi"][..., 1], arrays["grad_phi"])
+    assert all(v["sampled"] is None for v in info.values())
+    budget = 8 * 1024
+    for d in ("b", "c"):
+        info = bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    files = {k: [np.load(str(tmp_path / d / (k + ".npy"))) for d in ("b", "c")] for k in arrays}
+    assert sum(v[0].nbytes for v in files.values()) <= budget
+    assert all(np.array_equal(*v) for v in files.values())                                # same arguments, same sample
+    assert info["grad_f"]["shape"] == [1, 2, 64, 32] and info["grad_f"]["sampled"] == files["grad_f"][0].size < arrays["grad_f"].size
+    assert np.isin(files["grad_f"][0], arrays["grad_f"].ravel()).all()
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "0"], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr, r.stderr[-2000:]

@@ -1,7 +1,7 @@
 """The JLD2 reader (cmblensing.jl_amd/jld2.py) and `load_chains` on the reference's container format.
   * real-world vector: the reference's own dat/default_camb_Cls.jld2 (written by the JLD2 package: version-2 object headers,
     committed compound datatypes with compound `julia_type` attributes, object references, deflate-compressed arrays) decodes to
-    the spectra of tests/golden/camb_cls.npz -- only where /root/reference exists (the build container), skipped elsewhere;
+    the spectra of tests/golden/camb_cls.npz (the file is rebuilt byte for byte by tests/_ref_jld2.py);
   * a hand-built chain file with the layout `sample_joint` writes (src/sampling.jl:311-320), made by tests/_jld2_writer.py from the
     HDF5 specification: `load_chains` / resume read it like the package's own zip container."""
 import os
@@ -35,12 +35,17 @@ J, CF = _mod("jld2"), _mod("chainfile")
 import _jld2_writer as W                                  # noqa: E402
 W.Writer.lookup3 = staticmethod(J.lookup3)
 
-REF_JLD2 = "/root/reference/dat/default_camb_Cls.jld2"
 
 
-@pytest.mark.skipif(not os.path.isfile(REF_JLD2), reason="the reference's data file only exists in the build container")
-def test_reads_the_reference_s_own_jld2_file():
-    f = J.JLD2File(REF_JLD2)
+@pytest.fixture(scope="session")
+def ref_jld2(tmp_path_factory):
+    """the reference's dat/default_camb_Cls.jld2, unchanged (SHA-256 checked)"""
+    from _ref_jld2 import write_reference_jld2
+    return write_reference_jld2(str(tmp_path_factory.mktemp("ref") / "default_camb_Cls.jld2"))
+
+
+def test_reads_the_reference_s_own_jld2_file(ref_jld2):
+    f = J.JLD2File(ref_jld2)
     assert sorted(f.keys()) == ["Cℓ", "params"]
     p = f["params"]
     assert p["r"] == 0.2 and p["ℓmax"] == 16000 and abs(p["ωb"] - 0.0224567) < 1e-12 and p["AL"] == 1      # src/cls.jl:135-141 defaults

@@ -1,7 +1,7 @@
 """The JLD2 WRITER (cmblensing.jl_amd/jld2_writer.py): chain files in the reference's own container (src/sampling.jl:311-320).
   * round trip: every value kind, the chain-file layout, append ("a+"), through the reader with all lookup3 checksums verified;
   * structure: the same message kinds, versions and flags as the file the JLD2 package itself wrote (the reference's
-    dat/default_camb_Cls.jld2; only where /root/reference exists) -- superblock, root group, `_types` group, committed datatypes with
+    dat/default_camb_Cls.jld2, rebuilt by tests/_ref_jld2.py) -- superblock, root group, `_types` group, committed datatypes with
     `julia_type` as a value of the first committed datatype, DataType / Int64 parameter datasets, global heap collections;
   * the chain-file API (`write_chunk` / `load_chains` / `last_state`) on `.jld2` file names, and the read-only rule for files the Julia
     package wrote.
@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_jld2 import _mod, REF_JLD2, J, CF              # noqa: E402
+from test_jld2 import _mod, J, CF, ref_jld2               # noqa: E402,F401  (ref_jld2: the fixture)
 
 W = _mod("jld2_writer")
 
@@ -128,15 +128,14 @@ def test_structure_follows_the_conventions_of_jld2(tmp_path):
     assert b[p + 4] == 1 and size >= 4096 and struct.unpack_from("<H", b, p + 16)[0] == 1
 
 
-@pytest.mark.skipif(not os.path.isfile(REF_JLD2), reason="the reference's data file only exists in the build container")
-def test_same_structures_as_the_file_jld2_itself_wrote(tmp_path):
+def test_same_structures_as_the_file_jld2_itself_wrote(tmp_path, ref_jld2):
     """message kinds, versions and flags of each object class, side by side with dat/default_camb_Cls.jld2"""
     fn = str(tmp_path / "s.jld2")
     with W.JLD2Writer(fn, "w") as w:
         w.write("x", {"a": 1.0, "v": np.arange(3.0)})
-    mine, ref = J.JLD2File(fn), J.JLD2File(REF_JLD2)
+    mine, ref = J.JLD2File(fn), J.JLD2File(ref_jld2)
     mine.keys(); ref.keys()
-    bm, br = open(fn, "rb").read(), open(REF_JLD2, "rb").read()
+    bm, br = open(fn, "rb").read(), open(ref_jld2, "rb").read()
     assert bm[512:524] == br[512:524]                                   # superblock signature, version, offset / length sizes
     assert struct.unpack_from("<QQ", bm, 524) == struct.unpack_from("<QQ", br, 524)      # base address 512, no extension
     # root group and _types group: the same message kinds in the same order (links differ in number only)

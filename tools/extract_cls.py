@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Decode the reference's cached CAMB spectra into a small .npz data fixture.
 
-Source (data file, read-only, only in the build container):
-    /root/reference/dat/default_camb_Cls.jld2
+Source: the reference's data file dat/default_camb_Cls.jld2 (its path is the argument),
 written by dat/compute_default_camb_Cls.jl:1-2 from `camb(ℓmax=16000)`
 (src/cls.jl:135-200): five groups {unlensed_scalar, lensed_scalar, tensor,
 unlensed_total, total} x {TT,EE,BB,TE} + one shared ϕϕ, each a Float64 vector
@@ -20,7 +19,6 @@ import sys
 import zlib
 import numpy as np
 
-SRC = "/root/reference/dat/default_camb_Cls.jld2"
 DST = "tests/golden/camb_cls.npz"
 NL = 15998
 LMAX_KEEP = 12000      # 2048² @ 1′ would need ≈15274; 2′ pixels need 7638
@@ -46,8 +44,8 @@ def scan_streams(buf):
     return out
 
 
-def main():
-    buf = open(SRC, "rb").read()
+def main(src):
+    buf = open(src, "rb").read()
     s = scan_streams(buf)
     assert len(s) == 21, len(s)
     names = (["unlensed_scalar_" + k for k in ("TT", "EE", "BB", "TE")] + ["phiphi"]
@@ -80,4 +78,4 @@ def main():
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(main(sys.argv[1]))
