@@ -174,21 +174,26 @@ struct CtxBase {
   long npix() const { return (long)Ny * Nx; }
 };
 
+// Where and how one any-size launch runs: its stream; its slice window -- slices [sl0, sl0 + sln) of the slall slices of a flow, of each part of
+// its batch when that is a multiple of slall (pair launches); sln < 0: all slices -- and the layout of the hand-off arrays it touches: tile = rows
+// of a block column of tiled [x / 4][ky][x % 4] arrays (Ctx::gen_tile), 0: [ky][x] arrays.
+struct GenRun { hipStream_t st; long sl0 = 0, sln = -1, slall = 0; int tile = 0; };
+
 // The launches of the compile-time-plan kernels (kernels_ct.hpp) of ONE length N: declared here, defined in engine_ct.hpp and instantiated per
 // length by tu_cty_* (column side + the plain transforms) and tu_ctx_* (row side of the fused stages), so that no other translation unit
 // compiles those kernels and the build splits the list of lengths over several units.  Sx / S: wavefronts per workgroup of the launch.
 template <typename T> struct Ctx;
 template <typename T, int N> struct CtLaunchY {
-  static void dftx(Ctx<T>* c, const GenDft<T>& a, dim3 grid, int Sx, int kind);
-  static void dft(Ctx<T>* c, const GenDft<T>& a, dim3 grid, int kind);
-  static void flow_y(Ctx<T>* c, const GenDft<T>& a, dim3 grid);
-  static bool delta_y(Ctx<T>* c, const GenDft<T>& a, dim3 grid);       // false: two LDS row sets of this length do not fit
-  static void adj_y(Ctx<T>* c, const GenDft<T>& a, dim3 grid);
+  static void dftx(Ctx<T>* c, const GenRun& r, const GenDft<T>& a, dim3 grid, int Sx, int kind);
+  static void dft(Ctx<T>* c, const GenRun& r, const GenDft<T>& a, dim3 grid, int kind);
+  static void flow_y(Ctx<T>* c, const GenRun& r, const GenDft<T>& a, dim3 grid);
+  static bool delta_y(Ctx<T>* c, const GenRun& r, const GenDft<T>& a, dim3 grid);       // false: two LDS row sets of this length do not fit
+  static void adj_y(Ctx<T>* c, const GenRun& r, const GenDft<T>& a, dim3 grid);
 };
 template <typename T, int N> struct CtLaunchX {
-  static void adj_x(Ctx<T>* c, const GenDft<T>& a, dim3 grid, int Sx);
-  static void adj_x_dx(Ctx<T>* c, const GenDft<T>& a, dim3 grid, int Sx, int ws, const GenDft<T>& a1);
-  static void dft2(Ctx<T>* c, const GenDft<T>& a0, int kind0, dim3 grid, int Sx, int ws, const GenDft<T>& a1, int kind1);
+  static void adj_x(Ctx<T>* c, const GenRun& r, const GenDft<T>& a, dim3 grid, int Sx);
+  static void adj_x_dx(Ctx<T>* c, const GenRun& r, const GenDft<T>& a, dim3 grid, int Sx, int ws, const GenDft<T>& a1);
+  static void dft2(Ctx<T>* c, const GenRun& r, const GenDft<T>& a0, int kind0, dim3 grid, int Sx, int ws, const GenDft<T>& a1, int kind1);
 };
 
 template <typename T>
@@ -310,15 +315,12 @@ struct Ctx : CtxBase {
     for (int k = 0; k < L; ++k) { const double a = -2.0 * M_PI * k / L; tw[k] = mk<T>((T)std::cos(a), (T)std::sin(a)); }
     upload(ax.chirp, wc); upload(ax.bhat, bh); upload(ax.tw, tw);
   }
-  // Slice window of the any-size launches (set by Flow::GenWindow around the launches of one group of slices, which then go to that
-  // group's stream): every transform launch covers slices [gw0, gw0 + gwn) of the gwall slices of the flow -- of each part of its batch
-  // when that is a multiple of gwall (pair launches).  gwn < 0: no window.
-  long gw0 = 0, gwn = -1, gwall = 0;
-  long gen_window(GenDft<T>& a, long slices) const {
-    if (gwn < 0) return slices;
-    CMBL_REQUIRE(gwall > 0 && slices % gwall == 0, ERR_STATE, "any-size launch outside its slice window");
-    a.sl0 = (int)gw0; a.sln = (int)gwn; a.slstride = (int)gwall;
-    return slices / gwall * gwn;
+  // the slice window of run r in the argument block of a transform launch over `slices` slices; returns the slices the launch covers
+  static long gen_window(GenDft<T>& a, long slices, const GenRun& r) {
+    if (r.sln < 0) return slices;
+    CMBL_REQUIRE(r.slall > 0 && slices % r.slall == 0, ERR_STATE, "any-size launch outside its slice window");
+    a.sl0 = (int)r.sl0; a.sln = (int)r.sln; a.slstride = (int)r.slall;
+    return slices / r.slall * r.sln;
   }
   // lengths with a compile-time plan (kernels_ct.hpp): one wavefront per sequence, S = 64 bytes of sequences per workgroup
   // rows per workgroup of an x-pass launch over `rows` contiguous rows (`per`: wavefronts per row): the full group of ct_S wavefronts unless the
@@ -335,70 +337,78 @@ struct Ctx : CtxBase {
   // side) unless the launch would then have fewer than 0.4 workgroups per CU -- then half (32-byte pieces, but transform phases with half the
   // wavefronts per SIMD).  Measured (profiles/r06_ab_anysize_col_groups.txt): 768^2 QU, 96 groups per slice chain: (grad L)' -6 %, grad lnP -3 %;
   // 1000^2 QU, 125 groups: +5 % -- hence the 0.4.  Option gen_ct_rows switches it off with the row groups.
-  int ct_cols_per_group(long cols, long slices, int S) const {
+  int ct_cols_per_group(long cols, long slices, int S, int tile) const {
     if (!opts.gen_ct_rows || S != ct_S<T>() || opts.gen_ct_cols == 0) return S;
     if (opts.gen_ct_cols == 2) return S / 2;
-    // tiled hand-off arrays (htile), 8-byte elements: 4 columns are ONE block -- contiguous at either width -- and the half-width group won at every
+    // tiled hand-off arrays (tile != 0), 8-byte elements: 4 columns are ONE block -- contiguous at either width -- and the half-width group won at every
     // size and batch measured (1000^2 QU grad lnP -3.7 %, 1536^2 -4.7 %, 1000^2 T+QU -9 %, 768^2 QU at B = 4 -14.5 %; never slower:
     // profiles/r06_ab_anysize_tiled_cols.txt).  16-byte elements: the full group IS one block (half of it: +1...+3 % at 768^2 / 1000^2)
-    if (htile && sizeof(T) == 4) return S / 2;
+    if (tile && sizeof(T) == 4) return S / 2;
     return ((cols + S - 1) / S) * slices * 5 < 2L * num_cus ? S / 2 : S;
   }
-  bool gen_dft_ct(const GenAxis& ax, GenDft<T> a, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
-  void gen_dft(const GenAxis& ax, GenDft<T> a, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
-  // (the mixed scratch between the two launches of a 2-D transform is a hand-off array like those of the flows: tiled under bit 8 of gen_tiled)
-  struct HandOff2D {
-    Ctx<T>* c; int keep;
-    explicit HandOff2D(Ctx<T>* c_) : c(c_), keep(c_->htile) { c->htile = (c->opts.gen_tiled & 8) ? c->gen_tile() : 0; }
-    ~HandOff2D() { c->htile = keep; }
-  };
-  void gen_rfft2(const T* map, cx<T>* F, long slices) {
-    cx<T>* tmp = mixed_scratch(slices);
-    HandOff2D ho(this);
-    GenDft<T> a{};                                                          // y: map [x][y] -> tmp [ky][x]
-    a.in = map; a.out = tmp; a.in_real = 1; a.nin = Ny; a.nout = Nyh; a.nseq = Nx; a.scale = 1;
-    a.in_seq = Ny; a.in_elem = 1; a.in_slice = npix(); a.out_seq = 1; a.out_elem = Nx; a.out_slice = plane();
-    hand_out<1>(a);
-    gen_dft(genY, a, slices);
-    GenDft<T> b{};                                                          // x: tmp [ky][x] -> F [ky][kx]
-    b.in = tmp; b.out = F; b.nin = Nx; b.nout = Nx; b.nseq = Nyh; b.scale = 1;
+  bool gen_dft_ct(const GenRun& r, const GenAxis& ax, GenDft<T> a, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
+  void gen_dft(const GenRun& r, const GenAxis& ax, GenDft<T> a, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
+  // The two argument-block layouts of the any-size launches.  x pass: length Nx along the rows of [ky][x] (or [ky][kx]) half planes.
+  GenDft<T> gen_xpass() const {
+    GenDft<T> b{};
+    b.nin = Nx; b.nout = Nx; b.nseq = Nyh; b.scale = 1;
     b.in_seq = Nx; b.in_elem = 1; b.in_slice = plane(); b.out_seq = Nx; b.out_elem = 1; b.out_slice = plane();
-    hand_in<2>(b);
-    gen_dft(genX, b, slices);
+    return b;
   }
-  void gen_irfft2(const cx<T>* F, T* map, long slices) {
+  // y pass between [x][y] maps and [ky][x] half planes: r2c map -> half plane, or (c2r) the Hermitian half plane -> map
+  GenDft<T> gen_ypass(bool c2r) const {
+    GenDft<T> a{};
+    a.nseq = Nx;
+    if (c2r) {
+      a.herm = 1; a.out_real = 1; a.inverse = 1; a.nin = Nyh; a.nout = Ny;
+      a.in_seq = 1; a.in_elem = Nx; a.in_slice = plane(); a.out_seq = Ny; a.out_elem = 1; a.out_slice = npix();
+    } else {
+      a.in_real = 1; a.nin = Ny; a.nout = Nyh;
+      a.in_seq = Ny; a.in_elem = 1; a.in_slice = npix(); a.out_seq = 1; a.out_elem = Nx; a.out_slice = plane();
+    }
+    return a;
+  }
+  // (the mixed scratch between the two launches of a 2-D transform is a hand-off array like those of the flows: tiled under bit 8 of gen_tiled,
+  //  whatever the caller's run says)
+  void gen_rfft2(GenRun r, const T* map, cx<T>* F, long slices) {
     cx<T>* tmp = mixed_scratch(slices);
-    HandOff2D ho(this);
-    GenDft<T> b{};                                                          // x (inverse): F [ky][kx] -> tmp [ky][x]
-    b.in = F; b.out = tmp; b.nin = Nx; b.nout = Nx; b.nseq = Nyh; b.scale = 1; b.inverse = 1;
-    b.in_seq = Nx; b.in_elem = 1; b.in_slice = plane(); b.out_seq = Nx; b.out_elem = 1; b.out_slice = plane();
-    hand_out<2>(b);
-    gen_dft(genX, b, slices);
-    GenDft<T> a{};                                                          // y (c2r): tmp [ky][x] -> map [x][y]
-    a.in = tmp; a.out = map; a.herm = 1; a.out_real = 1; a.inverse = 1; a.nin = Nyh; a.nout = Ny; a.nseq = Nx;
-    a.scale = (T)(1.0 / ((double)Ny * Nx));
-    a.in_seq = 1; a.in_elem = Nx; a.in_slice = plane(); a.out_seq = Ny; a.out_elem = 1; a.out_slice = npix();
-    hand_in<1>(a);
-    gen_dft(genY, a, slices);
+    r.tile = (opts.gen_tiled & 8) ? gen_tile() : 0;
+    GenDft<T> a = gen_ypass(false);                                         // y: map [x][y] -> tmp [ky][x]
+    a.in = map; a.out = tmp; a.scale = 1;
+    hand_out<1>(a, r);
+    gen_dft(r, genY, a, slices);
+    GenDft<T> b = gen_xpass();                                              // x: tmp [ky][x] -> F [ky][kx]
+    b.in = tmp; b.out = F;
+    hand_in<2>(b, r);
+    gen_dft(r, genX, b, slices);
+  }
+  void gen_irfft2(GenRun r, const cx<T>* F, T* map, long slices) {
+    cx<T>* tmp = mixed_scratch(slices);
+    r.tile = (opts.gen_tiled & 8) ? gen_tile() : 0;
+    GenDft<T> b = gen_xpass();                                              // x (inverse): F [ky][kx] -> tmp [ky][x]
+    b.in = F; b.out = tmp; b.inverse = 1;
+    hand_out<2>(b, r);
+    gen_dft(r, genX, b, slices);
+    GenDft<T> a = gen_ypass(true);                                          // y (c2r): tmp [ky][x] -> map [x][y]
+    a.in = tmp; a.out = map; a.scale = (T)(1.0 / ((double)Ny * Nx));
+    hand_in<1>(a, r);
+    gen_dft(r, genY, a, slices);
   }
   // Separable pieces of the any-size path (mixed layout [slice][ky][x], like the fused kernels use between their column and row passes):
   // the y transform alone (one real map, or TWO real maps per complex transform), the x transform alone with an optional i*lx multiply
   // in its store, and the pair c2r that returns (d/dx f, d/dy f) from (Gx, A) with the i*ly multiply in its fetch.
-  void gen_y_r2c(const T* map, cx<T>* A, long slices, const T* map2 = nullptr, cx<T>* A2 = nullptr, const GenPro<T>* pro = nullptr) {
-    GenDft<T> a{};
+  void gen_y_r2c(const GenRun& r, const T* map, cx<T>* A, long slices, const T* map2 = nullptr, cx<T>* A2 = nullptr, const GenPro<T>* pro = nullptr) {
+    GenDft<T> a = gen_ypass(false);
     if (pro) a.pro = *pro;
-    a.in = map; a.out = A; a.in2 = map2; a.out2 = A2; a.in_real = 1; a.nin = Ny; a.nout = Nyh; a.nseq = Nx; a.scale = 1; a.scale2 = 1;
-    a.in_seq = Ny; a.in_elem = 1; a.in_slice = npix(); a.out_seq = 1; a.out_elem = Nx; a.out_slice = plane();
-    hand_out<1>(a);
-    gen_dft(genY, a, slices);
+    a.in = map; a.out = A; a.in2 = map2; a.out2 = A2; a.scale = 1; a.scale2 = 1;
+    hand_out<1>(a, r);
+    gen_dft(r, genY, a, slices);
   }
-  void gen_y_c2r_pair(const cx<T>* G1, const cx<T>* G2, const T* lmul2, T* o1, T* o2, T s1, T s2, long slices) {
-    GenDft<T> a{};
-    a.in = G1; a.in2 = G2; a.lmul_in = lmul2; a.out = o1; a.out2 = o2; a.herm = 1; a.out_real = 1; a.inverse = 1; a.nin = Nyh; a.nout = Ny; a.nseq = Nx;
-    a.scale = s1; a.scale2 = s2;
-    a.in_seq = 1; a.in_elem = Nx; a.in_slice = plane(); a.out_seq = Ny; a.out_elem = 1; a.out_slice = npix();
-    hand_in<1>(a);
-    gen_dft(genY, a, slices);
+  void gen_y_c2r_pair(const GenRun& r, const cx<T>* G1, const cx<T>* G2, const T* lmul2, T* o1, T* o2, T s1, T s2, long slices) {
+    GenDft<T> a = gen_ypass(true);
+    a.in = G1; a.in2 = G2; a.lmul_in = lmul2; a.out = o1; a.out2 = o2; a.scale = s1; a.scale2 = s2;
+    hand_in<1>(a, r);
+    gen_dft(r, genY, a, slices);
   }
   // the y axis has a compile-time plan (and they are switched on): the fused y passes of a flow stage exist
   bool gen_ct_y() const {
@@ -412,15 +422,15 @@ struct Ctx : CtxBase {
   }
   // pair c2r of (G1, i ly G2) + the stage's velocity / RK update on the maps of `pro` + rfft_y of the next stage input -> Anext, one launch
   // (GenDft::yy, kernels_ct.hpp ct_flow_stage); last: the flow ends, only y0 is updated
-  void gen_y_flow_stage(const cx<T>* G1, const cx<T>* G2, const T* lmul2, T s1, T s2, const GenPro<T>& pro, cx<T>* Anext, bool last, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
+  void gen_y_flow_stage(const GenRun& r, const cx<T>* G1, const cx<T>* G2, const T* lmul2, T s1, T s2, const GenPro<T>& pro, cx<T>* Anext, bool last, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
   // ... and the four y passes of a delta-flow stage (two LDS rows per column: up to Ny ~ 1150)
   bool gen_ct_y2() const { return gen_ct_y() && ct_lds<T>(Ny, 2, ct_S2<T>(Ny)) <= 160 * 1024; }
   // c2r of T3 = ifft_x(delta f) -> L(df), pair c2r of (G1, i ly G2) -> grad f, the delta stage's pointwise work on the maps of `pro`
   // (w1p, w2p, y0, acc), rfft_y of the next f -> Anext, pair r2c of (p_x, p_y) L(df) -> (W2a, W2b): one launch (k_ct_delta_y)
-  void gen_y_delta_stage(const cx<T>* T3, T s3, const cx<T>* G1, const cx<T>* G2, const T* lmul2, T s1, T s2, const GenPro<T>& pro, cx<T>* Anext,                          cx<T>* W2a, cx<T>* W2b, bool last, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
+  void gen_y_delta_stage(const GenRun& r, const cx<T>* T3, T s3, const cx<T>* G1, const cx<T>* G2, const T* lmul2, T s1, T s2, const GenPro<T>& pro, cx<T>* Anext, cx<T>* W2a, cx<T>* W2b, bool last, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
   // fft_x of the pair (W2a, W2b) and the RK update of the Fourier state (Y0, acc -> Ys) with k = i lx Fx + i ly Fy in ONE launch where the x axis has
   // a compile-time plan; false: not available (the caller runs the x transform and k_gen_adj_rk)
-  bool gen_x_adj_update(const cx<T>* W2a, const cx<T>* W2b, cx<T>* Y0, cx<T>* acc_, cx<T>* Ys, const RKCoef<T>& rk, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
+  bool gen_x_adj_update(const GenRun& r, const cx<T>* W2a, const cx<T>* W2b, cx<T>* Y0, cx<T>* acc_, cx<T>* Ys, const RKCoef<T>& rk, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
   // the x axis has a compile-time plan: the row update of an adjoint-type stage can open the next stage in the same launch (gen_x_adj_next)
   bool gen_ct_x() const {
     if (!opts.gen_ct || !opts.gen_yy || !opts.gen_xmerge || genX.plan.nf == 0 || !ct_rowfuse_ok<T>(Nx)) return false;
@@ -437,39 +447,35 @@ struct Ctx : CtxBase {
     if (!opts.gen_tiled || !opts.gen_separable || !opts.gen_prologue || !opts.gen_xderiv_fused || (Nx & 3) || !gen_ct_x() || !gen_ct_y()) return 0;
     return (Nyh + 3) & ~3;
   }
-  // set by a flow around its stages (Flow::HandOff): the layout of gA / gGx / gW2 / the mixed scratch in the launches below; slice stride hplane()
-  int htile = 0;
-  long hplane() const { return htile ? mplane() : plane(); }
-  template <int SIDE /*1: y kernel (sequence = x), 2: x kernel (element = x)*/> void hand_in(GenDft<T>& a) const { if (htile) { a.in_tiled = SIDE; a.tile_np = htile; a.in_slice = mplane(); } }
-  template <int SIDE> void hand_out(GenDft<T>& a) const { if (htile) { a.out_tiled = SIDE; a.tile_np = htile; a.out_slice = mplane(); } }
+  // the input / output of a launch is a hand-off array (gA / gGx / gW2 / the mixed scratch of a flow): tiled when the run says so, slice stride mplane()
+  template <int SIDE /*1: y kernel (sequence = x), 2: x kernel (element = x)*/> void hand_in(GenDft<T>& a, const GenRun& r) const { if (r.tile) { a.in_tiled = SIDE; a.tile_np = r.tile; a.in_slice = mplane(); } }
+  template <int SIDE> void hand_out(GenDft<T>& a, const GenRun& r) const { if (r.tile) { a.out_tiled = SIDE; a.tile_np = r.tile; a.out_slice = mplane(); } }
   // row groups of an x launch on tiled arrays: a multiple of 8, so that xcd_tile (kernels_fft.hpp) puts the groups that share 128-byte lines on one XCD
   static long xgroups(long groups, bool tiled) { return tiled ? (groups + 7) & ~7L : groups; }
-  void gen_x_adj_next(const cx<T>* W2a, const cx<T>* W2b, cx<T>* Y0, cx<T>* acc_, const RKCoef<T>& rk, cx<T>* t3, const cx<T>* A_next, cx<T>* gx, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
+  void gen_x_adj_next(const GenRun& r, const cx<T>* W2a, const cx<T>* W2b, cx<T>* Y0, cx<T>* acc_, const RKCoef<T>& rk, cx<T>* t3, const cx<T>* A_next, cx<T>* gx, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
   // t3 = ifft_x(F) (unnormalised) and gx = ifft_x(i lx fft_x(A)) in ONE launch where the x axis has a compile-time plan (else two launches)
-  void gen_x_inv_and_deriv(const cx<T>* F, cx<T>* t3, const cx<T>* A_, cx<T>* gx, cx<T>* tmp, const T* lx, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
+  void gen_x_inv_and_deriv(const GenRun& r, const cx<T>* F, cx<T>* t3, const cx<T>* A_, cx<T>* gx, cx<T>* tmp, const T* lx, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
   // c2r of T3 = ifft_x(y) -> y, (p_x y, p_y y) at stage time t, its pair r2c -> (W2a, W2b): the y passes of an adjoint stage in one launch
-  void gen_y_adj_stage(const cx<T>* T3, T s3, const PhiMaps<T>& phm, T t, int P, cx<T>* W2a, cx<T>* W2b, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
+  void gen_y_adj_stage(const GenRun& r, const cx<T>* T3, T s3, const PhiMaps<T>& phm, T t, int P, cx<T>* W2a, cx<T>* W2b, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
   // out = ifft_x(i lx fft_x(in)) unnormalised, in ONE launch when the axis has a mixed-radix plan (else two: chirp-z transforms)
-  bool gen_x_deriv(const cx<T>* in, cx<T>* out, cx<T>* tmp, const T* lx, long slices) {
+  bool gen_x_deriv(const GenRun& r, const cx<T>* in, cx<T>* out, cx<T>* tmp, const T* lx, long slices) {
     if (genX.plan.nf == 0 || !opts.gen_xderiv_fused) {
-      gen_x(in, tmp, false, lx, slices);
-      gen_x(tmp, out, true, nullptr, slices);
+      gen_x(r, in, tmp, false, lx, slices);
+      gen_x(r, tmp, out, true, nullptr, slices);
       return false;
     }
-    GenDft<T> b{};
-    b.in = in; b.out = out; b.nin = Nx; b.nout = Nx; b.nseq = Nyh; b.scale = 1; b.lmul_mid = lx;
-    b.in_seq = Nx; b.in_elem = 1; b.in_slice = plane(); b.out_seq = Nx; b.out_elem = 1; b.out_slice = plane();
-    hand_in<2>(b); hand_out<2>(b);
-    gen_dft(genX, b, slices);
+    GenDft<T> b = gen_xpass();
+    b.in = in; b.out = out; b.lmul_mid = lx;
+    hand_in<2>(b, r); hand_out<2>(b, r);
+    gen_dft(r, genX, b, slices);
     return true;
   }
-  void gen_x(const cx<T>* in, cx<T>* out, bool inverse, const T* lmul_out, long slices, bool hand_i = false, bool hand_o = false) {
-    GenDft<T> b{};
-    b.in = in; b.out = out; b.nin = Nx; b.nout = Nx; b.nseq = Nyh; b.scale = 1; b.inverse = inverse ? 1 : 0; b.lmul_out = lmul_out;
-    b.in_seq = Nx; b.in_elem = 1; b.in_slice = plane(); b.out_seq = Nx; b.out_elem = 1; b.out_slice = plane();
-    if (hand_i) hand_in<2>(b);
-    if (hand_o) hand_out<2>(b);
-    gen_dft(genX, b, slices);
+  void gen_x(const GenRun& r, const cx<T>* in, cx<T>* out, bool inverse, const T* lmul_out, long slices, bool hand_i = false, bool hand_o = false) {
+    GenDft<T> b = gen_xpass();
+    b.in = in; b.out = out; b.inverse = inverse ? 1 : 0; b.lmul_out = lmul_out;
+    if (hand_i) hand_in<2>(b, r);
+    if (hand_o) hand_out<2>(b, r);
+    gen_dft(r, genX, b, slices);
   }
   template <typename V> void transpose(const V* in, V* out, int R, int C, long slices) {
     CMBL_LAUNCH(this, K_LAYOUT, (k_transpose<V>), dim3((C + 31) / 32, (R + 31) / 32, (unsigned)slices), 0, stream, in, out, R, C);
@@ -662,9 +668,9 @@ struct Ctx : CtxBase {
   // map -> F  (m_rfft, src/util_fft.jl:20)
   // (the x pass reads the tiled mixed layout and writes F rows, or the reverse: it cannot run in place -- `xtmp` holds the mixed side)
   cx<T>* mixed_scratch(long slices) { xtmp.ensure(sizeof(cx<T>) * slices * mplane()); return xtmp.as<cx<T>>(); }
-  void rfft2_F(const T* map, cx<T>* F, long slices) { if (generic) return gen_rfft2(map, F, slices); cx<T>* m = mixed_scratch(slices); y_r2c(map, m, slices); x_pass<0>(m, F, slices); }
+  void rfft2_F(const T* map, cx<T>* F, long slices) { if (generic) return gen_rfft2(GenRun{stream}, map, F, slices); cx<T>* m = mixed_scratch(slices); y_r2c(map, m, slices); x_pass<0>(m, F, slices); }
   // F -> map without a caller-provided scratch (F is left intact)
-  void F_to_map(const cx<T>* F, T* map, long slices) { if (generic) return gen_irfft2(F, map, slices); cx<T>* m = mixed_scratch(slices); x_pass<1>(F, m, slices); y_c2r(m, map, slices); }
+  void F_to_map(const cx<T>* F, T* map, long slices) { if (generic) return gen_irfft2(GenRun{stream}, F, map, slices); cx<T>* m = mixed_scratch(slices); x_pass<1>(F, m, slices); y_c2r(m, map, slices); }
 
   // harmonic-operator application (see k_harm_apply)
   void harm(const cx<T>* in, cx<T>* out, int P, int B, int kind, const T* const* d, bool transpose, bool in_qu, bool out_qu,
@@ -1039,11 +1045,9 @@ struct Flow {
   // ---- any-size path: the reference's pass structure on k_gen_dft + pointwise kernels (kernels_generic.hpp) ----------------------
   // (x, y) pairs live in the two halves of ONE buffer so that both members go through a transform in one launch
   DevBuf gF, gFxy, gmxy, gms, gYs, gLdf, gWxy;
-  // (pointwise launches of a stage: over the slice window when one is set)
-  long wsl(long slices) const { return c->gwn >= 0 ? c->gwn : slices; }
-  int wsl0() const { return c->gwn >= 0 ? (int)c->gw0 : 0; }
-  dim3 pgrid(long n, long slices) const { return dim3((unsigned)std::min<long>((n + NTP - 1) / NTP, 4096), (unsigned)wsl(slices)); }
-  dim3 fgrid(long slices) const { return dim3((unsigned)((c->plane() + NTP - 1) / NTP), (unsigned)wsl(slices)); }
+  // (pointwise launches of a stage: over the slice window of the run; the kernels take its first slice r.sl0)
+  dim3 pgrid(long n, long slices, const GenRun& r) const { return dim3((unsigned)std::min<long>((n + NTP - 1) / NTP, 4096), (unsigned)(r.sln < 0 ? slices : r.sln)); }
+  dim3 fgrid(long slices, const GenRun& r) const { return dim3((unsigned)((c->plane() + NTP - 1) / NTP), (unsigned)(r.sln < 0 ? slices : r.sln)); }
   // One launch chain per group of slices for the flows of the any-size path, like the fused flows (groups()): a launch there is one
   // residency round of workgroups that all fetch, then all transform, then all store (k_ct_dft stamps: each phase alone runs at
   // 3 - 5 TB/s and the memory system idles during the transforms), so two chains side by side fill each other's gaps.
@@ -1067,59 +1071,53 @@ struct Flow {
     }
     return 1;
   }
-  struct GenWindow {                                                    // RAII: the launches of group g of K go to its stream
-    Ctx<T>* c; hipStream_t main;
-    GenWindow(Flow* f, int g, int K, long slices) : c(f->c), main(f->c->stream) {
-      if (K <= 1) return;
-      c->gwall = slices; c->gwn = slices / K; c->gw0 = g * (slices / K);
-      c->stream = g == 0 ? main : f->sub[g - 1];
-    }
-    ~GenWindow() { c->stream = main; c->gwn = -1; c->gw0 = 0; c->gwall = 0; }
-  };
+  // the run of chain g of K over `slices` slices (its stream and slice window) with hand-off layout `tile`; K = 1: all slices on the main stream
+  GenRun gen_run(int g, int K, long slices, int tile) const {
+    if (K <= 1) return GenRun{c->stream, 0, -1, 0, tile};
+    return GenRun{gstream(g), g * (slices / K), slices / K, slices, tile};
+  }
+  // layout of the hand-off arrays of a flow: tiled when the flow runs its fused stages and Ctx::gen_tile() allows
+  int gen_flow_tile(bool fused, int kind /*option gen_tiled: 1 map flows, 2 adjoint flows, 4 delta flows*/) const {
+    return fused && (c->opts.gen_tiled & kind) ? c->gen_tile() : 0;
+  }
   // (gmx, gmy) = grad of the stage input f_s from its y transform A = rfft_y(f_s) (mixed layout), using the separability the fused
   // kernels use: d/dy needs the y transform alone (the i*ly multiply commutes with the x transforms, which then cancel), d/dx one
   // forward / i*lx / inverse x pass; ONE complex inverse y transform returns both real maps (pair c2r).  Equal to the reference's
   // rfft2 -> (i lx, i ly) -> 2 x irfft2 (src/lenseflow.jl:155-157) incl. FFTW's c2r rule at ky = 0 / Nyquist, in 3 launches and
   // 3 slice-passes instead of 5 launches and 7.5.  CMBL_GEN_SEPARABLE=0: the reference's own pass structure (kept for A/B).
   DevBuf gA, gGx, gT, gW2;
-  // layout of the hand-off arrays for the launches of one flow (Ctx::htile): tiled when the flow runs its fused stages and Ctx::gen_tile() allows
-  struct HandOff {
-    Ctx<T>* c;
-    HandOff(Ctx<T>* c_, bool fused, int kind /*option gen_tiled: 1 map flows, 2 adjoint flows, 4 delta flows*/) : c(c_) { c->htile = fused && (c->opts.gen_tiled & kind) ? c->gen_tile() : 0; }
-    ~HandOff() { c->htile = 0; }
-  };
   bool gen_sep() const { return c->opts.gen_separable != 0; }
-  void gen_grad_sep(const cx<T>* A_, long slices) {
+  void gen_grad_sep(const GenRun& r, const cx<T>* A_, long slices) {
     const long pl = c->plane(), np = c->npix();
     gT.ensure(sizeof(cx<T>) * slices * pl); gGx.ensure(sizeof(cx<T>) * slices * pl); gmxy.ensure(sizeof(T) * 2 * slices * np);
-    c->gen_x_deriv(A_, gGx.as<cx<T>>(), gT.as<cx<T>>(), c->lx_r.template as<T>(), slices);     // Nx * d/dx in mixed space: ifft_x(i lx fft_x(A))
-    c->gen_y_c2r_pair(gGx.as<cx<T>>(), A_, c->ly.template as<T>(), gmxy.as<T>(), gmxy.as<T>() + slices * np,
+    c->gen_x_deriv(r, A_, gGx.as<cx<T>>(), gT.as<cx<T>>(), c->lx_r.template as<T>(), slices);     // Nx * d/dx in mixed space: ifft_x(i lx fft_x(A))
+    c->gen_y_c2r_pair(r, gGx.as<cx<T>>(), A_, c->ly.template as<T>(), gmxy.as<T>(), gmxy.as<T>() + slices * np,
                       (T)(1.0 / ((double)c->Ny * c->Nx)), (T)(1.0 / (double)c->Ny), slices);
   }
   // (gmx, gmy) = grad of the map `ys`  (rfft2, i l multiplies, irfft2 of both components)
-  void gen_grad(const T* ys, long slices) {
+  void gen_grad(const GenRun& r, const T* ys, long slices) {
     const long pl = c->plane(), np = c->npix();
     gF.ensure(sizeof(cx<T>) * slices * pl); gFxy.ensure(sizeof(cx<T>) * 2 * slices * pl); gmxy.ensure(sizeof(T) * 2 * slices * np);
-    c->rfft2_F(ys, gF.as<cx<T>>(), slices);
-    CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_lmul2<T>), fgrid(slices), 0, c->stream, gF.as<cx<T>>(), gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * pl,
+    c->gen_rfft2(r, ys, gF.as<cx<T>>(), slices);
+    CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_lmul2<T>), fgrid(slices, r), 0, r.st, gF.as<cx<T>>(), gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * pl,
                 c->lx_r.template as<T>(), c->ly.template as<T>(), c->Nx, pl);
-    c->F_to_map(gFxy.as<cx<T>>(), gmxy.as<T>(), 2 * slices);
+    c->gen_irfft2(r, gFxy.as<cx<T>>(), gmxy.as<T>(), 2 * slices);
   }
   // d(Fourier state)/dt from the maps (Wx, Wy) = the halves of Wxy: rfft2 of both + the RK update with k = i lx Fx + i ly Fy
   // (separable form: the two real maps go through ONE complex y transform, then one x launch over both)
   bool gen_pro() const { return c->opts.gen_prologue != 0; }
-  void gen_adj_update(const T* Wxy, cx<T>* Y0, cx<T>* Yacc_, cx<T>* Ys, const RKCoef<T>& rk, long slices, const GenPro<T>* pro = nullptr) {
+  void gen_adj_update(const GenRun& r, const T* Wxy, cx<T>* Y0, cx<T>* Yacc_, cx<T>* Ys, const RKCoef<T>& rk, long slices, const GenPro<T>* pro = nullptr) {
     const long pl = c->plane(), np = c->npix();
     gFxy.ensure(sizeof(cx<T>) * 2 * slices * pl);
     if (gen_sep()) {
       gW2.ensure(sizeof(cx<T>) * 2 * slices * pl);
       // pro (mode 3): the pair is formed in the fetch from L(df) and p; `in` / `in2` only mark the launch as a real pair
-      if (pro) c->gen_y_r2c(pro->Ldf, gW2.as<cx<T>>(), slices, pro->Ldf, gW2.as<cx<T>>() + slices * pl, pro);
-      else c->gen_y_r2c(Wxy, gW2.as<cx<T>>(), slices, Wxy + slices * np, gW2.as<cx<T>>() + slices * pl);
-      c->gen_x(gW2.as<cx<T>>(), gFxy.as<cx<T>>(), false, nullptr, 2 * slices, true, false);
-    } else c->rfft2_F(Wxy, gFxy.as<cx<T>>(), 2 * slices);
-    CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_adj_rk<T>), fgrid(slices), 0, c->stream, gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * pl, c->lx_r.template as<T>(),
-                c->ly.template as<T>(), c->Nx, Y0, Yacc_, Ys, rk, pl, wsl0());
+      if (pro) c->gen_y_r2c(r, pro->Ldf, gW2.as<cx<T>>(), slices, pro->Ldf, gW2.as<cx<T>>() + slices * pl, pro);
+      else c->gen_y_r2c(r, Wxy, gW2.as<cx<T>>(), slices, Wxy + slices * np, gW2.as<cx<T>>() + slices * pl);
+      c->gen_x(r, gW2.as<cx<T>>(), gFxy.as<cx<T>>(), false, nullptr, 2 * slices, true, false);
+    } else c->gen_rfft2(r, Wxy, gFxy.as<cx<T>>(), 2 * slices);
+    CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_adj_rk<T>), fgrid(slices, r), 0, r.st, gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * pl, c->lx_r.template as<T>(),
+                c->ly.template as<T>(), c->Nx, Y0, Yacc_, Ys, rk, pl, (int)r.sl0);
   }
   void gen_flow_map(const T* in, T* out, int P, int B, bool inverse) {
     const long slices = (long)P * B, np = c->npix();
@@ -1129,9 +1127,9 @@ struct Flow {
     const double t0 = inverse ? 1.0 : 0.0, h = (inverse ? -1.0 : 1.0) / n;
     const bool sep = gen_sep();
     const bool yy = sep && gen_pro() && c->opts.gen_yy && c->opts.gen_xderiv_fused && c->gen_ct_y();
-    HandOff ho(c, yy, 1);
-    const long pl = c->hplane();
-    if (sep) { gA.ensure(sizeof(cx<T>) * slices * pl); c->gen_y_r2c(gms.as<T>(), gA.as<cx<T>>(), slices); }
+    const int tile = gen_flow_tile(yy, 1);
+    const long pl = tile ? c->mplane() : c->plane();
+    if (sep) { gA.ensure(sizeof(cx<T>) * slices * pl); c->gen_y_r2c(gen_run(0, 1, slices, tile), gms.as<T>(), gA.as<cx<T>>(), slices); }
     const int K = gen_groups(slices);
     // every scratch buffer a stage can grow is sized BEFORE the chains fork: a growth (hipFree / hipMalloc) inside the multi-stream region
     // would pull a buffer from under a launch of another chain (the separate-launch path used to ensure inside gen_grad_sep / gen_grad)
@@ -1143,25 +1141,25 @@ struct Flow {
         const bool last = step == n - 1 && stage == 4;
         const RKCoef<T> rk = coef(step, stage, t0, h, last);
         for (int g = 0; g < K; ++g) {
-          GenWindow w(this, g, K, slices);
+          const GenRun r = gen_run(g, K, slices, tile);
           if (yy) {                                                          // d/dx pass, then every y pass of the stage in one launch
             GenPro<T> e{};
             e.mode = 1; e.ph = ph(rk.t); e.rk = rk; e.y0 = out; e.acc = acc.as<T>(); e.npix = np; e.P = P;
-            c->gen_x_deriv(gA.as<cx<T>>(), gGx.as<cx<T>>(), gT.as<cx<T>>(), c->lx_r.template as<T>(), slices);
-            c->gen_y_flow_stage(gGx.as<cx<T>>(), gA.as<cx<T>>(), c->ly.template as<T>(), (T)(1.0 / ((double)c->Ny * c->Nx)), (T)(1.0 / (double)c->Ny), e,
+            c->gen_x_deriv(r, gA.as<cx<T>>(), gGx.as<cx<T>>(), gT.as<cx<T>>(), c->lx_r.template as<T>(), slices);
+            c->gen_y_flow_stage(r, gGx.as<cx<T>>(), gA.as<cx<T>>(), c->ly.template as<T>(), (T)(1.0 / ((double)c->Ny * c->Nx)), (T)(1.0 / (double)c->Ny), e,
                                 gA.as<cx<T>>(), last, slices);
             continue;
           }
-          if (sep) gen_grad_sep(gA.as<cx<T>>(), slices); else gen_grad(gms.as<T>(), slices);
+          if (sep) gen_grad_sep(r, gA.as<cx<T>>(), slices); else gen_grad(r, gms.as<T>(), slices);
           if (sep && !last && gen_pro()) {                                   // velocity + RK bookkeeping in the fetch of the next stage's y transform
             GenPro<T> e{};
             e.mode = 1; e.ph = ph(rk.t); e.rk = rk; e.gx = gmxy.as<T>(); e.gy = gmxy.as<T>() + slices * np; e.y0 = out; e.acc = acc.as<T>(); e.npix = np; e.P = P;
-            c->gen_y_r2c(gms.as<T>(), gA.as<cx<T>>(), slices, nullptr, nullptr, &e);
+            c->gen_y_r2c(r, gms.as<T>(), gA.as<cx<T>>(), slices, nullptr, nullptr, &e);
             continue;
           }
-          CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_vel_rk<T>), pgrid(np, slices), 0, c->stream, gmxy.as<T>(), gmxy.as<T>() + slices * np, ph(rk.t), out, acc.as<T>(),
-                      gms.as<T>(), rk, np, P, wsl0());
-          if (sep && !last) c->gen_y_r2c(gms.as<T>(), gA.as<cx<T>>(), slices);
+          CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_vel_rk<T>), pgrid(np, slices, r), 0, r.st, gmxy.as<T>(), gmxy.as<T>() + slices * np, ph(rk.t), out, acc.as<T>(),
+                      gms.as<T>(), rk, np, P, (int)r.sl0);
+          if (sep && !last) c->gen_y_r2c(r, gms.as<T>(), gA.as<cx<T>>(), slices);
         }
       }
     join(K);
@@ -1174,8 +1172,8 @@ struct Flow {
     CMBL_HIP(hipMemcpyAsync(gYs.p, out, sizeof(cx<T>) * slices * pl, hipMemcpyDeviceToDevice, c->stream));
     const double t0 = inverse ? 0.0 : 1.0, h = (inverse ? 1.0 : -1.0) / n;
     const bool yy = gen_sep() && c->opts.gen_yy && c->gen_ct_y();
-    HandOff ho(c, yy, 2);
-    const long hpl = c->hplane();                                          // (the pair W2 and the mixed scratch t3 are hand-off arrays; the Fourier state is not)
+    const int tile = gen_flow_tile(yy, 2);
+    const long hpl = tile ? c->mplane() : c->plane();                                          // (the pair W2 and the mixed scratch t3 are hand-off arrays; the Fourier state is not)
     gFxy.ensure(sizeof(cx<T>) * 2 * slices * pl); gW2.ensure(sizeof(cx<T>) * 2 * slices * hpl); (void)c->mixed_scratch(slices);   // before the chains fork
     const int K = gen_groups(slices);
     fork(K);
@@ -1183,22 +1181,22 @@ struct Flow {
       for (int stage = 1; stage <= 4; ++stage) {
         const RKCoef<T> rk = coef(step, stage, t0, h, step == n - 1 && stage == 4);
         for (int g = 0; g < K; ++g) {
-          GenWindow w(this, g, K, slices);
+          const GenRun r = gen_run(g, K, slices, tile);
           if (yy) {                                                          // ifft_x, every y pass of the stage in one launch, fft_x of the pair, RK update
             cx<T>* t3 = c->mixed_scratch(slices);
             const bool mrg = c->gen_ct_x();                                  // the row update of stage s also writes t3 = ifft_x(Ys) of stage s + 1
-            if (!mrg || (step == 0 && stage == 1)) c->gen_x(gYs.as<cx<T>>(), t3, true, nullptr, slices, false, true);
-            c->gen_y_adj_stage(t3, (T)(1.0 / ((double)c->Ny * c->Nx)), ph(rk.t), rk.t, P, gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, slices);
-            if (mrg && !rk.last) { c->gen_x_adj_next(gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, out, Yacc.as<cx<T>>(), rk, t3, nullptr, nullptr, slices); continue; }
-            if (c->gen_x_adj_update(gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, out, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices)) continue;
-            c->gen_x(gW2.as<cx<T>>(), gFxy.as<cx<T>>(), false, nullptr, 2 * slices, true, false);
-            CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_adj_rk<T>), fgrid(slices), 0, c->stream, gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * pl, c->lx_r.template as<T>(),
-                        c->ly.template as<T>(), c->Nx, out, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, pl, wsl0());
+            if (!mrg || (step == 0 && stage == 1)) c->gen_x(r, gYs.as<cx<T>>(), t3, true, nullptr, slices, false, true);
+            c->gen_y_adj_stage(r, t3, (T)(1.0 / ((double)c->Ny * c->Nx)), ph(rk.t), rk.t, P, gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, slices);
+            if (mrg && !rk.last) { c->gen_x_adj_next(r, gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, out, Yacc.as<cx<T>>(), rk, t3, nullptr, nullptr, slices); continue; }
+            if (c->gen_x_adj_update(r, gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, out, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices)) continue;
+            c->gen_x(r, gW2.as<cx<T>>(), gFxy.as<cx<T>>(), false, nullptr, 2 * slices, true, false);
+            CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_adj_rk<T>), fgrid(slices, r), 0, r.st, gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * pl, c->lx_r.template as<T>(),
+                        c->ly.template as<T>(), c->Nx, out, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, pl, (int)r.sl0);
             continue;
           }
-          c->F_to_map(gYs.as<cx<T>>(), gms.as<T>(), slices);
-          CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_pmul<T>), pgrid(np, slices), 0, c->stream, gms.as<T>(), ph(rk.t), rk.t, gmxy.as<T>(), gmxy.as<T>() + slices * np, np, P, wsl0());
-          gen_adj_update(gmxy.as<T>(), out, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices);
+          c->gen_irfft2(r, gYs.as<cx<T>>(), gms.as<T>(), slices);
+          CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_pmul<T>), pgrid(np, slices, r), 0, r.st, gms.as<T>(), ph(rk.t), rk.t, gmxy.as<T>(), gmxy.as<T>() + slices * np, np, P, (int)r.sl0);
+          gen_adj_update(r, gmxy.as<T>(), out, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices);
         }
       }
     join(K);
@@ -1216,9 +1214,9 @@ struct Flow {
     const double t0 = forward_primal ? 1.0 : 0.0, h = (forward_primal ? -1.0 : 1.0) / n;
     const bool sep = gen_sep();
     const bool yy = sep && gen_pro() && c->opts.gen_yy && c->opts.gen_xderiv_fused && c->gen_ct_y2() && c->genX.plan.nf > 0;
-    HandOff ho(c, yy, 4);
-    const long hpl = c->hplane();                                          // (A, Gx, the pair W2 and the mixed scratch t3 are hand-off arrays; the Fourier state is not)
-    if (sep) { gA.ensure(sizeof(cx<T>) * slices * hpl); c->gen_y_r2c(gms.as<T>(), gA.as<cx<T>>(), slices); }
+    const int tile = gen_flow_tile(yy, 4);
+    const long hpl = tile ? c->mplane() : c->plane();                                          // (A, Gx, the pair W2 and the mixed scratch t3 are hand-off arrays; the Fourier state is not)
+    if (sep) { gA.ensure(sizeof(cx<T>) * slices * hpl); c->gen_y_r2c(gen_run(0, 1, slices, tile), gms.as<T>(), gA.as<cx<T>>(), slices); }
     tc_host.resize(2 * (size_t)nst);
     gT.ensure(sizeof(cx<T>) * slices * hpl); gGx.ensure(sizeof(cx<T>) * slices * hpl); gmxy.ensure(sizeof(T) * 2 * slices * np);   // before the chains fork
     gFxy.ensure(sizeof(cx<T>) * 2 * slices * pl); gW2.ensure(sizeof(cx<T>) * 2 * slices * hpl); (void)c->mixed_scratch(slices);
@@ -1232,29 +1230,29 @@ struct Flow {
         tc_host[2 * it + 1] = (T)((stage == 1 || stage == 4 ? 1.0 : 2.0) * h / 6);
         T* w1p = Wst.as<T>() + (size_t)(2 * it) * slices * np;
         for (int g = 0; g < K; ++g) {
-          GenWindow w(this, g, K, slices);
+          const GenRun r = gen_run(g, K, slices, tile);
           if (yy) {
             // x passes (ifft_x of delta f, d/dx of rfft_y(f)), then every y pass of the stage in one launch, then the delta-f velocity's x pass + RK update
             cx<T>* t3 = c->mixed_scratch(slices);
             const bool mrg = c->gen_ct_x();                                  // the row update of stage s also runs both x passes that open stage s + 1
-            if (!mrg || it == 0) c->gen_x_inv_and_deriv(gYs.as<cx<T>>(), t3, gA.as<cx<T>>(), gGx.as<cx<T>>(), gT.as<cx<T>>(), c->lx_r.template as<T>(), slices);
+            if (!mrg || it == 0) c->gen_x_inv_and_deriv(r, gYs.as<cx<T>>(), t3, gA.as<cx<T>>(), gGx.as<cx<T>>(), gT.as<cx<T>>(), c->lx_r.template as<T>(), slices);
             GenPro<T> e{};
             e.mode = 2; e.ph = ph(rk.t); e.rk = rk; e.y0 = f; e.acc = acc.as<T>(); e.w1p = w1p; e.w2p = w1p + (size_t)slices * np; e.npix = np; e.P = P;
-            c->gen_y_delta_stage(t3, (T)(1.0 / ((double)c->Ny * c->Nx)), gGx.as<cx<T>>(), gA.as<cx<T>>(), c->ly.template as<T>(),
+            c->gen_y_delta_stage(r, t3, (T)(1.0 / ((double)c->Ny * c->Nx)), gGx.as<cx<T>>(), gA.as<cx<T>>(), c->ly.template as<T>(),
                                  (T)(1.0 / ((double)c->Ny * c->Nx)), (T)(1.0 / (double)c->Ny), e, gA.as<cx<T>>(), gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl,
                                  rk.last != 0, slices);
             if (mrg && !rk.last) {
-              c->gen_x_adj_next(gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, df, Yacc.as<cx<T>>(), rk, t3, gA.as<cx<T>>(), gGx.as<cx<T>>(), slices);
+              c->gen_x_adj_next(r, gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, df, Yacc.as<cx<T>>(), rk, t3, gA.as<cx<T>>(), gGx.as<cx<T>>(), slices);
               continue;
             }
-            if (c->gen_x_adj_update(gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, df, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices)) continue;
-            c->gen_x(gW2.as<cx<T>>(), gFxy.as<cx<T>>(), false, nullptr, 2 * slices, true, false);
-            CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_adj_rk<T>), fgrid(slices), 0, c->stream, gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * pl, c->lx_r.template as<T>(),
-                        c->ly.template as<T>(), c->Nx, df, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, pl, wsl0());
+            if (c->gen_x_adj_update(r, gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, df, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices)) continue;
+            c->gen_x(r, gW2.as<cx<T>>(), gFxy.as<cx<T>>(), false, nullptr, 2 * slices, true, false);
+            CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_adj_rk<T>), fgrid(slices, r), 0, r.st, gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * pl, c->lx_r.template as<T>(),
+                        c->ly.template as<T>(), c->Nx, df, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, pl, (int)r.sl0);
             continue;
           }
-          c->F_to_map(gYs.as<cx<T>>(), gLdf.as<T>(), slices);                 // L(df)
-          if (sep) gen_grad_sep(gA.as<cx<T>>(), slices); else gen_grad(gms.as<T>(), slices);   // grad f -> gmxy
+          c->gen_irfft2(r, gYs.as<cx<T>>(), gLdf.as<T>(), slices);           // L(df)
+          if (sep) gen_grad_sep(r, gA.as<cx<T>>(), slices); else gen_grad(r, gms.as<T>(), slices);   // grad f -> gmxy
           if (sep && !rk.last && gen_pro()) {
             // the stage's pointwise work rides in the fetches of the two y transforms that consume it: f part + products -> rfft_y(f_{s+1});
             // (p_x L(df), p_y L(df)) -> the pair r2c of the delta-f velocity
@@ -1262,15 +1260,15 @@ struct Flow {
             e.ph = ph(rk.t); e.rk = rk; e.gx = gmxy.as<T>(); e.gy = gmxy.as<T>() + slices * np; e.Ldf = gLdf.as<T>(); e.y0 = f; e.acc = acc.as<T>();
             e.w1p = w1p; e.w2p = w1p + (size_t)slices * np; e.npix = np; e.P = P;
             e.mode = 2;
-            c->gen_y_r2c(gms.as<T>(), gA.as<cx<T>>(), slices, nullptr, nullptr, &e);
+            c->gen_y_r2c(r, gms.as<T>(), gA.as<cx<T>>(), slices, nullptr, nullptr, &e);
             e.mode = 3;
-            gen_adj_update(nullptr, df, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices, &e);
+            gen_adj_update(r, nullptr, df, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices, &e);
             continue;
           }
-          CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_delta<T>), pgrid(np, slices), 0, c->stream, gLdf.as<T>(), gmxy.as<T>(), gmxy.as<T>() + slices * np, ph(rk.t),
-                      gWxy.as<T>(), gWxy.as<T>() + slices * np, w1p, w1p + (size_t)slices * np, f, acc.as<T>(), gms.as<T>(), rk, np, P, wsl0());
-          if (sep && !rk.last) c->gen_y_r2c(gms.as<T>(), gA.as<cx<T>>(), slices);
-          gen_adj_update(gWxy.as<T>(), df, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices);
+          CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_delta<T>), pgrid(np, slices, r), 0, r.st, gLdf.as<T>(), gmxy.as<T>(), gmxy.as<T>() + slices * np, ph(rk.t),
+                      gWxy.as<T>(), gWxy.as<T>() + slices * np, w1p, w1p + (size_t)slices * np, f, acc.as<T>(), gms.as<T>(), rk, np, P, (int)r.sl0);
+          if (sep && !rk.last) c->gen_y_r2c(r, gms.as<T>(), gA.as<cx<T>>(), slices);
+          gen_adj_update(r, gWxy.as<T>(), df, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices);
         }
       }
     join(K);
