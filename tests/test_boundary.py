@@ -121,3 +121,54 @@ def test_plan_length_list_of_the_gpu_tests_is_the_header_s():
         for pr in (2, 3, 5):
             while k % pr == 0: k //= pr
         assert k == 1 and n % 4 == 0, n
+
+
+def test_transform_branch_list_of_the_gpu_tests_covers_the_header_s():
+    """tests/test_gpu_sizes.py::SIZES visits every chirp-z convolution length of CMBL_GEN_LIST (csrc/engine.hpp) and every launch branch of
+    the run-time mixed-radix kernel: each length's branch is recomputed here with the rules of Ctx::build_axis / Ctx::gen_dft (engine.hpp,
+    engine_gen.hpp), so a length or a branch added to the header without its GPU test fails here"""
+    import ast
+    import math
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    eng = open(os.path.join(root, "cmblensing.jl_amd", "csrc", "engine.hpp")).read()
+    m = re.search(r"#define CMBL_GEN_LIST\(X\)(.*)", eng)
+    gen_list = {int(v) for v in re.findall(r"X\((\d+)\)", m.group(1))}
+    assert gen_list and max(gen_list) == 13                              # sides up to 4096: L = 8192
+    # the plan rule of build_axis: radices 13, 11, 7, 5, 3 (as often as they divide), then 4s, then one 2
+    assert "for (int p : {13, 11, 7, 5, 3})" in eng and "ax.lgL = std::max(3, ilog2(2 * N - 1))" in eng
+    gen = open(os.path.join(root, "cmblensing.jl_amd", "csrc", "engine_gen.hpp")).read()
+    assert "const bool tw_lds = lds_of(a.S, true) <= 158 * 1024;" in gen     # the LDS twiddle bound used below
+    tree = ast.parse(open(os.path.join(root, "tests", "test_gpu_sizes.py")).read())
+    sizes = next(ast.literal_eval(n.value) for n in tree.body if isinstance(n, ast.Assign) and getattr(n.targets[0], "id", "") == "SIZES")
+
+    def radices(n):
+        f = []
+        for p in (13, 11, 7, 5, 3, 4, 2):
+            while n % p == 0:
+                f.append(p)
+                n //= p
+        return f if n == 1 else None
+
+    lgl = lambda n: max(3, math.ceil(math.log2(2 * n - 1)))
+    visited, classes = set(), set()
+    for n, forced in sizes:
+        assert 2 <= n <= 4096, n
+        plan = radices(n)
+        if forced or plan is None:
+            visited.add(lgl(n))
+            classes.add("chirp-z forced" if forced else "chirp-z")
+            continue
+        big = max(plan) > 5
+        classes.add("mixed-radix big" if big else "mixed-radix")
+        if 48 * n > 158 * 1024:                                          # double precision, one sequence per workgroup: table in global memory
+            classes.add("global twiddles, big" if big else "global twiddles")
+        if len(plan) >= 4 and len(set(plan)) == 1:
+            classes.add(f"many stages of radix {plan[0]}")
+        if n < 32:
+            classes.add("smallest")
+    assert gen_list <= visited, f"CMBL_GEN_LIST lengths without a GPU test: LGL {sorted(gen_list - visited)}"
+    want = {"chirp-z", "chirp-z forced", "mixed-radix", "mixed-radix big", "global twiddles", "global twiddles, big", "smallest"} | \
+           {f"many stages of radix {r}" for r in (3, 5, 7)}
+    assert want <= classes, sorted(want - classes)
+    assert {lgl(n) for n, f in sizes if f} >= {3, 4, 5}                  # reachable only when forced
+    assert any(f and n == 4096 for n, f in sizes)                        # L = 8192 = 2N exactly

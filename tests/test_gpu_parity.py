@@ -87,9 +87,15 @@ def test_geometry_and_basis_transforms(prec, Ny, Nx):
 
 @pytest.mark.parametrize("prec", ["f32", "f64"])
 def test_reductions_and_diag_ops(prec):
+    reductions_and_diag_ops(prec, 128, 64)
+
+
+def reductions_and_diag_ops(prec, Ny, Nx):
+    """dot / norm / logdet, the diagonal operators in each basis and the TE block operator, axpby, tr and logdet of a diagonal: against
+    the oracle and dense NumPy transforms.  The Fourier-space reductions weight each ky column with lam (1 for ky = 0 and, at even Ny only,
+    the Nyquist column; 2 elsewhere): at odd Ny Parseval and the dense sums fail if the last column were weighted as a Nyquist column."""
     C = _pkg()
     tT, nT = DT[prec]
-    Ny, Nx = 128, 64
     p = C.ProjLambert(Ny, Nx, 2.0, tT)
     op = O.Proj(Ny, Nx, 2.0, np.float64)
     rng = np.random.default_rng(1)
@@ -121,6 +127,55 @@ def test_reductions_and_diag_ops(prec):
     want = H(O.to_harm(op, a.astype(float)))
     got = p.diag_apply(te, p.tensor(a), C.HARMONIC, C.MAP, C.HARMONIC)
     close("got.cpu().numpy()", got.cpu().numpy(), want, (5e-6 if prec == "f32" else 1e-12))
+    # (the checks below use names of their own: the table keys above count occurrences of "got.cpu().numpy()")
+    dtol = 5e-6 if prec == "f32" else 1e-12
+    to_basis = {C.MAP: lambda q: O.irfft2(q, Ny), C.FOURIER: lambda q: q, C.HARMONIC: lambda q: O.qu_to_harm(op, q)}   # from QU Fourier
+    to_qu = {C.MAP: O.rfft2, C.FOURIER: lambda q: q, C.HARMONIC: lambda h: O.harm_to_qu(op, h)}
+    # basis change bi -> bo the direct way (at even Ny the rotation is not orthogonal on the Nyquist column, src/proj_lambert.jl:69-71)
+    conv = lambda x, bi, bo: x if bi == bo else to_basis[bo](to_qu[bi](x))
+    for P, B in [(1, 2), (2, 1), (3, 2)]:
+        a = rng.standard_normal((B, P, Nx, Ny)).astype(nT)
+        al = O.rfft2(a.astype(float))
+        # norm = sqrt(dot) per batch slot, in the map and a Fourier basis
+        np.testing.assert_allclose(p.norm(p.tensor(a), C.MAP), np.sqrt(O.dot_map(a.astype(float), a.astype(float))), rtol=1e-6 if prec == "f32" else 1e-12)
+        np.testing.assert_allclose(p.norm(p.tensor(al), C.FOURIER), np.sqrt(O.dot_fourier(op, al, al)), rtol=1e-5 if prec == "f32" else 1e-12)
+        hb = O.qu_to_harm(op, al)
+        np.testing.assert_allclose(p.dot(p.tensor(hb), p.tensor(hb), C.HARMONIC), O.dot_fourier(op, hb, hb), rtol=1e-5 if prec == "f32" else 1e-12)
+        # DiagOp * and \ with the diagonal in FOURIER (QU) and in HARMONIC (EB), every input / output basis
+        d = (rng.random((P, Nx, Ny // 2 + 1)) + 0.5).astype(nT)
+        d[..., 1, 0] = 0                                                                  # nan2zero of the \ kind
+        for bd in (C.FOURIER, C.HARMONIC):
+            for kind, op_ in ((1, O.diag_mul), (3, O.diag_div)):                     # CMBL_DIAG_MUL, CMBL_DIAG_DIV_NAN2ZERO
+                for bi, bo in ((C.MAP, C.MAP), (C.FOURIER, C.HARMONIC), (C.HARMONIC, C.FOURIER), (C.MAP, C.HARMONIC), (C.FOURIER, C.MAP)):
+                    src = p.tensor(a if bi == C.MAP else to_basis[bi](al))
+                    want = conv(op_(d.astype(float), conv(src.cpu().numpy().astype(float if bi == C.MAP else complex), bi, bd)), bd, bo)
+                    got = p.diag_apply(d, src, bd, bi, bo, kind=kind)
+                    close(("diag_apply", bd, kind, bi, bo, P), got.cpu().numpy(), want, dtol)
+        with pytest.raises(C.CmblError) as e:                                              # a MAP diagonal is not an operator of the API
+            p.diag_apply(d, p.tensor(a), C.MAP, C.MAP)
+        assert e.value.code == 1                                                           # CMBL_ERR_ARG
+        # axpby with per-batch coefficients, with and without y, in each basis
+        x2 = rng.standard_normal((B, P, Nx, Ny)).astype(nT)
+        xl2 = O.rfft2(x2.astype(float))
+        ca, cb = rng.standard_normal(B), rng.standard_normal(B)
+        bc = lambda c: c[:, None, None, None]
+        for basis, u, v in ((C.MAP, a, x2), (C.FOURIER, al, xl2), (C.HARMONIC, O.qu_to_harm(op, al), O.qu_to_harm(op, xl2))):
+            ut, vt = p.tensor(u), p.tensor(v)
+            u64, v64 = ut.cpu().numpy().astype(np.complex128 if basis != C.MAP else np.float64), vt.cpu().numpy().astype(np.complex128 if basis != C.MAP else np.float64)
+            close(("axpby", basis, P), p.axpby(ca, ut, cb, vt, basis).cpu().numpy(), bc(ca) * u64 + bc(cb) * v64, 1.5e-6 if prec == "f32" else 1e-12)
+            close(("ax", basis, P), p.axpby(ca, ut, basis=basis).cpu().numpy(), bc(ca) * u64, 1.5e-6 if prec == "f32" else 1e-12)
+        # tr / logdet of Diagonal(field): a map, and a Fourier half plane against the dense 2-D transform (np.fft.fft2) of its real map --
+        # the lam weights must make the half-plane sums the full-plane sums
+        dm = (np.abs(a) + 0.5).astype(nT)
+        np.testing.assert_allclose(p.tr_diag(p.tensor(dm), C.MAP), dm.astype(float).sum(axis=(1, 2, 3)), rtol=1e-6 if prec == "f32" else 1e-12)
+        np.testing.assert_allclose(p.logdet_diag(p.tensor(dm), C.MAP), np.log(dm.astype(float)).sum(axis=(1, 2, 3)), rtol=1e-6 if prec == "f32" else 1e-12)
+        dl = p.tensor(al)
+        dense = np.fft.fft2(O.irfft2(dl.cpu().numpy().astype(np.complex128), Ny), axes=(-2, -1))   # the full plane of the (rounded) half plane
+        scale = np.abs(dense).sum(axis=(1, 2, 3))
+        rt = 1e-6 if prec == "f32" else 1e-12
+        np.testing.assert_array_less(np.abs(p.tr_diag(dl, C.FOURIER) - dense.real.sum(axis=(1, 2, 3))), rt * scale)   # (a sum that cancels)
+        logs = np.log(np.abs(dense))
+        np.testing.assert_array_less(np.abs(p.logdet_diag(dl, C.FOURIER) - logs.sum(axis=(1, 2, 3))), rt * np.abs(logs).sum(axis=(1, 2, 3)))
 
 
 @pytest.mark.parametrize("prec", ["f32", "f64"])
