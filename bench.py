@@ -5,15 +5,20 @@ One "step" = one evaluation of ∇_(f°,ϕ°) logpdf(Mixed(ds)) (the reference's
 test/runbenchmarks.jl:120): precompute(ϕ) + 1 inverse flow + 1 forward flow + 2 δ-flows +
 the Fourier-diagonal / mask / reduction work, LenseFlow n = 7 RK4 steps, fp32, inputs resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--nside 1024] [--pol P] [--nbatch B] [--config {2,3,5}] [--no-cpu-baseline]
-                    [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--nside 1024] [--pol P] [--nbatch B] [--config {2,3,5}] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-roofline] [--no-extras]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-`--config C` runs BASELINE.json's configuration C (2: 512² QU fp32; 3: 1024² T+QU fp32; 5: 2048² QU fp64 n=10) with the same step and
-adds that configuration's own operations (L*f, L'g, Wiener CG / one MAP_joint step / quadratic_estimate) under `extras`.
+A plain run does only what the headline needs: set-up, clock ramp, W warm-up steps, K timed steps, `--dump-outputs`, one JSON line.
+`--full` adds everything else the line can carry, after the timed region: `roofline` (a per-launch re-run of the step), `extras`
+(other configurations and sizes, the reference-exact arithmetic), `cpu_baseline` and `parity_at_config` (the NumPy oracle);
+`--no-cpu-baseline` / `--no-roofline` / `--no-extras` drop single legs of a `--full` run.
+
+`--config C` runs BASELINE.json's configuration C (2: 512² QU fp32; 3: 1024² T+QU fp32; 5: 2048² QU fp64 n=10) with the same step;
+with `--full` it adds that configuration's own operations (L*f, L'g, Wiener CG / one MAP_joint step / quadratic_estimate) under `extras`.
 `--only cg` (profiling aid, not a headline): the step is ONE Wiener-filter CG iteration (src/numerical_algorithms.jl:73-134).
 
-roofline: every fraction in the line is a bandwidth.
+roofline (`--full`): every fraction in the line is a bandwidth.
   * `frac` / `achieved`: the COMPULSORY bytes of the dominant kernel's launch -- every array the launch must read or write once,
     derived per kernel in `compulsory_bytes()` below and in DESIGN.md §5 -- divided by the launch's mean duration (the kernel's own
     start/stop timestamps, recorded by the library with hipExtLaunchKernel events on the stream it launches on) and by 8 TB/s.
@@ -408,7 +413,8 @@ def clock_ramp(step, sync, block=5, tol=0.01, max_blocks=60):
     return n, cur * 1e3
 
 
-def main():
+def parse_args(argv=None):
+    """the command line, with the legs a run skips already resolved into the --no-* switches"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -420,9 +426,12 @@ def main():
     ap.add_argument("--nbatch", type=int, default=1, help="chains per GPU (batch dim 4)")
     ap.add_argument("--config", type=int, default=0, choices=[0, 2, 3, 5], help="BASELINE.json configuration (0 = the headline workload)")
     ap.add_argument("--only", default="", choices=["", "cg"], help="profiling aid: the step is one Wiener-CG iteration instead of ∇lnP")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the roofline, extras, reference-exact arithmetic and CPU baseline (with its "
+                         "parity check); a plain run prints the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and its parity check")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline leg (and the extras of the headline workload)")
+    ap.add_argument("--no-extras", action="store_true", help="--full without extras")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (default); gloo lets the N>1 logic be exercised on a box with fewer GPUs than ranks")
     ap.add_argument("--no-ramp", action="store_true", help="skip the untimed clock-ramp spin before the warm-up steps")
@@ -433,18 +442,26 @@ def main():
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most "
                          "64 MB in all: a fixed, seeded sample of larger outputs); rank 0 writes")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.dry_run_ranks and args.dump_outputs:
         ap.error("--dump-outputs needs the real step (not --dry-run-ranks)")
     dry = args.dry_run_ranks > 0
+    if not args.full:
+        args.no_roofline = args.no_extras = args.no_cpu_baseline = True
     if dry:
         args.gpus, args.dist_backend = args.dry_run_ranks, "gloo"
         args.no_roofline = args.no_extras = args.no_cpu_baseline = args.no_ramp = True
     if args.config:
         for k, v in CONFIGS[args.config].items():
             setattr(args, k, v)
+    return args
+
+
+def main():
+    args = parse_args()
+    dry = args.dry_run_ranks > 0
     cmd = self_launch_command(args, sys.argv[1:], os.environ)
     if cmd is not None:
         # plain `python bench.py --gpus N`: this process becomes the launcher of N ranks (one per GPU), like the reference's own

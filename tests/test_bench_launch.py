@@ -121,3 +121,15 @@ def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
 def test_steps_must_be_positive():
     r = subprocess.run([sys.executable, "bench.py", "--steps", "0"], cwd=ROOT, capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "--steps must be at least 1" in r.stderr, r.stderr[-2000:]
+
+
+def test_plain_run_measures_the_headline_alone():
+    """a plain run skips every leg after the timed region; --full runs them all unless a --no-* switch drops one"""
+    legs = lambda a: (a.no_roofline, a.no_extras, a.no_cpu_baseline)
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert legs(plain) == (True, True, True) and not plain.full and not plain.no_ramp
+    assert (plain.steps, plain.warmup, plain.nside, plain.pol, plain.dtype, plain.nrk, plain.nbatch) == (20, 5, 1024, "P", "f32", 7, 1)
+    assert legs(bench.parse_args(["--config", "5"])) == (True, True, True)
+    assert legs(bench.parse_args(["--full"])) == (False, False, False)
+    assert legs(bench.parse_args(["--full", "--no-cpu-baseline"])) == (False, False, True)
+    assert legs(bench.parse_args(["--full", "--dry-run-ranks", "2"])) == (True, True, True)

@@ -22,8 +22,8 @@ bash tools/run_traffic.sh $tag cg_1024IQU_f32 --only cg --steps 19 --nside 1024 
 # make the fresh traffic files visible to bench.py on this box
 for f in $out/traffic_*.json; do cp $f profiles/${tag}_$(basename $f); done
 cp $out/counter_calibration.json profiles/${tag}_counter_calibration.json 2>/dev/null
-B="python bench.py --no-cpu-baseline"
-python bench.py > $out/bench_line.json 2> $out/bench.err
+B="python bench.py --full --no-cpu-baseline"
+python bench.py --full > $out/bench_line.json 2> $out/bench.err
 # kernel statistics of the headline workload over 50 warm steps, one launch over all pol slices: the per-kernel means bench.py's roofline
 # leg measures with the kernels' own timestamps (kernel_stats_1024QU_f32.csv, from the 8-step counter run, includes the cold first steps)
 CMBL_SLICE_STREAMS=1 rocprofv3 --kernel-trace --stats -f csv -d $out/trace_bench -o b -- python bench.py --steps 50 --warmup 5 --no-ramp --no-cpu-baseline --no-roofline --no-extras > $out/trace_bench.log 2>&1

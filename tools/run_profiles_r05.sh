@@ -12,9 +12,9 @@ for f in $out/traffic_*.json; do cp $f profiles/${tag}_$(basename $f); done
 CMBL_SLICE_STREAMS=1 timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $out/trace_bench -o b -- python bench.py --steps 50 --warmup 5 --no-ramp --no-cpu-baseline --no-roofline --no-extras > $out/trace_bench.log 2>&1
 s=$(find $out/trace_bench -name '*kernel_stats.csv' | head -1); [ -n "$s" ] && cp $s $out/kernel_stats_1024QU_f32_50steps.csv && cp $s profiles/${tag}_kernel_stats_1024QU_f32_50steps.csv
 rm -rf $out/trace_bench
-timeout 900 python bench.py > $out/bench_line.json 2> $out/bench.err
-timeout 900 python bench.py --steps 20 --warmup 5 > $out/bench_line_k20.json 2>> $out/bench.err
-B="python bench.py --no-cpu-baseline"
+timeout 900 python bench.py --full > $out/bench_line.json 2> $out/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $out/bench_line_k20.json 2>> $out/bench.err
+B="python bench.py --full --no-cpu-baseline"
 for c in 2 3 5; do timeout 900 $B --config $c --steps 50 > $out/bench_config$c.json 2>> $out/bench.err; done
 timeout 600 $B --nbatch 8 --steps 30 > $out/bench_nbatch8.json 2>> $out/bench.err
 timeout 600 python tools/gpu_configs.py > $out/configs_table.txt 2>&1

@@ -12,9 +12,9 @@ s=$(find $out/trace_bench -name '*kernel_stats.csv' | head -1); [ -n "$s" ] && c
 rm -rf $out/trace_bench
 timeout 600 bash tools/run_traffic.sh $tag 1024QU_f32 --nside 1024 --pol P --dtype f32 --nrk 7
 # bench lines: the default (as the driver runs it: K = 20, and K = 200), the other BASELINE configurations WITH their extras, 8 chains per GPU
-timeout 900 python bench.py > $out/bench_line.json 2> $out/bench.err
-timeout 900 python bench.py --steps 20 --warmup 5 > $out/bench_line_k20.json 2>> $out/bench.err
-B="python bench.py --no-cpu-baseline"
+timeout 900 python bench.py --full > $out/bench_line.json 2> $out/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $out/bench_line_k20.json 2>> $out/bench.err
+B="python bench.py --full --no-cpu-baseline"
 for c in 2 3 5; do timeout 900 $B --config $c --steps 50 > $out/bench_config$c.json 2>> $out/bench.err; done
 timeout 600 $B --nbatch 8 --steps 30 > $out/bench_nbatch8.json 2>> $out/bench.err
 timeout 600 python tools/gpu_configs.py > $out/configs_table.txt 2>&1
