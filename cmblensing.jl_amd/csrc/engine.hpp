@@ -104,7 +104,6 @@ struct CtxBase {
     // fewer workgroups than `fill_target` (0: the rule in Ctx::tileY), shorter row groups while it has fewer than `row_fill_target`
     // (0: half the number of CUs -- 130 -> 258 row workgroups at 512^2 QU measured slower, 34 -> 130 at 128^2 17 % faster)
     int col_prefetch = env_int("CMBL_COL_PREFETCH", -1);                  // touch prefetch of multi-round column launches: -1 = Ctx::col_prefetch's rule, 0 = off, > 0 = that distance (blocks)
-    int col_pipeline = env_int("CMBL_COL_PIPELINE", 1);                   // only in -DCMBL_EXPERIMENT_COL_PIPELINE builds: two tiles per column workgroup
     int occupancy_tiles = env_int("CMBL_OCCUPANCY_TILES", 3);             // bit 0: narrower column tiles, bit 1: shorter row groups
     int fill_target = env_int("CMBL_FILL_TARGET", 0);
     int row_fill_target = env_int("CMBL_ROW_FILL_TARGET", 0);
@@ -127,7 +126,6 @@ struct CtxBase {
     if (k == "gen_yy") return &opts.gen_yy;
     if (k == "gen_slice_streams") return &opts.gen_slice_streams;
     if (k == "gen_streams_min_pix") return &opts.gen_streams_min_pix;
-    if (k == "col_pipeline") return &opts.col_pipeline;
     if (k == "col_prefetch") return &opts.col_prefetch;
     if (k == "occupancy_tiles") return &opts.occupancy_tiles;
     if (k == "fill_target") return &opts.fill_target;
@@ -545,17 +543,10 @@ struct Ctx : CtxBase {
 #undef CMBL_X
       };
       for (const auto& e : list)
-        if (e[0] == lgM && e[2] == (opts.col_pipeline >= 2 ? 256 : 512) && (((long)e[1] * e[2]) >> lgM) == 2 && ldsY(2, true) <= 160 * 1024) return TileY{2, e[2], e[1]};   // (col_pipeline = 2, experiment builds: the 256-thread tile, whose 512 registers per thread hold a prefetched head tile)
+        if (e[0] == lgM && e[2] == 512 && (((long)e[1] * e[2]) >> lgM) == 2 && ldsY(2, true) <= 160 * 1024) return TileY{2, e[2], e[1]};
       return t;
     }
     return tileY(slices, true);
-  }
-  // tiles per workgroup of the experimental software-pipelined column kernel (-DCMBL_EXPERIMENT_COL_PIPELINE; col_pipelined shapes)
-  int col_tpw(int tiles, long slices) const {
-    if (opts.col_pipeline <= 0) return 1;
-    int tpw = 2;
-    while (tpw > 1 && (tiles % (8 * tpw) != 0 || (long)(tiles / tpw) * slices < num_cus)) tpw >>= 1;
-    return tpw;
   }
   // Touch-prefetch distance of a column launch (kernels_flow.hpp TouchTiles): three quarters of the workgroups of this launch that are resident at
   // once -- the CUs, shared by the K launch chains that run side by side -- as a multiple of 8 (XCDs): measured best at 80-96 for two chains and
@@ -1454,17 +1445,6 @@ struct Flow {
           d.pf = c->col_prefetch(c->Nx / tile.C, gs, K);
           c->dispatch_col(tile, [&](auto lgm, auto r, auto nt) {
             constexpr int LGM = decltype(lgm)::value, R = decltype(r)::value, NT = decltype(nt)::value;
-            // one-workgroup-per-CU shapes (2048 rows in double precision) walk several tiles per workgroup with the next tile's loads
-            // under the current tile's last phase (delta_y_body_pipelined)
-#ifdef CMBL_EXPERIMENT_COL_PIPELINE      // measured and rejected (profiles/r05_ab_col_pipeline_rejected.txt); the kernel is kept for the record
-            if constexpr (col_pipelined<T>(LGM)) {
-              const int tiles = c->Nx / tile.C, tpw = c->col_tpw(tiles, gs);
-              if (tpw == 2) {
-                CMBL_LAUNCH_NT(c, K_DELTA_Y, NT, (k_delta_cols_pl<T, R, NT, LGM, 2>), dim3(tiles / tpw, (unsigned)gs), c->ldsY(tile.C), st, d);
-                return;
-              }
-            }
-#endif
             CMBL_LAUNCH_NT(c, K_DELTA_Y, NT, (k_delta_cols<T, R, NT, LGM>), dim3(c->Nx / tile.C, (unsigned)gs), c->ldsY(tile.C), st, d);
           });
           // delta-f row pass (RK update of df + next H) + d/dx of the next stage's f (a_nxt holds A_{s+1} after this column launch)

@@ -6,7 +6,7 @@
 // so a forward/pointwise/inverse chain never needs a reordering pass: frequency k lives at slot brev(k).
 // Up to four radix-2 levels are fused per LDS round trip: a thread pulls 2^LG elements into registers, runs LG levels of
 // the in-place network on them (radix-16 for LG=4) and writes them back, so a 1024-point transform is 3 round trips / 3
-// barriers.  Element i of a sequence lives at LDS index pad(i) = i + (i >> CMBL_PAD_SHIFT): the padding spreads the
+// barriers.  Element i of a sequence lives at LDS index pad(i) = i + (i >> 4): the padding spreads the
 // power-of-two strides of bit-reversed and butterfly accesses over the 64 banks.  All sizes are template parameters, so
 // every LDS address inside a stage is `pad(base) + immediate` and every twiddle index is a constant shift.
 //
@@ -23,21 +23,14 @@
 #include "common.hpp"
 #include "fft_core.hpp"
 
-#ifndef CMBL_STAGE_SYNC
-#define CMBL_STAGE_SYNC() __syncthreads()
-#endif
-
 namespace cmbl {
 
-// One spare slot per 2^CMBL_PAD_SHIFT.  A third of the LDS cycles of the fused kernels are bank conflicts (SQ_LDS_BANK_CONFLICT /
+// One spare slot per 16.  A third of the LDS cycles of the fused kernels are bank conflicts (SQ_LDS_BANK_CONFLICT /
 // SQ_LDS_IDX_ACTIVE = 0.32, all on the ds_read_b64 side: 32-lane groups on 64 banks; the writes stay inside their transfer time).
 // A spare slot per 8 removes the read conflicts of the two lower stages of a wave-private 512-point transform (bank model of the
 // stage accesses: 96 -> 64 LDS cycles per transform, 48 ideal) -- and changes no kernel time on the GPU (A/B at 1024^2), so the
 // smaller footprint stays: the conflict cycles hide behind the waits of the dependent chain.
-#ifndef CMBL_PAD_SHIFT
-#define CMBL_PAD_SHIFT 4
-#endif
-__device__ __host__ __forceinline__ constexpr int pad(int i) { return i + (i >> CMBL_PAD_SHIFT); }
+__device__ __host__ __forceinline__ constexpr int pad(int i) { return i + (i >> 4); }
 // leading dimension (in complex slots) of a tile row holding n elements (+1 spare slot for the packed-real Nyquist term)
 __device__ __host__ __forceinline__ constexpr int tile_ld(int n) { return pad(n) + 1; }
 template <int LG> __device__ __forceinline__ int brevc(int i) { return LG == 0 ? 0 : (int)(__brev((unsigned)i) >> (32 - (LG == 0 ? 1 : LG))); }
@@ -62,7 +55,7 @@ template <int NT> struct WorkCoop {
   template <int LGNB, typename F> __device__ __forceinline__ void each(F&& f) const {
     for (int q = threadIdx.x; q < (S << LGNB); q += NT) f(q >> LGNB, q & ((1 << LGNB) - 1));
   }
-  __device__ __forceinline__ void sync() const { CMBL_STAGE_SYNC(); }
+  __device__ __forceinline__ void sync() const { __syncthreads(); }
 };
 // WorkRows: RT consecutive threads own row `threadIdx.x / RT` of each of NA arrays (sequence a*RPW + row); rows >= nr are absent.
 // The row kernels run the TOP radix-2 level of a row transform while loading / storing (kernels_fft.hpp), so the stages here act on
@@ -74,7 +67,7 @@ template <int NT> struct WorkCoop {
 // quarter is -i times the first (stage_twiddles)
 template <int RT, int RPW, bool TWQ = false> struct WorkRows {
   int NA, nr;
-  int tid = (int)threadIdx.x;             // (a member so that a kernel that walks several tiles can pass an opaque copy per tile: kernels_flow.hpp delta_y_body_pipelined)
+  int tid = (int)threadIdx.x;
   static constexpr bool twq = TWQ;
   static constexpr bool wave_private = RT <= 128;
   template <int LGNB, typename F> __device__ __forceinline__ void each(F&& f) const {
@@ -128,12 +121,10 @@ template <int RT, int RPW, bool TWQ = false> struct WorkSeqs {
   __device__ __forceinline__ void sync() const { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 };
 
-// External twiddles of a stage, W^(j k) for k = 1..r-1.  CMBL_TW_REC = 1 (single precision only): ONE table read, W^j, and the powers by
-// multiplication (depth-3 product tree) instead of r-1 table reads -- the transforms are bound by LDS throughput at the CU and the
-// twiddle reads are a quarter of a radix-8 stage's LDS traffic; the products cost 2 packed instructions each on a VALU that has room.
-#ifndef CMBL_TW_REC
-#define CMBL_TW_REC 2
-#endif
+// External twiddles of a stage, W^(j k) for k = 1..r-1: ONE table read, W^j, and the powers by multiplication (depth-3 product tree)
+// instead of r-1 table reads -- the transforms are bound by LDS throughput at the CU and the twiddle reads are a quarter of a radix-8
+// stage's LDS traffic; the products cost 2 packed instructions each on a VALU that has room.  The row kernels rely on it: their LDS
+// table holds only the first half (or quarter) of the circle, all that index j * 2^sh ever reaches.
 // table entry i < 2^(QLG+1) of a table that keeps the first 2^QLG entries (a quarter of the circle): W^(i + N/4) = -i W^i.  QLG = 0: plain read
 template <typename T, int QLG> __device__ __forceinline__ typename vreg<T>::type tw_read(const cx<T>* __restrict__ tw, int i) {
   if constexpr (QLG == 0) return vload(tw + i);
@@ -144,19 +135,9 @@ template <typename T, int QLG> __device__ __forceinline__ typename vreg<T>::type
 }
 template <typename T, int r, int QLG = 0, typename V>
 __device__ __forceinline__ void stage_twiddles(const cx<T>* __restrict__ tw, int j, int sh, V (&w)[r]) {
-  if constexpr (QLG != 0) {
-    static_assert(CMBL_TW_REC == 2, "quarter-circle tables need the one-read stage twiddles");
-    w[1] = tw_read<T, QLG>(tw, j << sh);
+  w[1] = tw_read<T, QLG>(tw, j << sh);
 #pragma unroll
-    for (int k = 2; k < r; ++k) w[k] = vmul(w[k >> 1], w[k - (k >> 1)]);
-  } else if constexpr ((CMBL_TW_REC == 2 || (CMBL_TW_REC == 1 && sizeof(T) == 4)) && r >= 4) {
-    w[1] = vload(tw + (j << sh));
-#pragma unroll
-    for (int k = 2; k < r; ++k) w[k] = vmul(w[k >> 1], w[k - (k >> 1)]);
-  } else {
-#pragma unroll
-    for (int k = 1; k < r; ++k) w[k] = vload(tw + ((j * k) << sh));
-  }
+  for (int k = 2; k < r; ++k) w[k] = vmul(w[k >> 1], w[k - (k >> 1)]);
 }
 
 // One fused DIF stage = LG radix-2 levels with spans h = 2^LGH (top) ... hmin = 2^(LGH-LG+1), evaluated as ONE r-point DFT per

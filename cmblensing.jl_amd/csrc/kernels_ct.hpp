@@ -51,12 +51,9 @@ template <typename T> constexpr int ct_Smax(int N) { return ct_lds<T>(N) <= 160 
 template <typename T> constexpr bool ct_rowfuse_ok(int N) { return !(sizeof(T) == 8 && N > 1920); }
 // columns per workgroup of the delta-stage kernel (two LDS rows per column): the usual count, or half of it where that does not fit (Ny > ~1150;
 // the transposed side then moves 32-byte pieces)
-#ifndef CMBL_CT_S2_HALF
-#define CMBL_CT_S2_HALF 0      // 1: always half (A/B: shorter transform phases, 32-byte pieces on the transposed side)
-#endif
 // (a quarter from 2304 points on: 2 columns in single, 1 in double precision)
 template <typename T> constexpr int ct_S2(int N) {
-  return (!CMBL_CT_S2_HALF && ct_lds<T>(N, 2) <= 160 * 1024) ? ct_S<T>() : ct_lds<T>(N, 2, ct_S<T>() / 2) <= 160 * 1024 ? ct_S<T>() / 2 : ct_S<T>() / 4;
+  return ct_lds<T>(N, 2) <= 160 * 1024 ? ct_S<T>() : ct_lds<T>(N, 2, ct_S<T>() / 2) <= 160 * 1024 ? ct_S<T>() / 2 : ct_S<T>() / 4;
 }
 
 // fetch variants
@@ -241,16 +238,14 @@ __device__ __forceinline__ cx<T> ct_value(const CtRegs<T, CH>& g, int i, const G
   return a.inverse ? conj(v) : v;
 }
 
-// elements a thread requests before it consumes the first: as many as fit a budget of operand registers (in units of T)
-#ifndef CMBL_CT_FETCH_WORDS
-#define CMBL_CT_FETCH_WORDS 64
-#endif
+// elements a thread requests before it consumes the first: as many as fit a budget of 64 operand registers (in units of T; 48 and 96
+// measured within 0.5 % on the tiled kernels, profiles/r06_ab_anysize_fetch_words_neutral.txt)
 constexpr int ct_words(int kind, bool flag) {
   return kind == CT_C ? 2 : kind == CT_R1 ? 1 : kind == CT_R2 ? 2 : kind == CT_H1 ? 2 + flag : kind == CT_H2 ? 4 + flag
        : (flag ? 2 : 5) + (kind == CT_P1 ? 4 : kind == CT_P2 ? 5 : 1);
 }
 constexpr int ct_chunk(int E, int kind, bool flag) {
-  int ch = CMBL_CT_FETCH_WORDS / ct_words(kind, flag);
+  int ch = 64 / ct_words(kind, flag);
   ch = ch < 2 ? 2 : ch;
   ch = ch > E ? E : ch;
   const int nch = (E + ch - 1) / ch;
@@ -332,14 +327,12 @@ __device__ __forceinline__ void ct_fetch(const GenDft<T>& a, cx<T>* __restrict__
 // gen_put (kernels_generic.hpp) with the addressing of the fetch: wave-uniform slice base in scalar registers + one 32-bit element
 // offset (the 64-bit multiplies of a general index cost the store phase 4.4k cycles per launch: 12 elements per thread)
 template <int BYTES> __device__ __forceinline__ void ct_store(void* sbase, unsigned byte_off, const void* v, bool wt) {
-#if CMBL_WT_GEN
   if (wt) {
     if constexpr (BYTES == 16) { const wt_f4 d = *reinterpret_cast<const wt_f4*>(v); asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" : : "v"(byte_off), "v"(d), "s"(sbase) : "memory"); }
     else if constexpr (BYTES == 8) { const wt_f2 d = *reinterpret_cast<const wt_f2*>(v); asm volatile("global_store_dwordx2 %0, %1, %2 sc1" : : "v"(byte_off), "v"(d), "s"(sbase) : "memory"); }
     else { const float d = *reinterpret_cast<const float*>(v); asm volatile("global_store_dword %0, %1, %2 sc1" : : "v"(byte_off), "v"(d), "s"(sbase) : "memory"); }
     return;
   }
-#endif
   char* q = reinterpret_cast<char*>(sbase) + byte_off;
   if constexpr (BYTES == 16) *reinterpret_cast<wt_f4*>(q) = *reinterpret_cast<const wt_f4*>(v);
   else if constexpr (BYTES == 8) *reinterpret_cast<wt_f2*>(q) = *reinterpret_cast<const wt_f2*>(v);
@@ -473,9 +466,6 @@ __device__ __forceinline__ void ct_flow_stage(const GenDft<T>& a, cx<T>* __restr
 #define CMBL_CT_STAMP(i) do {} while (0)
 #endif
 
-#ifndef CMBL_DY_PROBE
-#define CMBL_DY_PROBE 0      // timing-only probes of k_ct_delta_y (results wrong): 1 no transforms, 2 no product stores, 4 no operand loads, 8 no final stores
-#endif
 template <typename T> constexpr int ct_min_waves() { return sizeof(T) == 4 ? 4 : 2; }       // two workgroups per CU
 // ... of the x-pass kernels: two workgroups of S wavefronts per CU, and ONE from 1000 points on -- 16-24 elements per lane under the 128-register
 // cap spilled 80-170 registers (1000 = 8 5 5 5: 300 bytes of scratch per lane in the d/dx pass), while a launch of <= 256 row groups has one
@@ -628,7 +618,6 @@ __global__ __launch_bounds__(128 * S) void k_ct_delta_y(GenDft<T> a) {
 #pragma unroll
   for (int j = 0; j < EH; ++j) {
     const unsigned o = (unsigned)seqc * (unsigned)N + (unsigned)min(lane + 64 * (2 * j + set), N - 1);
-    if (CMBL_DY_PROBE & 4) { y0v[j] = T(o); acv[j] = T(1); px[j] = T(2); py[j] = T(3); continue; }
     y0v[j] = at32(e.y0 + mb, o); acv[j] = at32(e.acc + mb, o);
     if (pc) { px[j] = at32(e.ph.pcx + pb, o); py[j] = at32(e.ph.pcy + pb, o); }
     else {
@@ -637,7 +626,7 @@ __global__ __launch_bounds__(128 * S) void k_ct_delta_y(GenDft<T> a) {
     }
   }
   __syncthreads();
-  if (live && !(CMBL_DY_PROBE & 1)) ct_transform<T, N>(set ? r2 : r1, tw, lane);
+  if (live) ct_transform<T, N>(set ? r2 : r1, tw, lane);
   __syncthreads();
   if (live) {
 #pragma unroll
@@ -650,7 +639,7 @@ __global__ __launch_bounds__(128 * S) void k_ct_delta_y(GenDft<T> a) {
         const T k = px[j] * gx + py[j] * gy;
         T y = y0v[j], ac = e.rk.stage == 1 ? T(0) : acv[j];
         const T nxt = rk_update(e.rk, k, y, ac);
-        if (!(CMBL_DY_PROBE & 2)) { at32(e.w1p + mb, o) = l * gx; at32(e.w2p + mb, o) = l * gy; }
+        at32(e.w1p + mb, o) = l * gx; at32(e.w2p + mb, o) = l * gy;
         if (e.rk.stage == 4) at32(e.y0 + mb, o) = y; else at32(e.acc + mb, o) = ac;
         r1[pad(n)] = mk<T>(nxt, T(0));
         r2[pad(n)] = mk<T>(px[j] * l, py[j] * l);
@@ -658,12 +647,11 @@ __global__ __launch_bounds__(128 * S) void k_ct_delta_y(GenDft<T> a) {
     }
   }
   __syncthreads();
-  if (live && !(set == 0 && a.yy_last) && !(CMBL_DY_PROBE & 1)) ct_transform<T, N>(set ? r2 : r1, tw, lane);
+  if (live && !(set == 0 && a.yy_last)) ct_transform<T, N>(set ? r2 : r1, tw, lane);
   __syncthreads();
   GenDft<T> b{};                                                         // store side, [ky][x] like the inputs
   b.N = N; b.nout = a.yy_nout; b.nseq = a.nseq; b.in_real = 1; b.scale = T(1); b.scale2 = T(1);
   b.out_seq = a.in_seq; b.out_elem = a.in_elem; b.out_slice = a.in_slice; b.out_tiled = a.in_tiled; b.tile_np = a.tile_np;
-  if (CMBL_DY_PROBE & 8) return;
   if (set == 0) {
     if (!a.yy_last) { b.out = a.yy_out; ct_store_rows<T, N, S>(b, s, sl, seq0, true, wave, lane, false, tid); }
   } else {

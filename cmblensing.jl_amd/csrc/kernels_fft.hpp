@@ -10,21 +10,6 @@
 #pragma once
 #include "fft_lds.hpp"
 
-#ifndef CMBL_XLG
-#define CMBL_XLG 4      // row kernels: radix-16 stages (radix-8 = 3 measured 5 % faster for L*f alone but 3 % slower for the gradient step)
-#endif
-
-#ifndef CMBL_YLGN
-#define CMBL_YLGN 4     // column kernels, N-point (pair) transforms: cap on fused radix-2 levels per LDS round trip
-#endif
-#ifndef CMBL_YLGM
-#define CMBL_YLGM 4     // column kernels, N/2-point (packed real) transforms
-#endif
-
-#ifndef CMBL_ROW_WAVES
-#define CMBL_ROW_WAVES 1
-#endif
-
 namespace cmbl {
 
 __host__ __device__ constexpr int ilog2c(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
@@ -62,9 +47,6 @@ __device__ unsigned long long g_stamps[8192 * 16];
 #define CMBL_XWSTAMP(i) do {} while (0)
 #endif
 
-// register budget of the row kernels (waves per SIMD the compiler must leave room for; fp32 only)
-template <typename T> constexpr int row_min_waves() { return sizeof(T) == 4 ? CMBL_ROW_WAVES : 1; }
-
 // Column tiles that are neighbours in x share 64/128-byte lines of the [ky][x] arrays.  Workgroup b is observed to run
 // on XCD b % 8 (speed only, never correctness), so give every XCD a contiguous range of tiles: its private L2 then sees
 // both halves of each shared line.
@@ -78,20 +60,13 @@ __device__ __forceinline__ int xcd_tile(int b, int nb) { return (nb & 7) ? b : (
 // takes 4 adjacent ky rows gathers whole 128-byte lines (4 rows x 4 values), which is as fast as contiguous rows (2.9 us / 2.9 us).
 // The row count of a block is padded to a multiple of 4 (Ny/2+1 is odd): blocks and the gathered 4 x 4 lines then start on 128-byte
 // boundaries (unpadded, every line of a row workgroup straddled two: +35 % measured traffic in the row kernels).
-// Block width per precision (round 6): 4 columns of 8-byte elements, CMBL_MIXW64 (2) columns of 16-byte ones -- a block row is then 32 bytes in both
-// precisions, 4 padded rows x one block row = one 128-byte line, and the TWO-column tile the double-precision delta-flow kernel runs on (engine.hpp
-// tileY_delta: the four-column tile spills) is ONE contiguous block of whole lines instead of the 32-byte halves of a four-column block's 64-byte
-// rows (those half lines were fetched by both neighbours: +18 % L2 read requests at 2048^2 fp64, profiles/r05_pmc_tcc_requests.txt).
-// -DCMBL_MIXW64=4 restores the round-2..5 layout for A/B.
-#ifndef CMBL_MIXW64
-#define CMBL_MIXW64 4
-#endif
-template <int BYTES> __host__ __device__ constexpr int mixw_b() { return BYTES == 16 ? CMBL_MIXW64 : 4; }      // BYTES = sizeof(cx<T>)
-template <typename T> __host__ __device__ constexpr int mixw() { return mixw_b<(int)sizeof(cx<T>)>(); }
-template <int W> __host__ __device__ constexpr int lg_mixw() { return W == 4 ? 2 : W == 2 ? 1 : 0; }
-static_assert(CMBL_MIXW64 == 1 || CMBL_MIXW64 == 2 || CMBL_MIXW64 == 4, "block width of the double-precision mixed layout");
+// The block is 4 columns wide in both precisions: a block row is 32 bytes of single- and 64 bytes of double-precision values.  2 columns
+// for 16-byte elements (32-byte block rows in both precisions: the two-column tile of the double-precision delta-flow kernel, engine.hpp
+// tileY_delta, would then be one contiguous block of whole lines) was measured and rejected: delta_cols -5 %, but the one-row adjoint row
+// groups then gather 32-byte pieces, step +4.6 % at 2048^2 fp64 (profiles/r06_ab_mixw64_rejected.txt).
+constexpr int MIXW = 4, LG_MIXW = 2;
 __host__ __device__ constexpr int mixed_rows(int Nyh) { return (Nyh + 3) & ~3; }
-template <int W> __device__ __forceinline__ size_t mix_idx(int ky, int x, int NyhP) { return ((size_t)(x >> lg_mixw<W>()) * NyhP + ky) * W + (x & (W - 1)); }
+__device__ __forceinline__ size_t mix_idx(int ky, int x, int NyhP) { return ((size_t)(x >> LG_MIXW) * NyhP + ky) * MIXW + (x & (MIXW - 1)); }
 // Addressing: uniform 64-bit base (scalar registers) + 32-bit unsigned byte offset (one vector register) is the form global_load /
 // global_store take directly, with no 64-bit vector arithmetic per access (the fused kernels are partly VALU-issue bound, and a
 // third of their vector instructions was address arithmetic).  Offsets inside one slice of a field stay far below 4 GB.
@@ -108,14 +83,10 @@ template <typename V> __device__ __forceinline__ V& at32(V* base, unsigned idx) 
 // (profiles/r04_ab_write_through.txt): x_grad 7.6 -> 6.7 us, adj_y 12.0 -> 10.8 us, flow_y_fwd 13.5 -> 12.7 us, delta_cols 20.3 -> 19.5 us.
 // NOT for arrays the same workgroup index re-reads in the next stage (the RK state): sc1 drops the line from the L2 and those
 // re-reads then miss (adj_x +14 %).  One store per complex value (8 bytes in single precision): 16-byte forms measured the same.
-#ifndef CMBL_WT_STORES
-#define CMBL_WT_STORES 1
-#endif
 typedef float wt_f2 __attribute__((ext_vector_type(2)));
 typedef float wt_f4 __attribute__((ext_vector_type(4)));
 template <int BYTES> __device__ __forceinline__ void store_wt(void* q, const void* v) {
   static_assert(BYTES == 4 || BYTES == 8 || BYTES == 16, "hand-off stores are 4, 8 or 16 bytes");
-#if CMBL_WT_STORES
   // The compiler cannot see that the asm is a store of more than 64 bits, so it does not keep the two wait states gfx950 needs before a
   // vector instruction overwrites the store's data registers (it scheduled `v_or_b32 v2, ...` right behind `global_store_dwordx4 .., v[2:5]`
   // in k_delta_rows: wrong Gx in single AND double precision).  The s_nop supplies them.
@@ -124,11 +95,6 @@ template <int BYTES> __device__ __forceinline__ void store_wt(void* q, const voi
   if constexpr (BYTES == 16) { const wt_f4 d = *reinterpret_cast<const wt_f4*>(v); asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(q), "v"(d) : "memory"); }
   else if constexpr (BYTES == 8) { const wt_f2 d = *reinterpret_cast<const wt_f2*>(v); asm volatile("global_store_dwordx2 %0, %1, off sc1" : : "v"(q), "v"(d) : "memory"); }
   else { const float d = *reinterpret_cast<const float*>(v); asm volatile("global_store_dword %0, %1, off sc1" : : "v"(q), "v"(d) : "memory"); }
-#else
-  if constexpr (BYTES == 16) *reinterpret_cast<wt_f4*>(q) = *reinterpret_cast<const wt_f4*>(v);
-  else if constexpr (BYTES == 8) *reinterpret_cast<wt_f2*>(q) = *reinterpret_cast<const wt_f2*>(v);
-  else *reinterpret_cast<float*>(q) = *reinterpret_cast<const float*>(v);
-#endif
 }
 // Only for transforms whose lines (a column of the column kernels, a row of the row kernels) are at most 16 KB.  Above that -- 2048^2 in
 // double, 4096^2 in single precision -- sc1 LOSES: delta_cols 198 -> 236 us at 2048^2 fp64 and 497 -> 590 us at 4096^2 fp32 with it in
@@ -144,14 +110,10 @@ template <typename T, bool WT> __device__ __forceinline__ void handoff_store(cx<
 
 // A column tile of C = MIXW columns is ONE contiguous block of the mixed layout: entry (ky, c) of the tile at x0 sits at
 // tile_base(g, x0) + ky * MIXW + c.  Other widths go through mix_idx.
-template <typename V> __device__ __forceinline__ V* tile_base(V* g, int x0, int NyhP) {
-  constexpr int W = mixw_b<(int)sizeof(V)>();
-  return g + (size_t)(x0 >> lg_mixw<W>()) * NyhP * W;
-}
+template <typename V> __device__ __forceinline__ V* tile_base(V* g, int x0, int NyhP) { return g + (size_t)(x0 >> LG_MIXW) * NyhP * MIXW; }
 template <typename T, int C> __device__ __forceinline__ unsigned tile_off(int ky, int c, int x0, int NyhP) {
-  constexpr int W = mixw<T>();
-  if constexpr (C == W) return (unsigned)(ky * W + c);
-  else return (unsigned)(mix_idx<W>(ky, x0 + c, NyhP) - (size_t)(x0 >> lg_mixw<W>()) * NyhP * W);
+  if constexpr (C == MIXW) return (unsigned)(ky * MIXW + c);
+  else return (unsigned)(mix_idx(ky, x0 + c, NyhP) - (size_t)(x0 >> LG_MIXW) * NyhP * MIXW);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -255,19 +217,12 @@ __device__ __forceinline__ void tile_store_mixed(const cx<T>* __restrict__ s, cx
   }
 }
 
-#ifndef CMBL_COL_SPLIT
-#define CMBL_COL_SPLIT 1
-#endif
-// threads that run the sub-stages of one column of a packed-real (M-point) transform: NT/C (two wavefronts, one per half-column; a
-// radix-8 stage then has 32 butterflies per wave, half the lanes idle) or 64 (one wavefront per column, every lane busy, the other
-// wavefronts of the workgroup wait at the barrier and leave the LDS / VALU pipes to the co-resident workgroup)
-#ifndef CMBL_MPT_RT
-#define CMBL_MPT_RT 64
-#endif
-template <int NT, int C> constexpr int mpt_rt() { return CMBL_MPT_RT ? CMBL_MPT_RT : NT / C; }
+// The sub-stages of one column of a packed-real (M-point) transform run on ONE wavefront (WorkRows<64, C> in mpt_inverse_read /
+// mpt_write_forward): every lane busy, the other wavefronts of the workgroup wait at the barrier and leave the LDS / VALU pipes to the
+// co-resident workgroup.  (Two wavefronts, one per half-column, leave half the lanes of a radix-8 stage idle: 32 butterflies per wave.)
 template <int R, int NT, int LGM> struct PairMap {
   static constexpr int M = 1 << LGM, MH = M >> 1, C = (R * NT) >> LGM;
-  static constexpr bool split = CMBL_COL_SPLIT && (R % 2 == 0) && (NT % MH == 0) && (NT % C == 0) && (NT / C == 64 || NT / C == 128) && M >= 32;
+  static constexpr bool split = (R % 2 == 0) && (NT % MH == 0) && (NT % C == 0) && (NT / C == 64 || NT / C == 128) && M >= 32;
   static constexpr int XLG = LGM + 1 >= 11 ? 4 : 3;            // sub-stage radix of the split N-point transforms
   __device__ static __forceinline__ int e(int i, int tid = (int)threadIdx.x) {
     if constexpr (split) {
@@ -343,7 +298,7 @@ __device__ __forceinline__ void mpt_inverse_read(cx<T>* s, const cx<T>* tw, T sc
   using V = typename vreg<T>::type;
   constexpr int M = 1 << LGM, MH = M >> 1, C = PM::C;
   if constexpr (PM::split) {
-    fft_dit_w<T, LD, LGM, LGM + 1, 3, 1>(s, WorkRows<mpt_rt<NT, C>(), C>{1, C, tid}, tw);
+    fft_dit_w<T, LD, LGM, LGM + 1, 3, 1>(s, WorkRows<64, C>{1, C, tid}, tw);
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < R; i += 2) {
@@ -353,7 +308,7 @@ __device__ __forceinline__ void mpt_inverse_read(cx<T>* s, const cx<T>* tw, T sc
       z[i] = vcx(vscale(vadd(u, t), scale)); z[i + 1] = vcx(vscale(vsub(u, t), scale));
     }
   } else {
-    fft_dit<T, NT, LD, LGM, LGM + 1, CMBL_YLGM>(s, C, tw);
+    fft_dit<T, NT, LD, LGM, LGM + 1>(s, C, tw);
 #pragma unroll
     for (int i = 0; i < R; ++i) {
       const int e = PM::e(i, tid), c = e >> LGM, jj = e & (M - 1);
@@ -377,7 +332,7 @@ __device__ __forceinline__ void mpt_write_forward(cx<T>* s, const cx<T>* tw, ZF&
       vstore(p + pad(MH), vmul(vsub(za, zb), vload(tw + 2 * jj)));
     }
     __syncthreads();
-    fft_dif_w<T, LD, LGM, LGM + 1, 3, 1>(s, WorkRows<mpt_rt<NT, C>(), C>{1, C, tid}, tw);
+    fft_dif_w<T, LD, LGM, LGM + 1, 3, 1>(s, WorkRows<64, C>{1, C, tid}, tw);
     __syncthreads();
   } else {
 #pragma unroll
@@ -386,7 +341,7 @@ __device__ __forceinline__ void mpt_write_forward(cx<T>* s, const cx<T>* tw, ZF&
       s[c * LD + pad(jj)] = zf(i);
     }
     __syncthreads();
-    fft_dif<T, NT, LD, LGM, LGM + 1, CMBL_YLGM>(s, C, tw);
+    fft_dif<T, NT, LD, LGM, LGM + 1>(s, C, tw);
   }
 }
 
@@ -408,19 +363,6 @@ template <typename T, int NT, int LGN, int LGC> struct PairStage {
         const int k = e >> LGC;
         const unsigned gi = tile_off<T, C>(k, e & (C - 1), x0, mixed_rows(M + 1));
         X[i] = at32(tX, gi); Y[i] = at32(tY, gi); l[i] = at32(ly, (unsigned)k);
-      }
-    }
-  }
-  // the two tiles alone (l = ly[k] depends on the entry index only: a workgroup that walks several tiles keeps it from its first issue)
-  __device__ __forceinline__ void issue_xy(const cx<T>* __restrict__ gX, const cx<T>* __restrict__ gY, int x0, int tid = (int)threadIdx.x) {
-    const cx<T>* tX = tile_base(gX, x0, mixed_rows(M + 1));
-    const cx<T>* tY = tile_base(gY, x0, mixed_rows(M + 1));
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-      const int e = tid + i * NT;
-      if (e < TOT) {
-        const unsigned gi = tile_off<T, C>(e >> LGC, e & (C - 1), x0, mixed_rows(M + 1));
-        X[i] = at32(tX, gi); Y[i] = at32(tY, gi);
       }
     }
   }
@@ -453,44 +395,28 @@ template <typename T, int NT, int LGN, int LGC> struct PairStage {
 // The mixed-layout side is a gather / scatter of RPW x 4 values per x/4 (one 128-byte line for RPW = 4, fp32), the F-layout side
 // contiguous rows.  Row r of the group sits at LDS offset r * row_ld(Nx); row_ld = 4 (mod 16) slots, so that the 16 lanes that
 // write one gathered line (4 rows x 4 values) hit 16 different bank pairs.
-#ifndef CMBL_ROW_ROT
-#define CMBL_ROW_ROT(ky0) 0        // per-workgroup starting point of the x/4 walk, e.g. (((ky0) * 29) >> 2): measured, no effect
-#endif
 constexpr int ROW_RT = 128;                                              // threads per row
 __host__ __device__ constexpr int row_nt(int rpw) { return ROW_RT * rpw; }   // workgroup size
 __host__ __device__ constexpr int row_ld(int n) { return pad(n) + ((4 - pad(n) % 16) + 16) % 16; }
-// rows per workgroup: as many of 4, 2, 1 as fit the 160 KB of LDS next to the twiddle table (NA row sets: 1, or 2 for the adjoint pass)
-#ifndef CMBL_RPW_SMALL
-#define CMBL_RPW_SMALL 4
-#endif
-#ifndef CMBL_RPW_BIG
-#define CMBL_RPW_BIG 4        // Nx >= 1024; 2 measured slower for every row kernel in the timed mode (profiles/r04_probe_short_row_groups.txt)
-#endif
-#ifndef CMBL_XLG_SMALL
-#define CMBL_XLG_SMALL 3      // Nx < 1024: radix-8 stages keep 64+ butterflies per stage for the two waves of a row (512²: step 2.58 -> 2.32 ms)
-#endif
 // Twiddle-table entries a row kernel keeps in LDS: the first half of the circle.  With the stage twiddles formed from ONE table read
 // (stage_twiddles: index j * 2^sh < Nx / 2) and the fused top level (index < Nx / 2) nothing beyond it is read; the 4 KB saved at
 // Nx = 1024 are 4 KB less to load per workgroup.
-static_assert(CMBL_TW_REC == 2, "row kernels load half of the twiddle circle: needs the one-read stage twiddles in both precisions");
 // 2048-point rows in double precision keep a QUARTER (8 KB instead of 16; the second quarter is -i times the first: tw_read, fft_lds.hpp).
 // It was built so that two row groups of two rows (2 x 78 KB) could share a CU where one group of four rows (156 KB) is alone -- two
 // out-of-phase workgroups per CU.  Measured (profiles/r05_ab_fp64_rows_2wg_rejected.txt): the d/dx pass does not change, the adjoint row
-// pass on one-row groups is 7-9 % SLOWER, so the group heights stay (CMBL_F64_ROWS_2WG = 0); the smaller table stays as well (8 KB less to
-// load per workgroup, results identical).
+// pass on one-row groups is 7-9 % SLOWER, so the group heights stay; the smaller table stays as well (8 KB less to load per workgroup,
+// results identical).
 template <typename T> __host__ __device__ constexpr bool row_tw_quarter(int lgnx) { return sizeof(T) == 8 && lgnx == 11; }
 template <typename T> __host__ __device__ constexpr int row_tw(int nx) { return row_tw_quarter<T>(ilog2c(nx)) ? nx >> 2 : nx >> 1; }
 template <typename T, int LGNX> constexpr int row_qlg() { return row_tw_quarter<T>(LGNX) ? LGNX - 2 : 0; }
-// fused radix-2 levels per stage of a row transform
-__host__ __device__ constexpr int row_xlg(int lgnx) { return lgnx >= 10 ? CMBL_XLG : CMBL_XLG_SMALL; }
-#ifndef CMBL_F64_ROWS_2WG
-#define CMBL_F64_ROWS_2WG 0   // 1: quarter-table shapes take the tallest row group of which TWO fit a CU -- measured slower (profiles/r05_ab_fp64_rows_2wg_rejected.txt)
-#endif
+// fused radix-2 levels per stage of a row transform: radix-16 from Nx = 1024 on (radix-8 measured 5 % faster for L*f alone but 3 % slower
+// for the gradient step); radix-8 below, which keeps 64+ butterflies per stage for the two waves of a row (512^2: step 2.58 -> 2.32 ms)
+__host__ __device__ constexpr int row_xlg(int lgnx) { return lgnx >= 10 ? 4 : 3; }
+// rows per workgroup: as many of 4, 2, 1 as fit the 160 KB of LDS next to the twiddle table (NA row sets: 1, or 2 for the adjoint pass).
+// (2 rows at Nx >= 1024 measured slower for every row kernel in the timed mode: profiles/r04_probe_short_row_groups.txt)
 template <typename T> __host__ __device__ constexpr int row_rpw(int lgnx, int na) {
-  const size_t budget = (CMBL_F64_ROWS_2WG && row_tw_quarter<T>(lgnx)) ? 80 * 1024 : 160 * 1024;
-  for (int pass = 0; pass < 2; ++pass)                                   // second pass: nothing fits twice -> whatever fits once
-    for (int rpw = (lgnx >= 10 ? CMBL_RPW_BIG : CMBL_RPW_SMALL); rpw >= 1; rpw >>= 1)
-      if (((size_t)row_tw<T>(1 << lgnx) + (size_t)na * rpw * row_ld(1 << lgnx)) * sizeof(cx<T>) <= (pass == 0 ? budget : (size_t)160 * 1024)) return rpw;
+  for (int rpw = 4; rpw >= 1; rpw >>= 1)
+    if (((size_t)row_tw<T>(1 << lgnx) + (size_t)na * rpw * row_ld(1 << lgnx)) * sizeof(cx<T>) <= (size_t)160 * 1024) return rpw;
   return 0;
 }
 // Row-group heights compiled BESIDES the LDS-fit maximum.  Below Nx = 1024 a launch over groups of four rows has fewer workgroups than
@@ -529,26 +455,24 @@ template <typename T> __device__ __forceinline__ CxVec<T>& vec32(cx<T>* base, un
 
 // mixed layout (slice bases g[a]) -> the NA row sets in LDS, through the top DIF level:
 //   s[a] <- x[a] + x[a + N/2],   s[a + N/2] <- (x[a] - x[a + N/2]) * W_N^a        (twg: the global twiddle table exp(-2 pi i k / N))
-// All loads of the thread are issued before the first LDS store.
-// (CMBL_ROW_ROT lets every workgroup walk x/4 from its own starting point, so that the workgroups of a launch do not touch the same
-// 16 KB window at the same moment; measured on MI355X: no difference, the default is no rotation)
+// All loads of the thread are issued before the first LDS store.  (Every workgroup walking x/4 from its own starting point, so that the
+// workgroups of a launch do not touch the same 16 KB window at the same moment, measured no different on MI355X.)
 template <typename T, int LGNX, int RPW, int NA> struct RowsMixedStage {
   using V = typename vreg<T>::type;
-  static constexpr int Nx = 1 << LGNX, NH = Nx >> 1, LD = row_ld(Nx), VE = 16 / (int)sizeof(cx<T>), UPG = mixw<T>() / VE, NT = row_nt(RPW);
+  static constexpr int Nx = 1 << LGNX, NH = Nx >> 1, LD = row_ld(Nx), VE = 16 / (int)sizeof(cx<T>), UPG = MIXW / VE, NT = row_nt(RPW);
   static constexpr int TOT = RPW * NH / VE, K = (TOT + NT - 1) / NT;
   CxVec<T> va[NA][K] = {}, vb[NA][K] = {}, w[K] = {};
   // tid: index of the thread among the NT that share this load (threadIdx.x unless several row sets are loaded side by side)
   __device__ __forceinline__ void issue(const cx<T>* const (&g)[NA], const cx<T>* __restrict__ twg, int NyhP, int ky0, int nr, int tid = threadIdx.x) {
-    const int rot = CMBL_ROW_ROT(ky0);
 #pragma unroll
     for (int i = 0; i < K; ++i) {
-      const int u = tid + i * NT, xt = (u / (UPG * RPW) + rot) & (NH / mixw<T>() - 1), r = (u / UPG) % RPW, c = (u % UPG) * VE;
+      const int u = tid + i * NT, xt = (u / (UPG * RPW)) & (NH / MIXW - 1), r = (u / UPG) % RPW, c = (u % UPG) * VE;
       if ((TOT % NT == 0 || u < TOT) && r < nr) {
-        vload32(w[i], twg, (unsigned)(xt * mixw<T>() + c));
-        const unsigned o = (unsigned)((xt * NyhP + r) * mixw<T>() + c), ob = (unsigned)(((xt + NH / mixw<T>()) * NyhP + r) * mixw<T>() + c);
+        vload32(w[i], twg, (unsigned)(xt * MIXW + c));
+        const unsigned o = (unsigned)((xt * NyhP + r) * MIXW + c), ob = (unsigned)(((xt + NH / MIXW) * NyhP + r) * MIXW + c);
 #pragma unroll
         for (int a = 0; a < NA; ++a) {
-          const cx<T>* ga = g[a] + (size_t)ky0 * mixw<T>();                    // uniform part of the address
+          const cx<T>* ga = g[a] + (size_t)ky0 * MIXW;                    // uniform part of the address
           vload32(va[a][i], ga, o);
           vload32(vb[a][i], ga, ob);
         }
@@ -557,15 +481,14 @@ template <typename T, int LGNX, int RPW, int NA> struct RowsMixedStage {
   }
   // row set a -> the LDS rows at s
   __device__ __forceinline__ void commit(int a, cx<T>* __restrict__ s, int ky0, int nr, int tid = threadIdx.x) const {
-    const int rot = CMBL_ROW_ROT(ky0);
 #pragma unroll
     for (int i = 0; i < K; ++i) {
-      const int u = tid + i * NT, xt = (u / (UPG * RPW) + rot) & (NH / mixw<T>() - 1), r = (u / UPG) % RPW, c = (u % UPG) * VE;
+      const int u = tid + i * NT, xt = (u / (UPG * RPW)) & (NH / MIXW - 1), r = (u / UPG) % RPW, c = (u % UPG) * VE;
       if ((TOT % NT == 0 || u < TOT) && r < nr) {
 #pragma unroll
         for (int e = 0; e < VE; ++e) {
           const V xa = vfrom(va[a][i].v[e]), xb = vfrom(vb[a][i].v[e]);
-          cx<T>* p = s + r * LD + pad(xt * mixw<T>() + c) + e;                 // c even: pad(x + 1) == pad(x) + 1; pad(x + N/2) == pad(x) + pad(N/2)
+          cx<T>* p = s + r * LD + pad(xt * MIXW + c) + e;                 // c even: pad(x + 1) == pad(x) + 1; pad(x + N/2) == pad(x) + pad(N/2)
           vstore(p, vadd(xa, xb));
           vstore(p + pad(NH), vmul(vsub(xa, xb), vfrom(w[i].v[e])));
         }
@@ -586,21 +509,20 @@ template <typename T, int LGNX, int RPW>
 __device__ __forceinline__ void rows_store_mixed_dit(const cx<T>* __restrict__ s, cx<T>* __restrict__ g, const cx<T>* __restrict__ tw, int NyhP, int ky0, int nr, T scale,
                                                      int nyq = -1 /* >= 0: drop Im of the ky = 0 and ky = nyq rows (what c2r ignores) */, int tid = threadIdx.x) {
   using V = typename vreg<T>::type;
-  constexpr int Nx = 1 << LGNX, NH = Nx >> 1, LD = row_ld(Nx), VE = 16 / (int)sizeof(cx<T>), UPG = mixw<T>() / VE, NT = row_nt(RPW), TOT = RPW * NH / VE;
-  const int rot = CMBL_ROW_ROT(ky0);
+  constexpr int Nx = 1 << LGNX, NH = Nx >> 1, LD = row_ld(Nx), VE = 16 / (int)sizeof(cx<T>), UPG = MIXW / VE, NT = row_nt(RPW), TOT = RPW * NH / VE;
   for (int u = tid; u < TOT; u += NT) {
-    const int xt = (u / (UPG * RPW) + rot) & (NH / mixw<T>() - 1), r = (u / UPG) % RPW, c = (u % UPG) * VE;
+    const int xt = (u / (UPG * RPW)) & (NH / MIXW - 1), r = (u / UPG) % RPW, c = (u % UPG) * VE;
     if (r < nr) {
       CxVec<T> oa, ob;
 #pragma unroll
       for (int e = 0; e < VE; ++e) {
-        const cx<T>* p = s + r * LD + pad(xt * mixw<T>() + c) + e;
-        const V uu = vload(p), t = vmulc(vload(p + pad(NH)), tw_read<T, row_qlg<T, LGNX>()>(tw, xt * mixw<T>() + c + e));
+        const cx<T>* p = s + r * LD + pad(xt * MIXW + c) + e;
+        const V uu = vload(p), t = vmulc(vload(p + pad(NH)), tw_read<T, row_qlg<T, LGNX>()>(tw, xt * MIXW + c + e));
         oa.v[e] = vcx(vscale(vadd(uu, t), scale)); ob.v[e] = vcx(vscale(vsub(uu, t), scale));
         if (nyq >= 0 && (ky0 + r == 0 || ky0 + r == nyq)) { oa.v[e].y = T(0); ob.v[e].y = T(0); }
       }
-      cx<T>* gk = g + (size_t)ky0 * mixw<T>();                                  // uniform part of the address
-      const unsigned ia = (unsigned)((xt * NyhP + r) * mixw<T>() + c), ib = (unsigned)(((xt + NH / mixw<T>()) * NyhP + r) * mixw<T>() + c);
+      cx<T>* gk = g + (size_t)ky0 * MIXW;                                  // uniform part of the address
+      const unsigned ia = (unsigned)((xt * NyhP + r) * MIXW + c), ib = (unsigned)(((xt + NH / MIXW) * NyhP + r) * MIXW + c);
       if constexpr (wt_line<T>(Nx)) {                                   // hand-off: see handoff_store
         store_wt<16>(reinterpret_cast<char*>(gk) + ia * (unsigned)sizeof(cx<T>), &oa);
         store_wt<16>(reinterpret_cast<char*>(gk) + ib * (unsigned)sizeof(cx<T>), &ob);
@@ -756,7 +678,7 @@ __global__ __launch_bounds__(NT) void k_y_mask(const cx<T>* __restrict__ in, cx<
 //   MODE 1: inverse  (F -> mixed), scaled by 1/Nx
 //   MODE 2: x-derivative  (mixed -> mixed):  ifft_x( i*lx * fft_x(row) ) / Nx        (src/proj_lambert.jl:146-159, coord 1)
 template <typename T, int MODE, int LGNX, int RPW>
-__global__ __launch_bounds__(row_nt(RPW), row_min_waves<T>()) void k_x_fft(const cx<T>* __restrict__ in, cx<T>* __restrict__ out,
+__global__ __launch_bounds__(row_nt(RPW), 1) void k_x_fft(const cx<T>* __restrict__ in, cx<T>* __restrict__ out,
                                                                           const cx<T>* __restrict__ twX, T dlx_over_Nx, int Nyh) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int Nx = 1 << LGNX, LD = row_ld(Nx), NT = row_nt(RPW);

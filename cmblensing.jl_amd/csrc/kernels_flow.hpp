@@ -34,9 +34,6 @@ __device__ __forceinline__ void flow_pm(T t, T gx, T gy, T hxx, T hyx, T hyy, T&
 // tile is small enough (R <= 4 single precision) that the cap costs at most a handful of spilled registers.
 template <typename T> constexpr int col_min_waves(int R, int NT) { return (sizeof(T) == 4 && R <= 4 && NT >= 256) ? 4 : 1; }
 
-// shapes whose column workgroups are alone on their CU and walk several tiles with software-pipelined loads (delta_y_body_pipelined)
-template <typename T> constexpr bool col_pipelined(int lgm) { return sizeof(T) == 8 && lgm >= 10; }
-
 // pcx/pcy: p(t) of the current stage time from the per-phi cache (k_pcache), or nullptr -> formed from the five maps
 template <typename T> struct PhiMaps { const T *gx, *gy, *hxx, *hyx, *hyy; int Bphi; const T *pcx, *pcy; };
 
@@ -149,7 +146,7 @@ __device__ __forceinline__ void npt_inverse_read(cx<T>* s, const cx<T>* tw, T sc
       read_pair_dit(s + c * LD, jj, M, tw, scale, x[i], y[i], x[i + 1], y[i + 1]);
     }
   } else {
-    fft_dit<T, NT, LD, LGN, LGN, CMBL_YLGN>(s, C, tw);
+    fft_dit<T, NT, LD, LGN, LGN>(s, C, tw);
 #pragma unroll
     for (int i = 0; i < R; ++i) {
       const int e = PM::e(i, tid), c = e >> LGM, jj = e & (M - 1);
@@ -183,7 +180,7 @@ __device__ __forceinline__ void npt_write_forward(cx<T>* s, const cx<T>* tw, XY&
       write_pair(s + c * LD, jj, x, y);
     }
     __syncthreads();
-    fft_dif<T, NT, LD, LGN, LGN, CMBL_YLGN>(s, C, tw);
+    fft_dif<T, NT, LD, LGN, LGN>(s, C, tw);
   }
 }
 
@@ -199,8 +196,8 @@ __device__ __forceinline__ void npt_write_forward(cx<T>* s, const cx<T>* tw, XY&
 // compiler's s_waitcnt bookkeeping: nothing waits for them; they return during the transforms that follow, and `drain()` -- one s_waitcnt before the
 // workgroup's last stores -- makes sure that none can land in LDS that already belongs to another workgroup.
 template <typename T, int NT, int LGM, int C, int NARR> struct TouchTiles {
-  static constexpr int M = 1 << LGM, NyhP = mixed_rows(M + 1), RPL = 128 / (mixw<T>() * (int)sizeof(cx<T>)), NL = (M + 1 + RPL - 1) / RPL;
-  static constexpr int NB = (C + mixw<T>() - 1) / mixw<T>(), K = (NL * NB + NT - 1) / NT;
+  static constexpr int M = 1 << LGM, NyhP = mixed_rows(M + 1), RPL = 128 / (MIXW * (int)sizeof(cx<T>)), NL = (M + 1 + RPL - 1) / RPL;
+  static constexpr int NB = (C + MIXW - 1) / MIXW, K = (NL * NB + NT - 1) / NT;
   static constexpr int PAD_BYTES = 256;                                   // one wave-instruction of 64 lanes x 4 bytes; every wave uses the same pad
   // pad: LDS byte address of the pad (wave-uniform)
   __device__ __forceinline__ static void issue(const cx<T>* const (&g)[NARR > 0 ? NARR : 1] /*slice bases*/, int x0, unsigned pad) {
@@ -213,7 +210,7 @@ template <typename T, int NT, int LGM, int C, int NARR> struct TouchTiles {
         int i = threadIdx.x + k * NT;
         if (i >= NL * NB) i = NL * NB - 1;                                  // the spare lanes of the last round re-touch the last line
         const int blk = i / NL, ln = i - blk * NL;
-        const void* q = tg + ((size_t)blk * NyhP + (size_t)ln * RPL) * mixw<T>();
+        const void* q = tg + ((size_t)blk * NyhP + (size_t)ln * RPL) * MIXW;
         unsigned keep;
         // M0 (the LDS-DMA destination base) is compiler-reserved: set and restored inside the statement (cdna_hip_programming.md, LDS-DMA recipe)
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(q), "s"(m0v) : "memory");
@@ -223,11 +220,8 @@ template <typename T, int NT, int LGM, int C, int NARR> struct TouchTiles {
   __device__ __forceinline__ static void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 };
 
-#ifndef CMBL_TOUCH_ALL
-#define CMBL_TOUCH_ALL 0            // 1: compile the touch prefetch into every column kernel (experiment builds)
-#endif
 // compiled into the one-workgroup-per-CU shapes only (every other instantiation is byte for byte what it was)
-template <typename T> constexpr bool col_touch(int lgm) { return CMBL_TOUCH_ALL || (sizeof(T) == 8 && lgm >= 10); }
+template <typename T> constexpr bool col_touch(int lgm) { return sizeof(T) == 8 && lgm >= 10; }
 // LDS byte address of the touch pad: right behind the column tile (twiddles M + C columns of LD slots); the launch asks for TOUCH_PAD bytes more
 constexpr int TOUCH_PAD = 256;
 template <typename T, int C, int LD> __device__ __forceinline__ unsigned touch_pad(int M) { return (unsigned)(((size_t)M + (size_t)C * LD) * sizeof(cx<T>)); }
@@ -486,7 +480,7 @@ __device__ __forceinline__ void adj_x_body(const AdjXArgs<T>& a, unsigned char* 
 }
 
 template <typename T, int LGNX, int RPW>
-__global__ __launch_bounds__(row_nt(RPW), row_min_waves<T>()) void k_adj_x(AdjXArgs<T> a) {
+__global__ __launch_bounds__(row_nt(RPW), 1) void k_adj_x(AdjXArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   adj_x_body<T, LGNX, RPW>(a, smem, blockIdx.x, gridDim.x);
 }
@@ -632,116 +626,6 @@ __device__ __forceinline__ void delta_y_body(const DeltaYArgs<T>& d, unsigned ch
   CMBL_WSTAMP(15);
 }
 
-#ifdef CMBL_EXPERIMENT_COL_PIPELINE
-// EXPERIMENT, measured and rejected in round 5 (-DCMBL_EXPERIMENT_COL_PIPELINE; profiles/r05_ab_col_pipeline_rejected.txt).
-// The same stage with the workgroup walking TPW tiles and the next tile's pair tile requested under the current tile's last phase.  For
-// shapes whose register footprint leaves ONE workgroup per CU -- 2048 rows in double precision: 244 registers x 512 threads is the CU's
-// whole register file -- nothing overlaps a workgroup's exposed waits: in-kernel stamps at 2048^2 fp64
-// (profiles/r05_stamps_delta_cols_2048_f64.txt) show 18.9k of a workgroup's 45.8k cycles spent waiting for its pair tile.  What killed it is
-// the compiler, not the idea: as soon as one thread walks two tiles -- as a loop or unrolled, WITH or WITHOUT the prefetch -- hipcc keeps
-// the tile-independent address values of all load / store sites live across the tiles (loop-invariant code motion / common
-// subexpressions) and spills 228-596 bytes per lane, which the launch then moves through the vector memory path: (grad L)' 14.4 -> 17.0 ms.
-template <typename T, int R, int NT, int LGM, int TPW>
-__device__ __forceinline__ void delta_y_body_pipelined(const DeltaYArgs<T>& d, unsigned char* smem, size_t sl) {
-  constexpr int tpw = TPW;
-  using G = ColTile<R, NT, LGM>;
-  constexpr int M = G::M, LGN = G::LGN, LD = G::LDN, Nyh = G::Nyh, C = G::C, LGC = G::LGC;
-  const FlowYArgs<T>& a = d.f;
-  cx<T>* tw = reinterpret_cast<cx<T>*>(smem);
-  cx<T>* s = tw + M;
-  const int Nx = a.Nx, ntiles = (int)gridDim.x * tpw;
-  const int bphi = a.ph.Bphi == 1 ? 0 : (int)(sl / a.P);
-  const T invNy = T(1) / T(2 * M);
-  constexpr int NyhP = mixed_rows(Nyh);
-  const size_t moff = sl * (size_t)NyhP * Nx;
-  using PM = PairMap<R, NT, LGM>;
-  // tile k of this workgroup: the virtual block blockIdx.x + k * gridDim.x of a one-tile-per-block launch (same XCD for every k when
-  // gridDim.x is a multiple of 8; neighbouring workgroups of an XCD walk neighbouring tiles in step and share their 64-byte lines)
-  auto tile_x0 = [&](int k) { return xcd_tile((int)blockIdx.x + k * (int)gridDim.x, ntiles) * C; };
-  TwStage<T, NT, M> twr;
-  PairStage<T, NT, LGN, LGC> ps;
-  HalfStage<T, NT, LGM, LGC> th;
-  cx<T> px[R], py[R];
-  // CMBL_PL_HEAD = 1: the pair tile alone is prefetched (it alone gates the first transform); 2: p(t) and the delta-f tile as well (118
-  // registers carried across the loop: 596 bytes of scratch per lane in double precision)
-#ifndef CMBL_PL_HEAD
-#define CMBL_PL_HEAD 1
-#endif
-  // tid: the thread index as a value the compiler cannot see through, a fresh one per tile -- every per-thread address below is then recomputed
-  // per tile instead of being hoisted above the tile loop and kept live across it (round 5's version spilled 228-596 bytes per lane that way;
-  // the trick is kernels_small.hpp's)
-  auto issue_rest = [&](int x0, int tid) {
-    const size_t pbase = ((size_t)bphi * Nx + x0) * M;
-#pragma unroll
-    for (int i = 0; i < R; ++i) load_p_only(a.ph, pbase, (unsigned)PM::e(i, tid), a.rk.t, px[i], py[i]);
-    th.issue(d.H + moff, a.twY, x0, tid);
-  };
-  auto issue_head = [&](int x0, int tid) {
-    ps.issue_xy(a.Gx + moff, a.A + moff, x0, tid);
-    if (CMBL_PL_HEAD >= 2) issue_rest(x0, tid);
-  };
-  auto fresh_tid = [] { int t = (int)threadIdx.x; asm volatile("" : "+v"(t)); return t; };
-  twr.issue(a.twY);
-  ps.issue(a.Gx + moff, a.A + moff, a.ly, Nx, tile_x0(0), fresh_tid());
-  if (CMBL_PL_HEAD >= 2) issue_rest(tile_x0(0), fresh_tid());
-  twr.commit(tw);
-#pragma unroll
-  for (int k = 0; k < tpw; ++k) {
-    const int x0 = tile_x0(k);
-    const int tid = fresh_tid();
-    const size_t mbase = (sl * Nx + x0) * (size_t)M;
-    if (CMBL_PL_HEAD == 0 && k > 0) ps.issue_xy(a.Gx + moff, a.A + moff, x0, tid);          // timing aid: several tiles, nothing prefetched
-    ps.template commit<LD>(s, tid);
-    if (CMBL_PL_HEAD < 2) issue_rest(x0, tid);
-    __syncthreads();
-    cx<T> dx[R], dy[R];
-    npt_inverse_read<T, R, NT, LGM, LD>(s, tw, invNy, dx, dy, tid);
-    __syncthreads();
-    th.template commit<LD>(s, tid);
-    cx<T>* y0p = reinterpret_cast<cx<T>*>(a.y0) + mbase;
-    cx<T>* accp = reinterpret_cast<cx<T>*>(a.acc) + mbase;
-    cx<T> fn[R], ldf[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      const unsigned e = PM::e(i, tid);
-      fn[i] = at32(reinterpret_cast<const cx<T>*>(a.y0r) + mbase, e);
-      ldf[i] = a.rk.stage == 1 ? mk<T>(0, 0) : at32(accp, e);
-    }
-    __syncthreads();
-    cx<T> lz[R];
-    mpt_inverse_read<T, R, NT, LGM, LD>(s, tw, invNy, lz, tid);
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      const unsigned e = PM::e(i, tid);
-      cx<T> y0 = fn[i], acc = ldf[i];
-      ldf[i] = lz[i];
-      nt_store(&at32(reinterpret_cast<cx<T>*>(d.w1p) + mbase, e), pmul(ldf[i], dx[i]));
-      nt_store(&at32(reinterpret_cast<cx<T>*>(d.w2p) + mbase, e), pmul(ldf[i], dy[i]));
-      const cx<T> kv = pmul(px[i], dx[i]) + pmul(py[i], dy[i]);
-      fn[i] = rk_update(a.rk, kv, y0, acc);
-      if (a.rk.stage == 4) at32(y0p, e) = y0; else at32(accp, e) = acc;
-    }
-    __syncthreads();
-    npt_write_forward<T, R, NT, LGM, LD>(s, tw, [&](int i, cx<T>& x, cx<T>& y) { x = pmul(px[i], ldf[i]); y = pmul(py[i], ldf[i]); }, tid);
-    {
-      cx<T>* Wx = tile_base(d.Wx + moff, x0, NyhP); cx<T>* Wy = tile_base(d.Wy + moff, x0, NyhP);
-      pair_split<T, NT, LD, LGN, LGC, G::RZ>(s, [&](int i, int kk, int c, cx<T> A, cx<T> B) {
-        const unsigned gi = tile_off<T, C>(kk, c, x0, NyhP);
-        handoff_store<T, wt_cols<T>(C, M)>(Wx, gi, A); handoff_store<T, wt_cols<T>(C, M)>(Wy, gi, mul_il(B, ps.l[i]));
-      }, tid);
-    }
-    // the next tile's head: everything it waits for first, requested while this tile's last transform runs
-    if (CMBL_PL_HEAD > 0 && k + 1 < tpw) issue_head(tile_x0(k + 1), fresh_tid());
-    if (!a.rk.last) {
-      __syncthreads();
-      mpt_write_forward<T, R, NT, LGM, LD>(s, tw, [&](int i) { return fn[i]; }, tid);
-      half_store<T, NT, LD, LGM, LGC>(s, a.Anext + moff, tw, x0, tid);
-    }
-    __syncthreads();                                          // the tile is rewritten by the next commit
-  }
-}
-
-#endif
 // ---------------------------------------------------------------------------------------------
 // delta-phi.  Its velocity (src/lenseflow.jl:198-206),
 //     d(dphi)/dt = i lx F(u1) + i ly F(u2) - lx^2 F(a) - lx ly F(b) - ly^2 F(c),   F = rfft2,
@@ -762,17 +646,11 @@ __device__ __forceinline__ void nt_load16(const double* p, double (&o)[2]) { con
 // k_dphi_reduce: stages whose loads are in flight together per thread (SU) and the register budget (waves per SIMD).  With SU = 4 the
 // kernel needed 165 registers = 3 waves per SIMD = 768 resident blocks for a grid of 1024 at 1024^2: a third of the blocks ran in a
 // second round (121 us).  SU = 2 fits 128 registers, the whole grid is resident at once: 89 us (512 MB -> 5.8 TB/s).
-#ifndef CMBL_DPHI_WAVES
-#define CMBL_DPHI_WAVES 4
-#endif
-#ifndef CMBL_DPHI_SU
-#define CMBL_DPHI_SU 2
-#endif
 // (t_s, c_s) of up to 64 stages ride in the kernel arguments (no upload per flow); longer flows pass a device table
 template <typename T> struct TcTab { static constexpr int MAXST = 64; T v[2 * MAXST]; };
 // V = pixels per thread: 16-byte loads when npix allows it, 1 for the any-size path (odd pixel counts)
 template <typename T, int V = 16 / (int)sizeof(T)>
-__global__ __launch_bounds__(NTP, CMBL_DPHI_WAVES) void k_dphi_reduce(PhiMaps<T> ph, const T* __restrict__ W /*[nst][2][slices][npix]*/,
+__global__ __launch_bounds__(NTP, 4) void k_dphi_reduce(PhiMaps<T> ph, const T* __restrict__ W /*[nst][2][slices][npix]*/,
                                                     TcTab<T> tcv, const T* __restrict__ tcd /*[nst][2] = (t_s, c_s), or nullptr: tcv*/, T* __restrict__ out /*[5][B][npix]*/,
                                                     long npix, int P, int B, int nst, int alias_quirk) {
   struct alignas(V * sizeof(T)) Vec { T v[V]; };
@@ -786,7 +664,7 @@ __global__ __launch_bounds__(NTP, CMBL_DPHI_WAVES) void k_dphi_reduce(PhiMaps<T>
     const Vec hyy = *reinterpret_cast<const Vec*>(ph.hyy + pb + i);
     double U1[V] = {}, U2[V] = {}, A[V] = {}, Bb[V] = {}, Cc[V] = {};
     // the per-stage products are read exactly once: non-temporal loads, SU stages' worth requested before the first is used
-    constexpr int SU = CMBL_DPHI_SU;
+    constexpr int SU = 2;
     for (int s0 = 0; s0 < nst; s0 += SU) {
       Vec w1[SU], w2[SU];
 #pragma unroll
@@ -863,15 +741,8 @@ __global__ __launch_bounds__(NT, col_min_waves<T>(R, NT)) void k_delta_cols(Delt
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   delta_y_body<T, R, NT, LGM>(d, smem, blockIdx.y);
 }
-#ifdef CMBL_EXPERIMENT_COL_PIPELINE
-template <typename T, int R, int NT, int LGM, int TPW>
-__global__ __launch_bounds__(NT, col_min_waves<T>(R, NT)) void k_delta_cols_pl(DeltaYArgs<T> d) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  delta_y_body_pipelined<T, R, NT, LGM, TPW>(d, smem, blockIdx.y);
-}
-#endif
 template <typename T, int LGNX, int RPW>
-__global__ __launch_bounds__(row_nt(RPW), row_min_waves<T>()) void k_delta_rows(AdjXArgs<T> a, GradXArgs<T> g, int nblk_adj) {
+__global__ __launch_bounds__(row_nt(RPW), 1) void k_delta_rows(AdjXArgs<T> a, GradXArgs<T> g, int nblk_adj) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int b = blockIdx.x;
 #ifdef CMBL_STAMPS_ROWS            // launch timeline of the last launch that has both parts (tools/gpu_stamps_rows.py)

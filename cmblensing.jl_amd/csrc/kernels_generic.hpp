@@ -144,15 +144,8 @@ __device__ __forceinline__ cx<T> gen_fetch(const GenDft<T>& a, size_t sl, int se
   }
   return a.inverse ? conj(v) : v;                                     // e^{+i} transform = conj(forward(conj x))
 }
-#ifndef CMBL_WT_GEN
-#define CMBL_WT_GEN 1
-#endif
 template <typename V> __device__ __forceinline__ void gen_wt(V* p, V v, bool wt) {
-#if CMBL_WT_GEN
   if (wt) store_wt<(int)sizeof(V)>(p, &v); else *p = v;
-#else
-  *p = v;
-#endif
 }
 // y = Z[k]; yr = Z[(N - k) % N] (only read for a real pair)
 template <typename T>

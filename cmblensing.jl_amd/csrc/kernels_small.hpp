@@ -36,10 +36,7 @@ template <typename T, int LGNY, int LGNX> struct SmallGeom {
   static constexpr int MAXLG = (sizeof(T) == 8 || WORDS > 8192) ? 3 : 4;   //                    // largest radix of a stage: 16 (8 in double precision: 64 registers of operands)
   // per-stage address recomputation (see the kernels) from 8 pixels per thread on; below that the registers have room for the hoisted
   // addresses and the stage saves their arithmetic: 64^2 L*f 0.146 -> 0.119 ms, L'g 0.167 -> 0.146 ms (profiles/r06_ab_small_flow.txt)
-#ifndef CMBL_SMALL_LAUNDER_PPT
-#define CMBL_SMALL_LAUNDER_PPT 8
-#endif
-  static constexpr bool LAUNDER = PPT >= CMBL_SMALL_LAUNDER_PPT;
+  static constexpr bool LAUNDER = PPT >= 8;
   static constexpr bool delta_fits = NPIX * (int)sizeof(T) <= 4096 * 4;     // the one-launch delta flow: 64 x 64 in single, 32 x 64 in double precision
   static constexpr size_t lds = ((size_t)NTW + (size_t)Nx * LDY) * sizeof(cx<T>);
   // (double precision up to 64 x 64: beyond that the adjoint kernel's state does not fit the register file of a 512-thread workgroup)
@@ -247,25 +244,13 @@ __global__ __launch_bounds__((SmallGeom<T, LGNY, LGNX>::NT)) void k_small_flow(S
         __syncthreads();
       }
       // p(t) of this stage: requested before the last transform, consumed after it
-#ifndef SM_LATE_P
       T px[PPT], py[PPT];
       {
         const T* pc = a.pcache + (size_t)(2 * kt) * ps + pb;
 #pragma unroll
         for (int i = 0; i < PPT; ++i) { px[i] = pc[tid + i * NT]; py[i] = pc[ps + tid + i * NT]; SM_FENCE(i); }
       }
-#endif
-#ifdef SM_LATE_P
       sm_dit<T, NT, Nx, LDY, 1, LGNY, LGNTW, G::MAXLG>(W, tw, tid);
-      T px[PPT], py[PPT];
-      {
-        const T* pc = a.pcache + (size_t)(2 * kt) * ps + pb;
-#pragma unroll
-        for (int i = 0; i < PPT; ++i) { px[i] = pc[tid + i * NT]; py[i] = pc[ps + tid + i * NT]; SM_FENCE(i); }
-      }
-#else
-      sm_dit<T, NT, Nx, LDY, 1, LGNY, LGNTW, G::MAXLG>(W, tw, tid);
-#endif
       // velocity and RK bookkeeping on this thread's pixels (src/numerical_algorithms.jl:15-21); the next stage input goes back as packed columns
       const bool last = step == a.n - 1 && stage == 4;
       const RKCoef<T> rk = sm_coef(a, stage, last);
@@ -327,7 +312,6 @@ __global__ __launch_bounds__((SmallGeom<T, LGNY, LGNX>::NT)) void k_small_adj(Sm
       // y = irfft2(Y): inverse x transform by ky slots, c2r by columns (packed: pixel (x, y) at the real view)
       sm_dit<T, NT, Nyh, 1, LDY, LGNX, LGNTW, G::MAXLG>(W, tw, tid);
       sm_c2r_pre<T, G>(W, tw, tid);
-#ifndef SM_LATE_P
       T px[PPT], py[PPT];
       {
         const T* pc = a.pcache + (size_t)(2 * kt) * ps + pb;
@@ -335,15 +319,6 @@ __global__ __launch_bounds__((SmallGeom<T, LGNY, LGNX>::NT)) void k_small_adj(Sm
         for (int i = 0; i < PPT; ++i) { px[i] = pc[tid + i * NT]; py[i] = pc[ps + tid + i * NT]; SM_FENCE(i); }
       }
       sm_dit<T, NT, Nx, LDY, 1, LGM, LGNTW, G::MAXLG>(W, tw, tid);
-#else
-      sm_dit<T, NT, Nx, LDY, 1, LGM, LGNTW, G::MAXLG>(W, tw, tid);
-      T px[PPT], py[PPT];
-      {
-        const T* pc = a.pcache + (size_t)(2 * kt) * ps + pb;
-#pragma unroll
-        for (int i = 0; i < PPT; ++i) { px[i] = pc[tid + i * NT]; py[i] = pc[ps + tid + i * NT]; SM_FENCE(i); }
-      }
-#endif
       // (p_x y, p_y y) as one complex column per x
       T yv[PPT];
 #pragma unroll

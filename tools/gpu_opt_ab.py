@@ -1,6 +1,6 @@
 """A/B of one context option on one workload, interleaved, with a bit-identity check of the results:
    python tools/gpu_opt_ab.py <option> <v0,v1,..> [N] [pol] [f32|f64] [nrk]      (CMBL_LIB=... for a dev build)
-e.g. python tools/gpu_opt_ab.py col_pipeline 0,1 2048 P f64 10"""
+e.g. python tools/gpu_opt_ab.py col_prefetch 0,-1 2048 P f64 10"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
