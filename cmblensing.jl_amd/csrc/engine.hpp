@@ -174,8 +174,19 @@ struct CtxBase {
 
 // Where and how one any-size launch runs: its stream; its slice window -- slices [sl0, sl0 + sln) of the slall slices of a flow, of each part of
 // its batch when that is a multiple of slall (pair launches); sln < 0: all slices -- and the layout of the hand-off arrays it touches: tile = rows
-// of a block column of tiled [x / 4][ky][x % 4] arrays (Ctx::gen_tile), 0: [ky][x] arrays.
+// of a block column of tiled [x / 4][ky][x % 4] arrays (GenForm::tile), 0: [ky][x] arrays.
 struct GenRun { hipStream_t st; long sl0 = 0, sln = -1, slall = 0; int tile = 0; };
+
+// The form of the RK stages of ONE any-size flow, chosen once per flow by Ctx::gen_form -- the only reader of the options gen_separable, gen_prologue,
+// gen_xderiv_fused, gen_yy, gen_xmerge and gen_tiled, and the only place that asks whether an axis has a compile-time plan for a fused stage.  The
+// flows dispatch on it and size their scratch from it; the launchers take it as given and fail when called without their kernel.
+enum GenKind { GEN_MAP = 1, GEN_ADJ = 2, GEN_DELTA = 4, GEN_PLAIN = 8 };   // map / adjoint / delta flow, the 2-D transforms alone: the bits of option gen_tiled
+struct GenForm {
+  enum Stage { REFERENCE, SEPARATE, PROLOGUE, FUSED } stage = REFERENCE;
+  bool dx_one = false, dx_pair = false;        // the d/dx pass ifft_x(i lx fft_x(.)) is one launch; ... which the ifft_x that opens a delta stage shares (k_ct_dft2)
+  bool row_update = false, row_next = false;   // fused stages: the row update of an adjoint-type stage is one launch (k_ct_adj_x); ... which also opens the next stage
+  int tile = 0; long hpl = 0;                  // layout of the hand-off arrays (GenRun::tile) and their slice stride: mplane() when tiled, else plane()
+};
 
 // The launches of the compile-time-plan kernels (kernels_ct.hpp) of ONE length N: declared here, defined in engine_ct.hpp and instantiated per
 // length by tu_cty_* (column side + the plain transforms) and tu_ctx_* (row side of the fused stages), so that no other translation unit
@@ -366,11 +377,11 @@ struct Ctx : CtxBase {
     }
     return a;
   }
-  // (the mixed scratch between the two launches of a 2-D transform is a hand-off array like those of the flows: tiled under bit 8 of gen_tiled,
-  //  whatever the caller's run says)
+  // (the mixed scratch between the two launches of a 2-D transform is a hand-off array like those of the flows: tiled under bit 8 of gen_tiled
+  //  -- gen_form(GEN_PLAIN) -- whatever the caller's run says)
   void gen_rfft2(GenRun r, const T* map, cx<T>* F, long slices) {
     cx<T>* tmp = mixed_scratch(slices);
-    r.tile = (opts.gen_tiled & 8) ? gen_tile() : 0;
+    r.tile = gen_form(GEN_PLAIN).tile;
     GenDft<T> a = gen_ypass(false);                                         // y: map [x][y] -> tmp [ky][x]
     a.in = map; a.out = tmp; a.scale = 1;
     hand_out<1>(a, r);
@@ -382,7 +393,7 @@ struct Ctx : CtxBase {
   }
   void gen_irfft2(GenRun r, const cx<T>* F, T* map, long slices) {
     cx<T>* tmp = mixed_scratch(slices);
-    r.tile = (opts.gen_tiled & 8) ? gen_tile() : 0;
+    r.tile = gen_form(GEN_PLAIN).tile;
     GenDft<T> b = gen_xpass();                                              // x (inverse): F [ky][kx] -> tmp [ky][x]
     b.in = F; b.out = tmp; b.inverse = 1;
     hand_out<2>(b, r);
@@ -408,65 +419,52 @@ struct Ctx : CtxBase {
     hand_in<1>(a, r);
     gen_dft(r, genY, a, slices);
   }
-  // the y axis has a compile-time plan (and they are switched on): the fused y passes of a flow stage exist
-  bool gen_ct_y() const {
-    if (!opts.gen_ct || genY.plan.nf == 0) return false;
-    switch (Ny) {
-#define CMBL_X(n) case n: return true;
-      CMBL_CT_LIST(CMBL_X)
-#undef CMBL_X
-      default: return false;
-    }
+  GenForm gen_form(GenKind kind) const {
+    const bool sep = opts.gen_separable, pro = opts.gen_prologue, dx = opts.gen_xderiv_fused, yy = opts.gen_yy;
+    // an axis has compile-time-plan kernels (and they are switched on)
+    const bool y_ct = opts.gen_ct && genY.plan.nf > 0 && ct_listed(Ny), x_ct = opts.gen_ct && genX.plan.nf > 0 && ct_listed(Nx);
+    GenForm f;
+    f.dx_one = dx && genX.plan.nf > 0;                                      // (chirp-z transforms have no one-launch d/dx pass)
+    f.dx_pair = f.dx_one && x_ct;
+    f.row_update = x_ct && yy && ct_rowfuse_ok<T>(Nx);
+    f.row_next = f.row_update && opts.gen_xmerge;
+    // fused y passes: the map flow's go with the prologue and the one-launch d/dx pass; the delta flow's also need an x plan and two LDS rows per column (ct_S2: every listed length has them); the adjoint flow's neither
+    const bool fused_map = sep && pro && dx && yy && y_ct;
+    const bool fused = kind == GEN_ADJ ? sep && yy && y_ct : kind == GEN_DELTA ? fused_map && ct_lds<T>(Ny, 2, ct_S2<T>(Ny)) <= 160 * 1024 && genX.plan.nf > 0 : fused_map;
+    f.stage = !sep ? GenForm::REFERENCE : fused ? GenForm::FUSED : pro && kind != GEN_ADJ ? GenForm::PROLOGUE : GenForm::SEPARATE;
+    // Tiled hand-off arrays (GenDft::in_tiled) only where EVERY launch that touches them is a compile-time-plan kernel: the fused y passes, the one-launch
+    // x passes, the row update that opens the next stage; 4 | Nx for the blocks.  (One rule, the map flow's, for all flows: stricter than the adjoint flow needs.)
+    const bool all_ct = fused && fused_map && f.dx_pair && f.row_next;
+    f.tile = (opts.gen_tiled & kind) && all_ct && !(Nx & 3) ? (Nyh + 3) & ~3 : 0;   // rows of a block column: ky padded to a multiple of 4
+    f.hpl = f.tile ? mplane() : plane();
+    return f;
   }
   // pair c2r of (G1, i ly G2) + the stage's velocity / RK update on the maps of `pro` + rfft_y of the next stage input -> Anext, one launch
   // (GenDft::yy, kernels_ct.hpp ct_flow_stage); last: the flow ends, only y0 is updated
   void gen_y_flow_stage(const GenRun& r, const cx<T>* G1, const cx<T>* G2, const T* lmul2, T s1, T s2, const GenPro<T>& pro, cx<T>* Anext, bool last, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
-  // ... and the four y passes of a delta-flow stage (two LDS rows per column: up to Ny ~ 1150)
-  bool gen_ct_y2() const { return gen_ct_y() && ct_lds<T>(Ny, 2, ct_S2<T>(Ny)) <= 160 * 1024; }
   // c2r of T3 = ifft_x(delta f) -> L(df), pair c2r of (G1, i ly G2) -> grad f, the delta stage's pointwise work on the maps of `pro`
   // (w1p, w2p, y0, acc), rfft_y of the next f -> Anext, pair r2c of (p_x, p_y) L(df) -> (W2a, W2b): one launch (k_ct_delta_y)
   void gen_y_delta_stage(const GenRun& r, const cx<T>* T3, T s3, const cx<T>* G1, const cx<T>* G2, const T* lmul2, T s1, T s2, const GenPro<T>& pro, cx<T>* Anext, cx<T>* W2a, cx<T>* W2b, bool last, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
-  // fft_x of the pair (W2a, W2b) and the RK update of the Fourier state (Y0, acc -> Ys) with k = i lx Fx + i ly Fy in ONE launch where the x axis has
-  // a compile-time plan; false: not available (the caller runs the x transform and k_gen_adj_rk)
-  bool gen_x_adj_update(const GenRun& r, const cx<T>* W2a, const cx<T>* W2b, cx<T>* Y0, cx<T>* acc_, cx<T>* Ys, const RKCoef<T>& rk, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
-  // the x axis has a compile-time plan: the row update of an adjoint-type stage can open the next stage in the same launch (gen_x_adj_next)
-  bool gen_ct_x() const {
-    if (!opts.gen_ct || !opts.gen_yy || !opts.gen_xmerge || genX.plan.nf == 0 || !ct_rowfuse_ok<T>(Nx)) return false;
-    switch (Nx) {
-#define CMBL_X(n) case n: return true;
-      CMBL_CT_LIST(CMBL_X)
-#undef CMBL_X
-      default: return false;
-    }
-  }
-  // Tiled hand-off arrays (GenDft::in_tiled): every launch that touches them must be a compile-time-plan kernel, i.e. both axes have a plan and
-  // the fused stages are on; 4 | Nx for the blocks.  Returns the rows of a block column (ky padded to a multiple of 4), 0 = [ky][x] arrays.
-  int gen_tile() const {
-    if (!opts.gen_tiled || !opts.gen_separable || !opts.gen_prologue || !opts.gen_xderiv_fused || (Nx & 3) || !gen_ct_x() || !gen_ct_y()) return 0;
-    return (Nyh + 3) & ~3;
-  }
+  // fft_x of the pair (W2a, W2b) and the RK update of the Fourier state (Y0, acc -> Ys) with k = i lx Fx + i ly Fy in ONE launch (GenForm::row_update)
+  void gen_x_adj_update(const GenRun& r, const cx<T>* W2a, const cx<T>* W2b, cx<T>* Y0, cx<T>* acc_, cx<T>* Ys, const RKCoef<T>& rk, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
   // the input / output of a launch is a hand-off array (gA / gGx / gW2 / the mixed scratch of a flow): tiled when the run says so, slice stride mplane()
   template <int SIDE /*1: y kernel (sequence = x), 2: x kernel (element = x)*/> void hand_in(GenDft<T>& a, const GenRun& r) const { if (r.tile) { a.in_tiled = SIDE; a.tile_np = r.tile; a.in_slice = mplane(); } }
   template <int SIDE> void hand_out(GenDft<T>& a, const GenRun& r) const { if (r.tile) { a.out_tiled = SIDE; a.tile_np = r.tile; a.out_slice = mplane(); } }
   // row groups of an x launch on tiled arrays: a multiple of 8, so that xcd_tile (kernels_fft.hpp) puts the groups that share 128-byte lines on one XCD
   static long xgroups(long groups, bool tiled) { return tiled ? (groups + 7) & ~7L : groups; }
+  // ... and the x passes that open the next stage (GenForm::row_next)
   void gen_x_adj_next(const GenRun& r, const cx<T>* W2a, const cx<T>* W2b, cx<T>* Y0, cx<T>* acc_, const RKCoef<T>& rk, cx<T>* t3, const cx<T>* A_next, cx<T>* gx, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
-  // t3 = ifft_x(F) (unnormalised) and gx = ifft_x(i lx fft_x(A)) in ONE launch where the x axis has a compile-time plan (else two launches)
-  void gen_x_inv_and_deriv(const GenRun& r, const cx<T>* F, cx<T>* t3, const cx<T>* A_, cx<T>* gx, cx<T>* tmp, const T* lx, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
+  // t3 = ifft_x(F) (unnormalised) and gx = ifft_x(i lx fft_x(A)) in ONE launch (fm.dx_pair), else the inverse transform and gen_x_deriv
+  void gen_x_inv_and_deriv(const GenRun& r, const GenForm& fm, const cx<T>* F, cx<T>* t3, const cx<T>* A_, cx<T>* gx, cx<T>* tmp, const T* lx, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
   // c2r of T3 = ifft_x(y) -> y, (p_x y, p_y y) at stage time t, its pair r2c -> (W2a, W2b): the y passes of an adjoint stage in one launch
   void gen_y_adj_stage(const GenRun& r, const cx<T>* T3, T s3, const PhiMaps<T>& phm, T t, int P, cx<T>* W2a, cx<T>* W2b, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
-  // out = ifft_x(i lx fft_x(in)) unnormalised, in ONE launch when the axis has a mixed-radix plan (else two: chirp-z transforms)
-  bool gen_x_deriv(const GenRun& r, const cx<T>* in, cx<T>* out, cx<T>* tmp, const T* lx, long slices) {
-    if (genX.plan.nf == 0 || !opts.gen_xderiv_fused) {
-      gen_x(r, in, tmp, false, lx, slices);
-      gen_x(r, tmp, out, true, nullptr, slices);
-      return false;
-    }
+  // out = ifft_x(i lx fft_x(in)) unnormalised, in one launch (GenForm::dx_one) or as two transforms through tmp
+  void gen_x_deriv(const GenRun& r, bool one, const cx<T>* in, cx<T>* out, cx<T>* tmp, const T* lx, long slices) {
+    if (!one) { gen_x(r, in, tmp, false, lx, slices); return gen_x(r, tmp, out, true, nullptr, slices); }
     GenDft<T> b = gen_xpass();
     b.in = in; b.out = out; b.lmul_mid = lx;
     hand_in<2>(b, r); hand_out<2>(b, r);
     gen_dft(r, genX, b, slices);
-    return true;
   }
   void gen_x(const GenRun& r, const cx<T>* in, cx<T>* out, bool inverse, const T* lmul_out, long slices, bool hand_i = false, bool hand_o = false) {
     GenDft<T> b = gen_xpass();
@@ -1035,7 +1033,7 @@ struct Flow {
 
   // ---- any-size path: the reference's pass structure on k_gen_dft + pointwise kernels (kernels_generic.hpp) ----------------------
   // (x, y) pairs live in the two halves of ONE buffer so that both members go through a transform in one launch
-  DevBuf gF, gFxy, gmxy, gms, gYs, gLdf, gWxy;
+  DevBuf gF, gFxy, gmxy, gms, gYs, gLdf, gWxy, gA, gGx, gT, gW2;
   // (pointwise launches of a stage: over the slice window of the run; the kernels take its first slice r.sl0)
   dim3 pgrid(long n, long slices, const GenRun& r) const { return dim3((unsigned)std::min<long>((n + NTP - 1) / NTP, 4096), (unsigned)(r.sln < 0 ? slices : r.sln)); }
   dim3 fgrid(long slices, const GenRun& r) const { return dim3((unsigned)((c->plane() + NTP - 1) / NTP), (unsigned)(r.sln < 0 ? slices : r.sln)); }
@@ -1053,8 +1051,8 @@ struct Flow {
   // -1.5 %, 640^2 -21 %.  (Round 5's rule -- pixels of ONE slice, x 4 from three slices on -- switched the chains on for T+QU from 131 k pixels.)
   // (One rule for all flows: chains in the delta flows alone -- their launches are longer -- make (grad L)' faster from 200 k pixels per chain, 480^2 QU
   //  -2.4 %, 480 x 640 T+QU -9 %, but the grad lnP around it SLOWER, +3.4 % / +7 %: profiles/r06_ab_anysize_streams_retuned.txt, last block.)
-  int gen_groups(long slices) const {
-    if (!c->opts.gen_slice_streams || !gen_sep()) return 1;
+  int gen_groups(long slices, const GenForm& fm) const {
+    if (!c->opts.gen_slice_streams || fm.stage == GenForm::REFERENCE) return 1;
     for (int k = (int)std::min<long>(std::min(max_groups, c->opts.slice_streams), slices); k > 1; --k) {
       if (slices % k) continue;
       const long per_chain = c->npix() * (slices / k) * (long)(sizeof(T) / 4), need = (long)c->opts.gen_streams_min_pix * (k >= 3 ? 4 : 3) / 3;
@@ -1062,207 +1060,210 @@ struct Flow {
     }
     return 1;
   }
-  // the run of chain g of K over `slices` slices (its stream and slice window) with hand-off layout `tile`; K = 1: all slices on the main stream
-  GenRun gen_run(int g, int K, long slices, int tile) const {
-    if (K <= 1) return GenRun{c->stream, 0, -1, 0, tile};
-    return GenRun{gstream(g), g * (slices / K), slices / K, slices, tile};
+  // The RK stages of a flow: chain g of K runs stage(its run -- stream, slice window, the form's layout; K = 1: all slices on the main stream --, RK coefficients, stage index) for every stage in turn
+  template <typename F> void gen_stages(const GenForm& fm, long slices, double t0, double h, F stage) {
+    const int K = gen_groups(slices, fm);
+    fork(K);
+    for (int it = 0; it < 4 * n; ++it) {
+      const RKCoef<T> rk = coef(it / 4, it % 4 + 1, t0, h, it == 4 * n - 1);
+      for (int g = 0; g < K; ++g) stage(K <= 1 ? GenRun{c->stream, 0, -1, 0, fm.tile} : GenRun{gstream(g), g * (slices / K), slices / K, slices, fm.tile}, rk, it);
+    }
+    join(K);
   }
-  // layout of the hand-off arrays of a flow: tiled when the flow runs its fused stages and Ctx::gen_tile() allows
-  int gen_flow_tile(bool fused, int kind /*option gen_tiled: 1 map flows, 2 adjoint flows, 4 delta flows*/) const {
-    return fused && (c->opts.gen_tiled & kind) ? c->gen_tile() : 0;
+  // Every buffer the chosen form of a flow can touch is sized here BEFORE the chains fork, and by nothing after it: a growth (hipFree / hipMalloc) inside
+  // the multi-stream region would pull a buffer from under a launch of another chain.  gA, gGx, gT, gW2 and the mixed scratch are hand-off arrays.
+  cx<T>* gen_scratch(const GenForm& fm, GenKind kind, long slices) {     // returns the mixed scratch of the flows that use it
+    const long pl = c->plane(), np = c->npix();
+    const bool ref = fm.stage == GenForm::REFERENCE, adj = kind != GEN_MAP, grad = kind != GEN_ADJ;   // adjoint-type stages (Fourier state); stages that take grad f
+    gms.ensure(sizeof(T) * slices * np); if (grad) acc.ensure(sizeof(T) * slices * np);
+    if (adj || fm.stage != GenForm::FUSED) gmxy.ensure(sizeof(T) * 2 * slices * np);
+    if (grad && ref) gF.ensure(sizeof(cx<T>) * slices * pl);
+    if (grad && !ref) { gA.ensure(sizeof(cx<T>) * slices * fm.hpl); gT.ensure(sizeof(cx<T>) * slices * fm.hpl); gGx.ensure(sizeof(cx<T>) * slices * fm.hpl); }
+    if (adj || ref) gFxy.ensure(sizeof(cx<T>) * 2 * slices * pl);
+    if (adj) { Yacc.ensure(sizeof(cx<T>) * slices * pl); gYs.ensure(sizeof(cx<T>) * slices * pl); gW2.ensure(sizeof(cx<T>) * 2 * slices * fm.hpl); }
+    return adj || ref ? c->mixed_scratch(ref ? 2 * slices : slices) : nullptr;   // (the reference form transforms pairs)
   }
-  // (gmx, gmy) = grad of the stage input f_s from its y transform A = rfft_y(f_s) (mixed layout), using the separability the fused
+  // (gmx, gmy) = grad of the stage input f_s from its y transform gA = rfft_y(f_s) (mixed layout), using the separability the fused
   // kernels use: d/dy needs the y transform alone (the i*ly multiply commutes with the x transforms, which then cancel), d/dx one
   // forward / i*lx / inverse x pass; ONE complex inverse y transform returns both real maps (pair c2r).  Equal to the reference's
   // rfft2 -> (i lx, i ly) -> 2 x irfft2 (src/lenseflow.jl:155-157) incl. FFTW's c2r rule at ky = 0 / Nyquist, in 3 launches and
   // 3 slice-passes instead of 5 launches and 7.5.  CMBL_GEN_SEPARABLE=0: the reference's own pass structure (kept for A/B).
-  DevBuf gA, gGx, gT, gW2;
-  bool gen_sep() const { return c->opts.gen_separable != 0; }
-  void gen_grad_sep(const GenRun& r, const cx<T>* A_, long slices) {
-    const long pl = c->plane(), np = c->npix();
-    gT.ensure(sizeof(cx<T>) * slices * pl); gGx.ensure(sizeof(cx<T>) * slices * pl); gmxy.ensure(sizeof(T) * 2 * slices * np);
-    c->gen_x_deriv(r, A_, gGx.as<cx<T>>(), gT.as<cx<T>>(), c->lx_r.template as<T>(), slices);     // Nx * d/dx in mixed space: ifft_x(i lx fft_x(A))
-    c->gen_y_c2r_pair(r, gGx.as<cx<T>>(), A_, c->ly.template as<T>(), gmxy.as<T>(), gmxy.as<T>() + slices * np,
+  void gen_grad_sep(const GenRun& r, const GenForm& fm, long slices) {
+    c->gen_x_deriv(r, fm.dx_one, gA.as<cx<T>>(), gGx.as<cx<T>>(), gT.as<cx<T>>(), c->lx_r.template as<T>(), slices);     // Nx * d/dx in mixed space: ifft_x(i lx fft_x(A))
+    c->gen_y_c2r_pair(r, gGx.as<cx<T>>(), gA.as<cx<T>>(), c->ly.template as<T>(), gmxy.as<T>(), gmxy.as<T>() + slices * c->npix(),
                       (T)(1.0 / ((double)c->Ny * c->Nx)), (T)(1.0 / (double)c->Ny), slices);
   }
-  // (gmx, gmy) = grad of the map `ys`  (rfft2, i l multiplies, irfft2 of both components)
-  void gen_grad(const GenRun& r, const T* ys, long slices) {
-    const long pl = c->plane(), np = c->npix();
-    gF.ensure(sizeof(cx<T>) * slices * pl); gFxy.ensure(sizeof(cx<T>) * 2 * slices * pl); gmxy.ensure(sizeof(T) * 2 * slices * np);
-    c->gen_rfft2(r, ys, gF.as<cx<T>>(), slices);
-    CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_lmul2<T>), fgrid(slices, r), 0, r.st, gF.as<cx<T>>(), gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * pl,
-                c->lx_r.template as<T>(), c->ly.template as<T>(), c->Nx, pl);
+  // (gmx, gmy) = grad of the map gms  (rfft2, i l multiplies, irfft2 of both components)
+  void gen_grad(const GenRun& r, long slices) {
+    c->gen_rfft2(r, gms.as<T>(), gF.as<cx<T>>(), slices);
+    CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_lmul2<T>), fgrid(slices, r), 0, r.st, gF.as<cx<T>>(), gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * c->plane(),
+                c->lx_r.template as<T>(), c->ly.template as<T>(), c->Nx, c->plane());
     c->gen_irfft2(r, gFxy.as<cx<T>>(), gmxy.as<T>(), 2 * slices);
   }
-  // d(Fourier state)/dt from the maps (Wx, Wy) = the halves of Wxy: rfft2 of both + the RK update with k = i lx Fx + i ly Fy
-  // (separable form: the two real maps go through ONE complex y transform, then one x launch over both)
-  bool gen_pro() const { return c->opts.gen_prologue != 0; }
-  void gen_adj_update(const GenRun& r, const T* Wxy, cx<T>* Y0, cx<T>* Yacc_, cx<T>* Ys, const RKCoef<T>& rk, long slices, const GenPro<T>* pro = nullptr) {
-    const long pl = c->plane(), np = c->npix();
-    gFxy.ensure(sizeof(cx<T>) * 2 * slices * pl);
-    if (gen_sep()) {
-      gW2.ensure(sizeof(cx<T>) * 2 * slices * pl);
-      // pro (mode 3): the pair is formed in the fetch from L(df) and p; `in` / `in2` only mark the launch as a real pair
-      if (pro) c->gen_y_r2c(r, pro->Ldf, gW2.as<cx<T>>(), slices, pro->Ldf, gW2.as<cx<T>>() + slices * pl, pro);
-      else c->gen_y_r2c(r, Wxy, gW2.as<cx<T>>(), slices, Wxy + slices * np, gW2.as<cx<T>>() + slices * pl);
-      c->gen_x(r, gW2.as<cx<T>>(), gFxy.as<cx<T>>(), false, nullptr, 2 * slices, true, false);
-    } else c->gen_rfft2(r, Wxy, gFxy.as<cx<T>>(), 2 * slices);
-    CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_adj_rk<T>), fgrid(slices, r), 0, r.st, gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * pl, c->lx_r.template as<T>(),
-                c->ly.template as<T>(), c->Nx, Y0, Yacc_, Ys, rk, pl, (int)r.sl0);
+  // d(Fourier state)/dt: the RK update of (Y0, Yacc -> gYs) with k = i lx Fx + i ly Fy from the pair (Fx, Fy) in gFxy ...
+  void gen_adj_rk(const GenRun& r, cx<T>* Y0, const RKCoef<T>& rk, long slices) {
+    CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_adj_rk<T>), fgrid(slices, r), 0, r.st, gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * c->plane(), c->lx_r.template as<T>(),
+                c->ly.template as<T>(), c->Nx, Y0, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, c->plane(), (int)r.sl0);
   }
+  // ... after the pair r2c of the real maps (Wx, Wy) = the halves of Wxy (ONE complex y transform; Wxy null: gW2 holds it already) and fft_x of the pair gW2
+  void gen_pair_adj_rk(const GenRun& r, const GenForm& fm, const T* Wxy, cx<T>* Y0, const RKCoef<T>& rk, long slices) {
+    if (Wxy) c->gen_y_r2c(r, Wxy, gW2.as<cx<T>>(), slices, Wxy + slices * c->npix(), gW2.as<cx<T>>() + slices * fm.hpl);
+    c->gen_x(r, gW2.as<cx<T>>(), gFxy.as<cx<T>>(), false, nullptr, 2 * slices, true, false);
+    gen_adj_rk(r, Y0, rk, slices);
+  }
+  // the row update that closes a FUSED adjoint-type stage from the pair gW2, in the most fused shape the form has (t3 / A_next / gx: gen_x_adj_next)
+  void gen_row_update(const GenRun& r, const GenForm& fm, cx<T>* Y0, const RKCoef<T>& rk, cx<T>* t3, const cx<T>* A_next, cx<T>* gx, long slices) {
+    cx<T>* W2a = gW2.as<cx<T>>(), *W2b = W2a + slices * fm.hpl;
+    if (fm.row_next && !rk.last) c->gen_x_adj_next(r, W2a, W2b, Y0, Yacc.as<cx<T>>(), rk, t3, A_next, gx, slices);
+    else if (fm.row_update) c->gen_x_adj_update(r, W2a, W2b, Y0, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices);
+    else gen_pair_adj_rk(r, fm, nullptr, Y0, rk, slices);
+  }
+  // the pointwise state of a map (mode 1) or delta (2; w1p: its products for delta-phi) stage that rides in a transform launch
+  GenPro<T> gen_pro(int mode, const RKCoef<T>& rk, T* y0, int P, T* w1p, long slices) {
+    GenPro<T> e{};
+    e.mode = mode; e.ph = ph(rk.t); e.rk = rk; e.y0 = y0; e.acc = acc.as<T>(); e.npix = c->npix(); e.P = P;
+    if (w1p) { e.w1p = w1p; e.w2p = w1p + (size_t)slices * c->npix(); }
+    return e;
+  }
+  // ---- map flow, one member per stage form.  Fused: d/dx pass, then every y pass of the stage in one launch
+  void gen_map_fused(const GenRun& r, const GenForm& fm, const RKCoef<T>& rk, T* out, int P, long slices) {
+    c->gen_x_deriv(r, fm.dx_one, gA.as<cx<T>>(), gGx.as<cx<T>>(), gT.as<cx<T>>(), c->lx_r.template as<T>(), slices);
+    c->gen_y_flow_stage(r, gGx.as<cx<T>>(), gA.as<cx<T>>(), c->ly.template as<T>(), (T)(1.0 / ((double)c->Ny * c->Nx)), (T)(1.0 / (double)c->Ny),
+                        gen_pro(1, rk, out, P, nullptr, slices), gA.as<cx<T>>(), rk.last != 0, slices);
+  }
+  void gen_map_point(const GenRun& r, const RKCoef<T>& rk, T* out, int P, long slices) {   // velocity + RK bookkeeping: gmxy, y0, acc -> gms
+    CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_vel_rk<T>), pgrid(c->npix(), slices, r), 0, r.st, gmxy.as<T>(), gmxy.as<T>() + slices * c->npix(), ph(rk.t), out, acc.as<T>(),
+                gms.as<T>(), rk, c->npix(), P, (int)r.sl0);
+  }
+  void gen_map_separate(const GenRun& r, const GenForm& fm, const RKCoef<T>& rk, T* out, int P, long slices) {
+    gen_grad_sep(r, fm, slices);
+    gen_map_point(r, rk, out, P, slices);
+    if (!rk.last) c->gen_y_r2c(r, gms.as<T>(), gA.as<cx<T>>(), slices);
+  }
+  // velocity + RK bookkeeping in the fetch of the next stage's y transform; the last stage has none and runs the separate form
+  void gen_map_prologue(const GenRun& r, const GenForm& fm, const RKCoef<T>& rk, T* out, int P, long slices) {
+    if (rk.last) return gen_map_separate(r, fm, rk, out, P, slices);
+    gen_grad_sep(r, fm, slices);
+    GenPro<T> e = gen_pro(1, rk, out, P, nullptr, slices);
+    e.gx = gmxy.as<T>(); e.gy = gmxy.as<T>() + slices * c->npix();
+    c->gen_y_r2c(r, gms.as<T>(), gA.as<cx<T>>(), slices, nullptr, nullptr, &e);
+  }
+  void gen_map_reference(const GenRun& r, const RKCoef<T>& rk, T* out, int P, long slices) { gen_grad(r, slices); gen_map_point(r, rk, out, P, slices); }
   void gen_flow_map(const T* in, T* out, int P, int B, bool inverse) {
     const long slices = (long)P * B, np = c->npix();
-    acc.ensure(sizeof(T) * slices * np); gms.ensure(sizeof(T) * slices * np);
+    const GenForm fm = c->gen_form(GEN_MAP);
+    gen_scratch(fm, GEN_MAP, slices);
     if (in != out) CMBL_HIP(hipMemcpyAsync(out, in, sizeof(T) * slices * np, hipMemcpyDeviceToDevice, c->stream));
     CMBL_HIP(hipMemcpyAsync(gms.p, out, sizeof(T) * slices * np, hipMemcpyDeviceToDevice, c->stream));
     const double t0 = inverse ? 1.0 : 0.0, h = (inverse ? -1.0 : 1.0) / n;
-    const bool sep = gen_sep();
-    const bool yy = sep && gen_pro() && c->opts.gen_yy && c->opts.gen_xderiv_fused && c->gen_ct_y();
-    const int tile = gen_flow_tile(yy, 1);
-    const long pl = tile ? c->mplane() : c->plane();
-    if (sep) { gA.ensure(sizeof(cx<T>) * slices * pl); c->gen_y_r2c(gen_run(0, 1, slices, tile), gms.as<T>(), gA.as<cx<T>>(), slices); }
-    const int K = gen_groups(slices);
-    // every scratch buffer a stage can grow is sized BEFORE the chains fork: a growth (hipFree / hipMalloc) inside the multi-stream region
-    // would pull a buffer from under a launch of another chain (the separate-launch path used to ensure inside gen_grad_sep / gen_grad)
-    if (sep) { gT.ensure(sizeof(cx<T>) * slices * pl); gGx.ensure(sizeof(cx<T>) * slices * pl); if (!yy) gmxy.ensure(sizeof(T) * 2 * slices * np); }
-    else { gF.ensure(sizeof(cx<T>) * slices * pl); gFxy.ensure(sizeof(cx<T>) * 2 * slices * pl); gmxy.ensure(sizeof(T) * 2 * slices * np); c->mixed_scratch(2 * slices); }
-    fork(K);
-    for (int step = 0; step < n; ++step)
-      for (int stage = 1; stage <= 4; ++stage) {
-        const bool last = step == n - 1 && stage == 4;
-        const RKCoef<T> rk = coef(step, stage, t0, h, last);
-        for (int g = 0; g < K; ++g) {
-          const GenRun r = gen_run(g, K, slices, tile);
-          if (yy) {                                                          // d/dx pass, then every y pass of the stage in one launch
-            GenPro<T> e{};
-            e.mode = 1; e.ph = ph(rk.t); e.rk = rk; e.y0 = out; e.acc = acc.as<T>(); e.npix = np; e.P = P;
-            c->gen_x_deriv(r, gA.as<cx<T>>(), gGx.as<cx<T>>(), gT.as<cx<T>>(), c->lx_r.template as<T>(), slices);
-            c->gen_y_flow_stage(r, gGx.as<cx<T>>(), gA.as<cx<T>>(), c->ly.template as<T>(), (T)(1.0 / ((double)c->Ny * c->Nx)), (T)(1.0 / (double)c->Ny), e,
-                                gA.as<cx<T>>(), last, slices);
-            continue;
-          }
-          if (sep) gen_grad_sep(r, gA.as<cx<T>>(), slices); else gen_grad(r, gms.as<T>(), slices);
-          if (sep && !last && gen_pro()) {                                   // velocity + RK bookkeeping in the fetch of the next stage's y transform
-            GenPro<T> e{};
-            e.mode = 1; e.ph = ph(rk.t); e.rk = rk; e.gx = gmxy.as<T>(); e.gy = gmxy.as<T>() + slices * np; e.y0 = out; e.acc = acc.as<T>(); e.npix = np; e.P = P;
-            c->gen_y_r2c(r, gms.as<T>(), gA.as<cx<T>>(), slices, nullptr, nullptr, &e);
-            continue;
-          }
-          CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_vel_rk<T>), pgrid(np, slices, r), 0, r.st, gmxy.as<T>(), gmxy.as<T>() + slices * np, ph(rk.t), out, acc.as<T>(),
-                      gms.as<T>(), rk, np, P, (int)r.sl0);
-          if (sep && !last) c->gen_y_r2c(r, gms.as<T>(), gA.as<cx<T>>(), slices);
-        }
+    if (fm.stage != GenForm::REFERENCE) c->gen_y_r2c(GenRun{c->stream, 0, -1, 0, fm.tile}, gms.as<T>(), gA.as<cx<T>>(), slices);
+    gen_stages(fm, slices, t0, h, [&](const GenRun& r, const RKCoef<T>& rk, int) {
+      switch (fm.stage) {
+        case GenForm::FUSED: return gen_map_fused(r, fm, rk, out, P, slices);
+        case GenForm::PROLOGUE: return gen_map_prologue(r, fm, rk, out, P, slices);
+        case GenForm::SEPARATE: return gen_map_separate(r, fm, rk, out, P, slices);
+        case GenForm::REFERENCE: return gen_map_reference(r, rk, out, P, slices);
       }
-    join(K);
+    });
+  }
+  // ---- adjoint flow (no prologue form).  Fused: ifft_x (unless the previous row update ran it), every y pass of the stage in one launch, fft_x of the pair + RK update
+  void gen_adj_fused(const GenRun& r, const GenForm& fm, const RKCoef<T>& rk, cx<T>* out, int P, bool first, cx<T>* t3, long slices) {
+    if (!fm.row_next || first) c->gen_x(r, gYs.as<cx<T>>(), t3, true, nullptr, slices, false, true);
+    c->gen_y_adj_stage(r, t3, (T)(1.0 / ((double)c->Ny * c->Nx)), ph(rk.t), rk.t, P, gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * fm.hpl, slices);
+    gen_row_update(r, fm, out, rk, t3, nullptr, nullptr, slices);
+  }
+  void gen_adj_point(const GenRun& r, const RKCoef<T>& rk, int P, long slices) {          // y = irfft2(gYs) -> gms, (p_x y, p_y y) -> gmxy
+    c->gen_irfft2(r, gYs.as<cx<T>>(), gms.as<T>(), slices);
+    CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_pmul<T>), pgrid(c->npix(), slices, r), 0, r.st, gms.as<T>(), ph(rk.t), rk.t, gmxy.as<T>(), gmxy.as<T>() + slices * c->npix(), c->npix(), P, (int)r.sl0);
+  }
+  void gen_adj_separate(const GenRun& r, const GenForm& fm, const RKCoef<T>& rk, cx<T>* out, int P, long slices) { gen_adj_point(r, rk, P, slices); gen_pair_adj_rk(r, fm, gmxy.as<T>(), out, rk, slices); }
+  void gen_adj_reference(const GenRun& r, const RKCoef<T>& rk, cx<T>* out, int P, long slices) {
+    gen_adj_point(r, rk, P, slices);
+    c->gen_rfft2(r, gmxy.as<T>(), gFxy.as<cx<T>>(), 2 * slices);
+    gen_adj_rk(r, out, rk, slices);
   }
   void gen_flow_adj_F(const cx<T>* in, cx<T>* out, int P, int B, bool inverse) {
-    const long slices = (long)P * B, pl = c->plane(), np = c->npix();
-    Yacc.ensure(sizeof(cx<T>) * slices * pl); gYs.ensure(sizeof(cx<T>) * slices * pl);
-    gms.ensure(sizeof(T) * slices * np); gmxy.ensure(sizeof(T) * 2 * slices * np);
+    const long slices = (long)P * B, pl = c->plane();
+    const GenForm fm = c->gen_form(GEN_ADJ);
+    cx<T>* t3 = gen_scratch(fm, GEN_ADJ, slices);
     if (in != out) CMBL_HIP(hipMemcpyAsync(out, in, sizeof(cx<T>) * slices * pl, hipMemcpyDeviceToDevice, c->stream));
     CMBL_HIP(hipMemcpyAsync(gYs.p, out, sizeof(cx<T>) * slices * pl, hipMemcpyDeviceToDevice, c->stream));
     const double t0 = inverse ? 0.0 : 1.0, h = (inverse ? 1.0 : -1.0) / n;
-    const bool yy = gen_sep() && c->opts.gen_yy && c->gen_ct_y();
-    const int tile = gen_flow_tile(yy, 2);
-    const long hpl = tile ? c->mplane() : c->plane();                                          // (the pair W2 and the mixed scratch t3 are hand-off arrays; the Fourier state is not)
-    gFxy.ensure(sizeof(cx<T>) * 2 * slices * pl); gW2.ensure(sizeof(cx<T>) * 2 * slices * hpl); (void)c->mixed_scratch(slices);   // before the chains fork
-    const int K = gen_groups(slices);
-    fork(K);
-    for (int step = 0; step < n; ++step)
-      for (int stage = 1; stage <= 4; ++stage) {
-        const RKCoef<T> rk = coef(step, stage, t0, h, step == n - 1 && stage == 4);
-        for (int g = 0; g < K; ++g) {
-          const GenRun r = gen_run(g, K, slices, tile);
-          if (yy) {                                                          // ifft_x, every y pass of the stage in one launch, fft_x of the pair, RK update
-            cx<T>* t3 = c->mixed_scratch(slices);
-            const bool mrg = c->gen_ct_x();                                  // the row update of stage s also writes t3 = ifft_x(Ys) of stage s + 1
-            if (!mrg || (step == 0 && stage == 1)) c->gen_x(r, gYs.as<cx<T>>(), t3, true, nullptr, slices, false, true);
-            c->gen_y_adj_stage(r, t3, (T)(1.0 / ((double)c->Ny * c->Nx)), ph(rk.t), rk.t, P, gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, slices);
-            if (mrg && !rk.last) { c->gen_x_adj_next(r, gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, out, Yacc.as<cx<T>>(), rk, t3, nullptr, nullptr, slices); continue; }
-            if (c->gen_x_adj_update(r, gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, out, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices)) continue;
-            c->gen_x(r, gW2.as<cx<T>>(), gFxy.as<cx<T>>(), false, nullptr, 2 * slices, true, false);
-            CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_adj_rk<T>), fgrid(slices, r), 0, r.st, gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * pl, c->lx_r.template as<T>(),
-                        c->ly.template as<T>(), c->Nx, out, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, pl, (int)r.sl0);
-            continue;
-          }
-          c->gen_irfft2(r, gYs.as<cx<T>>(), gms.as<T>(), slices);
-          CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_pmul<T>), pgrid(np, slices, r), 0, r.st, gms.as<T>(), ph(rk.t), rk.t, gmxy.as<T>(), gmxy.as<T>() + slices * np, np, P, (int)r.sl0);
-          gen_adj_update(r, gmxy.as<T>(), out, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices);
-        }
+    gen_stages(fm, slices, t0, h, [&](const GenRun& r, const RKCoef<T>& rk, int it) {
+      switch (fm.stage) {
+        case GenForm::FUSED: return gen_adj_fused(r, fm, rk, out, P, it == 0, t3, slices);
+        case GenForm::REFERENCE: return gen_adj_reference(r, rk, out, P, slices);
+        case GenForm::SEPARATE: return gen_adj_separate(r, fm, rk, out, P, slices);
+        case GenForm::PROLOGUE: fail(ERR_STATE, "the adjoint flow has no prologue form");
       }
-    join(K);
+    });
+  }
+  // ---- delta flow: the state of one stage (f, its products w1p / w2p for delta-phi, delta f)
+  struct GenDelta { RKCoef<T> rk; T* f; cx<T>* df; T* w1p; int P; bool first; cx<T>* t3; };
+  // x passes (ifft_x of delta f, d/dx of rfft_y(f); unless the previous row update ran them), then every y pass of the stage in one launch, then
+  // the delta-f velocity's x pass + RK update
+  void gen_delta_fused(const GenRun& r, const GenForm& fm, const GenDelta& d, long slices) {
+    if (!fm.row_next || d.first) c->gen_x_inv_and_deriv(r, fm, gYs.as<cx<T>>(), d.t3, gA.as<cx<T>>(), gGx.as<cx<T>>(), gT.as<cx<T>>(), c->lx_r.template as<T>(), slices);
+    c->gen_y_delta_stage(r, d.t3, (T)(1.0 / ((double)c->Ny * c->Nx)), gGx.as<cx<T>>(), gA.as<cx<T>>(), c->ly.template as<T>(),
+                         (T)(1.0 / ((double)c->Ny * c->Nx)), (T)(1.0 / (double)c->Ny), gen_pro(2, d.rk, d.f, d.P, d.w1p, slices), gA.as<cx<T>>(), gW2.as<cx<T>>(),
+                         gW2.as<cx<T>>() + slices * fm.hpl, d.rk.last != 0, slices);
+    gen_row_update(r, fm, d.df, d.rk, d.t3, gA.as<cx<T>>(), gGx.as<cx<T>>(), slices);
+  }
+  void gen_delta_point(const GenRun& r, const GenDelta& d, long slices) {                 // the stage's pointwise work: -> (Wx, Wy) in gWxy, products, f_{s+1} in gms
+    CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_delta<T>), pgrid(c->npix(), slices, r), 0, r.st, gLdf.as<T>(), gmxy.as<T>(), gmxy.as<T>() + slices * c->npix(), ph(d.rk.t),
+                gWxy.as<T>(), gWxy.as<T>() + slices * c->npix(), d.w1p, d.w1p + (size_t)slices * c->npix(), d.f, acc.as<T>(), gms.as<T>(), d.rk, c->npix(), d.P, (int)r.sl0);
+  }
+  void gen_delta_separate(const GenRun& r, const GenForm& fm, const GenDelta& d, long slices) {
+    c->gen_irfft2(r, gYs.as<cx<T>>(), gLdf.as<T>(), slices);               // L(df)
+    gen_grad_sep(r, fm, slices);                                            // grad f -> gmxy
+    gen_delta_point(r, d, slices);
+    if (!d.rk.last) c->gen_y_r2c(r, gms.as<T>(), gA.as<cx<T>>(), slices);
+    gen_pair_adj_rk(r, fm, gWxy.as<T>(), d.df, d.rk, slices);
+  }
+  // the stage's pointwise work rides in the fetches of the two y transforms that consume it: f part + products -> rfft_y(f_{s+1});
+  // (p_x L(df), p_y L(df)) -> the pair r2c of the delta-f velocity.  The last stage has no next f and runs the separate form.
+  void gen_delta_prologue(const GenRun& r, const GenForm& fm, const GenDelta& d, long slices) {
+    if (d.rk.last) return gen_delta_separate(r, fm, d, slices);
+    c->gen_irfft2(r, gYs.as<cx<T>>(), gLdf.as<T>(), slices);
+    gen_grad_sep(r, fm, slices);
+    GenPro<T> e = gen_pro(2, d.rk, d.f, d.P, d.w1p, slices);
+    e.gx = gmxy.as<T>(); e.gy = gmxy.as<T>() + slices * c->npix(); e.Ldf = gLdf.as<T>();
+    c->gen_y_r2c(r, gms.as<T>(), gA.as<cx<T>>(), slices, nullptr, nullptr, &e);
+    e.mode = 3;                                                             // the pair is formed in the fetch from L(df) and p; `in` / `in2` only mark the launch as a real pair
+    c->gen_y_r2c(r, e.Ldf, gW2.as<cx<T>>(), slices, e.Ldf, gW2.as<cx<T>>() + slices * fm.hpl, &e);
+    gen_pair_adj_rk(r, fm, nullptr, d.df, d.rk, slices);
+  }
+  void gen_delta_reference(const GenRun& r, const GenDelta& d, long slices) {
+    c->gen_irfft2(r, gYs.as<cx<T>>(), gLdf.as<T>(), slices);
+    gen_grad(r, slices);
+    gen_delta_point(r, d, slices);
+    c->gen_rfft2(r, gWxy.as<T>(), gFxy.as<cx<T>>(), 2 * slices);
+    gen_adj_rk(r, d.df, d.rk, slices);
   }
   void gen_flow_delta(T* f, cx<T>* df, cx<T>* dphi, int P, int B, bool forward_primal, bool alias_quirk) {
     const long slices = (long)P * B, pl = c->plane(), np = c->npix();
     const int nst = 4 * n;
-    acc.ensure(sizeof(T) * slices * np); gms.ensure(sizeof(T) * slices * np); gLdf.ensure(sizeof(T) * slices * np);
-    gWxy.ensure(sizeof(T) * 2 * slices * np);
-    Yacc.ensure(sizeof(cx<T>) * slices * pl); gYs.ensure(sizeof(cx<T>) * slices * pl);
+    const GenForm fm = c->gen_form(GEN_DELTA);
+    gLdf.ensure(sizeof(T) * slices * np); gWxy.ensure(sizeof(T) * 2 * slices * np);
     Wst.ensure(sizeof(T) * (size_t)nst * 2 * slices * np);
     U5.ensure(sizeof(T) * 5 * B * np); F5.ensure(sizeof(cx<T>) * 5 * B * pl); tcbuf.ensure(sizeof(T) * 2 * nst);
+    cx<T>* t3 = gen_scratch(fm, GEN_DELTA, slices);
     CMBL_HIP(hipMemcpyAsync(gms.p, f, sizeof(T) * slices * np, hipMemcpyDeviceToDevice, c->stream));
     CMBL_HIP(hipMemcpyAsync(gYs.p, df, sizeof(cx<T>) * slices * pl, hipMemcpyDeviceToDevice, c->stream));
     const double t0 = forward_primal ? 1.0 : 0.0, h = (forward_primal ? -1.0 : 1.0) / n;
-    const bool sep = gen_sep();
-    const bool yy = sep && gen_pro() && c->opts.gen_yy && c->opts.gen_xderiv_fused && c->gen_ct_y2() && c->genX.plan.nf > 0;
-    const int tile = gen_flow_tile(yy, 4);
-    const long hpl = tile ? c->mplane() : c->plane();                                          // (A, Gx, the pair W2 and the mixed scratch t3 are hand-off arrays; the Fourier state is not)
-    if (sep) { gA.ensure(sizeof(cx<T>) * slices * hpl); c->gen_y_r2c(gen_run(0, 1, slices, tile), gms.as<T>(), gA.as<cx<T>>(), slices); }
+    if (fm.stage != GenForm::REFERENCE) c->gen_y_r2c(GenRun{c->stream, 0, -1, 0, fm.tile}, gms.as<T>(), gA.as<cx<T>>(), slices);
     tc_host.resize(2 * (size_t)nst);
-    gT.ensure(sizeof(cx<T>) * slices * hpl); gGx.ensure(sizeof(cx<T>) * slices * hpl); gmxy.ensure(sizeof(T) * 2 * slices * np);   // before the chains fork
-    gFxy.ensure(sizeof(cx<T>) * 2 * slices * pl); gW2.ensure(sizeof(cx<T>) * 2 * slices * hpl); (void)c->mixed_scratch(slices);
-    const int K = gen_groups(slices);
-    fork(K);
-    int it = 0;
-    for (int step = 0; step < n; ++step)
-      for (int stage = 1; stage <= 4; ++stage, ++it) {
-        const RKCoef<T> rk = coef(step, stage, t0, h, step == n - 1 && stage == 4);
-        tc_host[2 * it] = rk.t;
-        tc_host[2 * it + 1] = (T)((stage == 1 || stage == 4 ? 1.0 : 2.0) * h / 6);
-        T* w1p = Wst.as<T>() + (size_t)(2 * it) * slices * np;
-        for (int g = 0; g < K; ++g) {
-          const GenRun r = gen_run(g, K, slices, tile);
-          if (yy) {
-            // x passes (ifft_x of delta f, d/dx of rfft_y(f)), then every y pass of the stage in one launch, then the delta-f velocity's x pass + RK update
-            cx<T>* t3 = c->mixed_scratch(slices);
-            const bool mrg = c->gen_ct_x();                                  // the row update of stage s also runs both x passes that open stage s + 1
-            if (!mrg || it == 0) c->gen_x_inv_and_deriv(r, gYs.as<cx<T>>(), t3, gA.as<cx<T>>(), gGx.as<cx<T>>(), gT.as<cx<T>>(), c->lx_r.template as<T>(), slices);
-            GenPro<T> e{};
-            e.mode = 2; e.ph = ph(rk.t); e.rk = rk; e.y0 = f; e.acc = acc.as<T>(); e.w1p = w1p; e.w2p = w1p + (size_t)slices * np; e.npix = np; e.P = P;
-            c->gen_y_delta_stage(r, t3, (T)(1.0 / ((double)c->Ny * c->Nx)), gGx.as<cx<T>>(), gA.as<cx<T>>(), c->ly.template as<T>(),
-                                 (T)(1.0 / ((double)c->Ny * c->Nx)), (T)(1.0 / (double)c->Ny), e, gA.as<cx<T>>(), gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl,
-                                 rk.last != 0, slices);
-            if (mrg && !rk.last) {
-              c->gen_x_adj_next(r, gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, df, Yacc.as<cx<T>>(), rk, t3, gA.as<cx<T>>(), gGx.as<cx<T>>(), slices);
-              continue;
-            }
-            if (c->gen_x_adj_update(r, gW2.as<cx<T>>(), gW2.as<cx<T>>() + slices * hpl, df, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices)) continue;
-            c->gen_x(r, gW2.as<cx<T>>(), gFxy.as<cx<T>>(), false, nullptr, 2 * slices, true, false);
-            CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_adj_rk<T>), fgrid(slices, r), 0, r.st, gFxy.as<cx<T>>(), gFxy.as<cx<T>>() + slices * pl, c->lx_r.template as<T>(),
-                        c->ly.template as<T>(), c->Nx, df, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, pl, (int)r.sl0);
-            continue;
-          }
-          c->gen_irfft2(r, gYs.as<cx<T>>(), gLdf.as<T>(), slices);           // L(df)
-          if (sep) gen_grad_sep(r, gA.as<cx<T>>(), slices); else gen_grad(r, gms.as<T>(), slices);   // grad f -> gmxy
-          if (sep && !rk.last && gen_pro()) {
-            // the stage's pointwise work rides in the fetches of the two y transforms that consume it: f part + products -> rfft_y(f_{s+1});
-            // (p_x L(df), p_y L(df)) -> the pair r2c of the delta-f velocity
-            GenPro<T> e{};
-            e.ph = ph(rk.t); e.rk = rk; e.gx = gmxy.as<T>(); e.gy = gmxy.as<T>() + slices * np; e.Ldf = gLdf.as<T>(); e.y0 = f; e.acc = acc.as<T>();
-            e.w1p = w1p; e.w2p = w1p + (size_t)slices * np; e.npix = np; e.P = P;
-            e.mode = 2;
-            c->gen_y_r2c(r, gms.as<T>(), gA.as<cx<T>>(), slices, nullptr, nullptr, &e);
-            e.mode = 3;
-            gen_adj_update(r, nullptr, df, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices, &e);
-            continue;
-          }
-          CMBL_LAUNCH(c, K_GEN_POINT, (k_gen_delta<T>), pgrid(np, slices, r), 0, r.st, gLdf.as<T>(), gmxy.as<T>(), gmxy.as<T>() + slices * np, ph(rk.t),
-                      gWxy.as<T>(), gWxy.as<T>() + slices * np, w1p, w1p + (size_t)slices * np, f, acc.as<T>(), gms.as<T>(), rk, np, P, (int)r.sl0);
-          if (sep && !rk.last) c->gen_y_r2c(r, gms.as<T>(), gA.as<cx<T>>(), slices);
-          gen_adj_update(r, gWxy.as<T>(), df, Yacc.as<cx<T>>(), gYs.as<cx<T>>(), rk, slices);
-        }
+    gen_stages(fm, slices, t0, h, [&](const GenRun& r, const RKCoef<T>& rk, int it) {
+      tc_host[2 * it] = rk.t;                                                // (time and quadrature weight of the stage, for dphi_finish; every chain writes the same)
+      tc_host[2 * it + 1] = (T)((it % 4 == 0 || it % 4 == 3 ? 1.0 : 2.0) * h / 6);
+      const GenDelta d{rk, f, df, Wst.as<T>() + (size_t)(2 * it) * slices * np, P, it == 0, t3};
+      switch (fm.stage) {
+        case GenForm::FUSED: return gen_delta_fused(r, fm, d, slices);
+        case GenForm::PROLOGUE: return gen_delta_prologue(r, fm, d, slices);
+        case GenForm::SEPARATE: return gen_delta_separate(r, fm, d, slices);
+        case GenForm::REFERENCE: return gen_delta_reference(r, d, slices);
       }
-    join(K);
+    });
     dphi_finish(dphi, P, B, nst, alias_quirk);
   }
   // delta-phi: quadrature over the stored stages, five real transforms, the l-multipliers (shared by both paths)

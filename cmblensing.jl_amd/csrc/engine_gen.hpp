@@ -109,8 +109,8 @@ void Ctx<T>::gen_y_delta_stage(const GenRun& r, const cx<T>* T3, T s3, const cx<
 }
 
 template <typename T>
-bool Ctx<T>::gen_x_adj_update(const GenRun& r, const cx<T>* W2a, const cx<T>* W2b, cx<T>* Y0, cx<T>* acc_, cx<T>* Ys, const RKCoef<T>& rk, long slices) {
-  if (!opts.gen_ct || !opts.gen_yy || genX.plan.nf == 0 || !ct_rowfuse_ok<T>(Nx)) return false;
+void Ctx<T>::gen_x_adj_update(const GenRun& r, const cx<T>* W2a, const cx<T>* W2b, cx<T>* Y0, cx<T>* acc_, cx<T>* Ys, const RKCoef<T>& rk, long slices) {
+  CMBL_REQUIRE(ct_rowfuse_ok<T>(Nx), ERR_STATE, "no fused row update for this Nx in this precision");
   GenDft<T> a = gen_xpass();
   a.in = W2a; a.in2 = W2b;
   a.pro.rk = rk; a.yy_out = Y0; a.out2 = acc_; a.out = Ys; a.lmul_out = lx_r.template as<T>(); a.lmul_in = ly.template as<T>();
@@ -122,17 +122,17 @@ bool Ctx<T>::gen_x_adj_update(const GenRun& r, const cx<T>* W2a, const cx<T>* W2
   const int R = Sx / 2;
   const dim3 grid((unsigned)xgroups((a.nseq + R - 1) / R, a.in_tiled != 0), (unsigned)slices);
   switch (Nx) {
-#define CMBL_X(n) case n: CtLaunchX<T, n>::adj_x(this, r, a, grid, Sx); return true;
+#define CMBL_X(n) case n: CtLaunchX<T, n>::adj_x(this, r, a, grid, Sx); return;
     CMBL_CT_LIST(CMBL_X)
 #undef CMBL_X
-    default: return false;
+    default: fail(ERR_STATE, "the fused row update needs a compile-time plan for Nx");
   }
 }
 
 // gen_x_adj_update that ALSO opens the next stage (round 6): the row workgroups that hold the new stage input Ys transform it back, t3 = ifft_x(Ys)
 // (no Ys round trip through memory, one launch less per stage), and -- delta flow: A_next given -- the d/dx pass gx = ifft_x(i lx fft_x(A_next)) of
 // the next stage's f rides in the same launch as further workgroups (k_ct_adj_x_dx).  Replaces gen_x_adj_update(s) + gen_x_inv_and_deriv(s + 1)
-// / gen_x(s + 1); needs a compile-time plan for Nx (gen_ct_x()).  Results bit-identical to the separate launches.
+// / gen_x(s + 1); needs a compile-time plan for Nx (GenForm::row_next).  Results bit-identical to the separate launches.
 template <typename T>
 void Ctx<T>::gen_x_adj_next(const GenRun& r, const cx<T>* W2a, const cx<T>* W2b, cx<T>* Y0, cx<T>* acc_, const RKCoef<T>& rk, cx<T>* t3, const cx<T>* A_next, cx<T>* gx, long slices) {
   GenDft<T> a = gen_xpass();
@@ -161,9 +161,8 @@ void Ctx<T>::gen_x_adj_next(const GenRun& r, const cx<T>* W2a, const cx<T>* W2b,
 }
 
 template <typename T>
-void Ctx<T>::gen_x_inv_and_deriv(const GenRun& r, const cx<T>* F, cx<T>* t3, const cx<T>* A_, cx<T>* gx, cx<T>* tmp, const T* lx, long slices) {
-  bool ct = opts.gen_ct && opts.gen_xderiv_fused && genX.plan.nf > 0;
-  if (ct) {
+void Ctx<T>::gen_x_inv_and_deriv(const GenRun& r, const GenForm& fm, const cx<T>* F, cx<T>* t3, const cx<T>* A_, cx<T>* gx, cx<T>* tmp, const T* lx, long slices) {
+  if (fm.dx_pair) {
     GenDft<T> a0 = gen_xpass();
     a0.in = F; a0.out = t3; a0.inverse = 1;
     GenDft<T> a1 = a0; a1.in = A_; a1.out = gx; a1.inverse = 0; a1.lmul_mid = lx;
@@ -178,11 +177,11 @@ void Ctx<T>::gen_x_inv_and_deriv(const GenRun& r, const cx<T>* F, cx<T>* t3, con
 #define CMBL_X(n) case n: CtLaunchX<T, n>::dft2(this, r, a0, ct_kind(a0), grid, Sx, (int)ws, a1, ct_kind(a1)); return;
       CMBL_CT_LIST(CMBL_X)
 #undef CMBL_X
-      default: break;
+      default: fail(ERR_STATE, "paired x passes need a compile-time plan for Nx");
     }
   }
   gen_x(r, F, t3, true, nullptr, slices, false, true);
-  gen_x_deriv(r, A_, gx, tmp, lx, slices);
+  gen_x_deriv(r, fm.dx_one, A_, gx, tmp, lx, slices);
 }
 
 template <typename T>
@@ -211,8 +210,8 @@ void Ctx<T>::gen_y_adj_stage(const GenRun& r, const cx<T>* T3, T s3, const PhiMa
   template void Ctx<T>::gen_y_adj_stage(const GenRun& r, const cx<T>* T3, T s3, const PhiMaps<T>& phm, T t, int P, cx<T>* W2a, cx<T>* W2b, long slices);
 // (the x-side launches: instantiated by the same units since the kernels moved behind CtLaunchX, engine_ct.hpp)
 #define CMBL_INSTANTIATE_GENX(T) \
-  template bool Ctx<T>::gen_x_adj_update(const GenRun& r, const cx<T>* W2a, const cx<T>* W2b, cx<T>* Y0, cx<T>* acc_, cx<T>* Ys, const RKCoef<T>& rk, long slices); \
+  template void Ctx<T>::gen_x_adj_update(const GenRun& r, const cx<T>* W2a, const cx<T>* W2b, cx<T>* Y0, cx<T>* acc_, cx<T>* Ys, const RKCoef<T>& rk, long slices); \
   template void Ctx<T>::gen_x_adj_next(const GenRun& r, const cx<T>* W2a, const cx<T>* W2b, cx<T>* Y0, cx<T>* acc_, const RKCoef<T>& rk, cx<T>* t3, const cx<T>* A_next, cx<T>* gx, long slices); \
-  template void Ctx<T>::gen_x_inv_and_deriv(const GenRun& r, const cx<T>* F, cx<T>* t3, const cx<T>* A_, cx<T>* gx, cx<T>* tmp, const T* lx, long slices);
+  template void Ctx<T>::gen_x_inv_and_deriv(const GenRun& r, const GenForm& fm, const cx<T>* F, cx<T>* t3, const cx<T>* A_, cx<T>* gx, cx<T>* tmp, const T* lx, long slices);
 
 }  // namespace cmbl

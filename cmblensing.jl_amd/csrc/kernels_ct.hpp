@@ -33,6 +33,13 @@
 
 namespace cmbl {
 
+// N is a length of CMBL_CT_LIST: the compile-time-plan kernels are instantiated for it
+constexpr bool ct_listed(int N) {
+#define CMBL_X(n) if (N == n) return true;
+  CMBL_CT_LIST(CMBL_X)
+#undef CMBL_X
+  return false;
+}
 constexpr int ct_count(int N, int p) { int c = 0; while (N % p == 0) { N /= p; ++c; } return c; }
 constexpr int ct_np2(int N) { return num_stages(ct_count(N, 2)); }                                   // power-of-two stages
 constexpr int ct_nstages(int N) { return ct_np2(N) + ct_count(N, 3) + ct_count(N, 5); }
@@ -47,7 +54,7 @@ template <typename T> constexpr size_t ct_lds(int N, int rowsets = 1, int S = ct
 // the most sequences per workgroup whose rows fit the LDS: ct_S up to 1920 points; 2304 and 3072 take half groups in every launch
 template <typename T> constexpr int ct_Smax(int N) { return ct_lds<T>(N) <= 160 * 1024 ? ct_S<T>() : ct_S<T>() / 2; }
 // the fused row update (k_ct_adj_x: a whole row AND its RK operands in registers) spills 600-800 bytes per lane in double precision beyond 1920 points:
-// those shapes run the x transform and the RK update as launches of their own (Ctx::gen_ct_x)
+// those shapes run the x transform and the RK update as launches of their own (GenForm::row_update, Ctx::gen_form)
 template <typename T> constexpr bool ct_rowfuse_ok(int N) { return !(sizeof(T) == 8 && N > 1920); }
 // columns per workgroup of the delta-stage kernel (two LDS rows per column): the usual count, or half of it where that does not fit (Ny > ~1150;
 // the transposed side then moves 32-byte pieces)
@@ -55,6 +62,11 @@ template <typename T> constexpr bool ct_rowfuse_ok(int N) { return !(sizeof(T) =
 template <typename T> constexpr int ct_S2(int N) {
   return ct_lds<T>(N, 2) <= 160 * 1024 ? ct_S<T>() : ct_lds<T>(N, 2, ct_S<T>() / 2) <= 160 * 1024 ? ct_S<T>() / 2 : ct_S<T>() / 4;
 }
+// Two LDS rows per column fit for EVERY listed length in both precisions (ct_S2 halves or quarters the group until they do), so the delta flow's own
+// condition in Ctx::gen_form is true wherever Ny has a plan; a longer length that breaks this must show here, not as a silently unfused flow
+#define CMBL_X(n) static_assert(ct_lds<float>(n, 2, ct_S2<float>(n)) <= 160 * 1024 && ct_lds<double>(n, 2, ct_S2<double>(n)) <= 160 * 1024, "delta stage: two LDS rows");
+CMBL_CT_LIST(CMBL_X)
+#undef CMBL_X
 
 // fetch variants
 enum { CT_C = 0, CT_R1, CT_R2, CT_H1, CT_H2, CT_P1, CT_P2, CT_P3 };

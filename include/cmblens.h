@@ -83,6 +83,8 @@ int cmbl_ctx_geometry_host(cmbl_ctx* ctx, int which, double* out_host, size_t n)
  *        "pcache_max_mb"         CMBL_PCACHE_MAX_MB (16384)
  *        "fused_harm"            !CMBL_NO_FUSED_HARM (1)           harmonic-space operator chains inside one row pass
  *        "gen_separable", "gen_prologue", "gen_xderiv_fused"       any-size path stage fusions (CMBL_GEN_SEPARABLE / _PROLOGUE / _XDERIV_FUSED, all 1)
+ *                                                                   (these, gen_yy, gen_xmerge and gen_tiled are read in ONE place, once per flow: Ctx::gen_form in
+ *                                                                   csrc/engine.hpp turns them and the two side lengths into the stage form every launch of the flow follows)
  *        "gen_ct"                                                   any-size path: compile-time-plan transforms for the lengths 2^a 3^b 5^c of
  *                                                                   CMBL_CT_LIST (CMBL_GEN_CT, 1; 0 = the run-time-planned kernel for every length)
  *        "gen_ct_rows"                                              any-size path: x-pass launches with fewer row groups than CUs take groups of 4 / 2 rows instead
