@@ -1,6 +1,7 @@
 // C ABI of libcmblens_hip.so (see include/cmblens.h): entry points, argument checks and error plumbing.  No kernel is instantiated in this
 // translation unit -- the typed bodies do_*<T> live in api_body.hpp and are compiled by tu_main_{f32,f64}.hip (api_decl.hpp has the map).
 #include "api_decl.hpp"
+#include "engine_ud.hpp"
 
 namespace cmbl { thread_local std::string g_last_error; }
 using namespace cmbl;
@@ -366,6 +367,31 @@ int cmbl_quadratic_estimate(cmbl_dataset* ds, int which, const double* Cf_host, 
     CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1");
     BY_DTYPE(ds->ctx, do_qe<float>(ds, which, Cf_host, Cftilde_host, Cn_host, TF_host, Cphi_host, wiener_filtered, AL_in_host, phiqe_out, AL_out_host, B),
              do_qe<double>(ds, which, Cf_host, Cftilde_host, Cn_host, TF_host, Cphi_host, wiener_filtered, AL_in_host, phiqe_out, AL_out_host, B));
+  });
+}
+
+// ---- ud_grade: the one entry point with two contexts ---------------------------------------------------------------
+int cmbl_ud_grade(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv_pixwin, int anti_aliasing, int bi, const void* in, int bo, void* out, int P, int B) {
+  return guard([&] {
+    NOTNULL(src); NOTNULL(dst); NOTNULL(in); NOTNULL(out); BASIS_OK(bi); BASIS_OK(bo); POLB_OK(P, B);
+    const CtxBase& s = *src->p; const CtxBase& d = *dst->p;
+    CMBL_REQUIRE(s.dtype == d.dtype && s.device == d.device && s.stream == d.stream, ERR_ARG, "ud_grade: the two contexts must share dtype, device and stream");
+    CMBL_REQUIRE(mode == CMBL_UD_MAP || mode == CMBL_UD_FOURIER, ERR_ARG, "mode must be CMBL_UD_MAP or CMBL_UD_FOURIER");
+    CMBL_REQUIRE((bi == B_HARMONIC) == (bo == B_HARMONIC), ERR_ARG, "ud_grade: HARMONIC is accepted on both sides at once only (the engine has no EB-map basis)");
+    CMBL_REQUIRE(bi != B_HARMONIC || mode == CMBL_UD_FOURIER, ERR_ARG, "ud_grade: HARMONIC planes are accepted in Fourier mode only");
+    const size_t el = s.dtype == CMBL_F32 ? 4 : 8, sl = (size_t)P * B;
+    const char* a = (const char*)in; const char* b = (const char*)out;
+    const size_t na = sl * el * (bi == B_MAP ? (size_t)s.npix() : 2 * (size_t)s.plane()), nb = sl * el * (bo == B_MAP ? (size_t)d.npix() : 2 * (size_t)d.plane());
+    CMBL_REQUIRE(a + na <= b || b + nb <= a, ERR_ARG, "ud_grade: in and out must not alias");
+    BY_DTYPE(src, do_ud_grade<float>(src, dst, mode, deconv_pixwin, anti_aliasing, bi, in, bo, out, P, B),
+             do_ud_grade<double>(src, dst, mode, deconv_pixwin, anti_aliasing, bi, in, bo, out, P, B));
+  });
+}
+int cmbl_pixwin_host(cmbl_ctx* ctx, double* out_host, size_t n) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(out_host);
+    CMBL_REQUIRE(n == (size_t)ctx->p->plane(), ERR_SHAPE, "pixwin output has the wrong length");
+    pixwin_plane(*ctx->p, out_host);
   });
 }
 

@@ -1,6 +1,7 @@
 // The typed bodies behind the C ABI (declared in api_decl.hpp); included by tu_main_{f32,f64}.hip only, which instantiate them.
 #pragma once
 #include "api_decl.hpp"
+#include "engine_ud.hpp"
 
 namespace cmbl {
 
@@ -228,5 +229,8 @@ template <typename T> void do_max_lensing_step(cmbl_flow* L, int basis, const vo
 template <typename T> void do_dataset_create(cmbl_dataset* h, int npol) { ds_of<T>(h) = std::make_unique<Dataset<T>>(C<T>(h->ctx), npol); }
 template <typename T> void do_dataset_set_op(cmbl_dataset* ds, int which, const void* planes, int nplanes) { ds_of<T>(ds)->set_op(which, planes, nplanes); }
 template <typename T> void do_dataset_set_data(cmbl_dataset* ds, const void* d, int B) { ds_of<T>(ds)->set_data(d, B); }
+template <typename T> void do_ud_grade(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv, int aa, int bi, const void* in, int bo, void* out, int P, int B) {
+  ud_grade<T>(C<T>(src), C<T>(dst), mode, deconv != 0, aa != 0, bi, in, bo, out, P, B);
+}
 
 }  // namespace cmbl

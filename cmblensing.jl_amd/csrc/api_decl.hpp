@@ -50,6 +50,7 @@ template <typename T> void do_max_lensing_step(cmbl_flow* L, int basis, const vo
 template <typename T> void do_dataset_create(cmbl_dataset* h, int npol);
 template <typename T> void do_dataset_set_op(cmbl_dataset* ds, int which, const void* planes, int nplanes);
 template <typename T> void do_dataset_set_data(cmbl_dataset* ds, const void* d, int B);
+template <typename T> void do_ud_grade(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv, int aa, int bi, const void* in, int bo, void* out, int P, int B);
 
 #define CMBL_INSTANTIATE_API(T) \
   template void do_convert<T>(cmbl_ctx* ctx, int bi, const void* in, int bo, void* out, int P, int B); \
@@ -76,5 +77,6 @@ template <typename T> void do_dataset_set_data(cmbl_dataset* ds, const void* d, 
   template void do_max_lensing_step<T>(cmbl_flow* L, int basis, const void* phi, const void* eta, int nb, double* out); \
   template void do_dataset_create<T>(cmbl_dataset* h, int npol); \
   template void do_dataset_set_op<T>(cmbl_dataset* ds, int which, const void* planes, int nplanes); \
-  template void do_dataset_set_data<T>(cmbl_dataset* ds, const void* d, int B);
+  template void do_dataset_set_data<T>(cmbl_dataset* ds, const void* d, int B); \
+  template void do_ud_grade<T>(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv, int aa, int bi, const void* in, int bo, void* out, int P, int B);
 }  // namespace cmbl

@@ -12,11 +12,12 @@ import ctypes
 import numpy as np
 import torch
 
-from .lib import load_library, check
+from .lib import load_library, check, CmblError
 
 MAP, FOURIER, HARMONIC = 0, 1, 2
 FLOW_FWD, FLOW_INV, FLOW_ADJ, FLOW_INVADJ = 0, 1, 2, 3
 DIAG_MUL, DIAG_DIV_NAN2ZERO = 1, 3
+UD_MAP, UD_FOURIER = 0, 1
 (OP_CF_INV, OP_CN_INV, OP_B, OP_MF, OP_D, OP_D_INV, OP_PRECOND_INV, OP_CPHI_INV, OP_G_INV, OP_MPIX) = range(10)
 
 
@@ -74,6 +75,15 @@ class ProjLambert:
     sin2phi = property(lambda s: s._g(3, (s.Nx, s.Nyh)))
     cos2phi = property(lambda s: s._g(4, (s.Nx, s.Nyh)))
     lmag = property(lambda s: s._g(5, (s.Nx, s.Nyh)))
+
+    @property
+    def pixwin(self):
+        """pixwin(θpix, ℓy) * pixwin(θpix, ℓx)' on the half plane (src/proj_lambert.jl:200, 552): host plane (Nx, Nyh), float64"""
+        if "pixwin" not in self._geom:
+            out = np.empty(self.Nx * self.Nyh, dtype=np.float64)
+            check(self.lib.cmbl_pixwin_host(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), out.size))
+            self._geom["pixwin"] = out.reshape(self.Nx, self.Nyh)
+        return self._geom["pixwin"]
 
     @property
     def Opix(self):
@@ -302,6 +312,51 @@ class Field:
 
     def __neg__(self):
         return self.proj.axpby(-1.0, self)
+
+
+def pixwin(theta_pix, ell):
+    """pixwin(θpix, ℓ) (src/proj_lambert.jl:200): window of square pixels of width `theta_pix` arcmin at the multipoles `ell`"""
+    return np.sinc(np.asarray(ell, dtype=np.float64) * np.deg2rad(theta_pix / 60) / (2 * np.pi))
+
+
+def ud_grade(f, theta_new, mode="map", deconv_pixwin=None, anti_aliasing=None, proj_new=None):
+    """ud_grade(f, θnew; mode, deconv_pixwin, anti_aliasing) (src/proj_lambert.jl:533-592): Field `f` at the pixel size `theta_new` (arcmin),
+    in integer steps, on the device (`cmbl_ud_grade`, include/cmblens.h has the semantics).  mode "map" averages / replicates pixels, "fourier"
+    truncates the Fourier grid; both flags default to `mode == "map"` like the reference's -- so an upgrade needs `deconv_pixwin=False`, as
+    there.  `proj_new`: the ProjLambert of the result (default: one of the new size, made once per source context and `theta_new`).  The
+    result is a MAP Field for map mode without deconvolution, otherwise a Field in the complex basis.  ValueError where the reference throws."""
+    p = f.proj
+    theta_new = float(theta_new)
+    if theta_new == p.theta_pix and proj_new is None:
+        return f                                                            # :542
+    if mode not in ("map", "fourier"):
+        raise ValueError("Available modes: ['map', 'fourier']")             # :543
+    deconv_pixwin = (mode == "map") if deconv_pixwin is None else bool(deconv_pixwin)
+    anti_aliasing = (mode == "map") if anti_aliasing is None else bool(anti_aliasing)
+    if proj_new is None:
+        down = theta_new > p.theta_pix
+        ratio = theta_new / p.theta_pix if down else p.theta_pix / theta_new
+        fac = int(round(ratio))
+        if fac < 2 or abs(ratio - fac) > 1e-6 * ratio or (down and (p.Ny % fac or p.Nx % fac)):
+            raise ValueError("Can only ud_grade in integer steps")          # :546
+        cache = p.__dict__.setdefault("_ud_proj", {})
+        if theta_new not in cache:
+            Ny, Nx = (p.Ny // fac, p.Nx // fac) if down else (p.Ny * fac, p.Nx * fac)
+            cache[theta_new] = ProjLambert(Ny, Nx, theta_new, p.T, p.device.index)
+        proj_new = cache[theta_new]
+    if f.basis == HARMONIC and mode == "map":
+        raise ValueError("ud_grade in map mode needs a MAP or FOURIER field (the engine has no EB-map basis)")
+    basis_out = MAP if (mode == "map" and not deconv_pixwin) else (HARMONIC if f.basis == HARMONIC else FOURIER)
+    P, B = p._check(f.arr, f.basis)
+    out = proj_new.empty(basis_out, P, B)
+    try:
+        check(p.lib.cmbl_ud_grade(p._h, proj_new._h, UD_MAP if mode == "map" else UD_FOURIER, int(deconv_pixwin), int(anti_aliasing),
+                                  f.basis, _ptr(f.arr), basis_out, _ptr(out), P, B))
+    except CmblError as e:
+        if e.code in (1, 2):                                                # CMBL_ERR_ARG / CMBL_ERR_SHAPE: "Not implemented" (:582, 585), integer steps (:546)
+            raise ValueError(str(e)) from e
+        raise
+    return Field(proj_new, out, basis_out)
 
 
 class _Adjoint:

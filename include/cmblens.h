@@ -142,6 +142,37 @@ int cmbl_rfft(cmbl_ctx* ctx, const void* map, void* fourier, int npol, int nbatc
 int cmbl_irfft(cmbl_ctx* ctx, const void* fourier, void* map, int npol, int nbatch);
 int cmbl_convert(cmbl_ctx* ctx, int basis_in, const void* in, int basis_out, void* out, int npol, int nbatch);
 
+/* ---- ud_grade(f, θnew; mode, deconv_pixwin, anti_aliasing) (src/proj_lambert.jl:533-592): the field `in` on the grid of `src` is brought to the
+ *      grid of `dst`.  The only entry point with two contexts: they must share dtype, device and stream (else CMBL_ERR_ARG); the work is
+ *      ordered on that stream like every other entry point; `in` and `out` must not alias.
+ *      Geometry: an integer fac >= 2 with src.N = fac * dst.N on both axes and theta_dst = fac * theta_src (relative 1e-6) is a downgrade, the
+ *      mirror image an upgrade, anything else CMBL_ERR_SHAPE ("Can only ud_grade in integer steps", :546).  Equal geometry (`θnew == θ &&
+ *      return f`, :542) is a copy, or the plain basis conversion asked for.
+ *      Bases: every step acts on each (pol, batch) plane separately, pol components are never mixed.  basis_in / basis_out: CMBL_MAP or a complex
+ *      basis, independently; CMBL_HARMONIC only on both sides at once and only in Fourier mode (the planes are then treated like FOURIER planes,
+ *      what the reference does with EB fields in :fourier mode); any other mix with CMBL_HARMONIC is CMBL_ERR_ARG -- the engine has no EB-map basis.
+ *      A complex input is taken to be the transform of real maps, as every reference Field is: where the reference goes through Map(f), the
+ *      imaginary parts a c2r transform would drop (ky = 0 and Nyquist after the x pass) are NOT dropped by the paths that stay in Fourier space.
+ *      Semantics -- the reference's, quirks included:
+ *        downgrade, CMBL_UD_MAP:      [anti_aliasing] -> mean over fac x fac pixel blocks (:561) -> [deconv_pixwin: divide by
+ *                                     PWF = pixwin(θnew) / pixwin(θ) on the new grid, nan2zero (:552, 571)]
+ *        downgrade, CMBL_UD_FOURIER:  [anti_aliasing] -> keep rows ky = 0 ... Ny_new/2 and columns kx = 0 ... ceil(Nx_new/2) - 1, -floor(Nx_new/2) ... -1
+ *                                     of the half plane (:566) -> [divide by PWF].  NOT rescaled by 1/fac^2 although the transforms are unnormalised
+ *                                     (src/util_fft.jl:20-25): the map of the result is fac^2 times too large, as in the reference
+ *        upgrade, CMBL_UD_MAP:        every pixel replicated fac x fac (:575-580); anti_aliasing is ignored; deconv_pixwin is CMBL_ERR_ARG
+ *                                     ("Not implemented", :582)
+ *        upgrade, CMBL_UD_FOURIER:    CMBL_ERR_ARG ("Not implemented", :585)
+ *        anti_aliasing:               zeroes every coefficient of the input with |ly| >= nyquist_new or |lx| >= nyquist_new (:557), decided by INTEGER
+ *                                     index: 2 |ky| >= Ny_new or 2 |kx| >= Nx_new (the reference compares rounded floats that are equal at the boundary)
+ *      With anti_aliasing the map-mode block mean is applied as a Fourier-space multiply (no aliased term survives): one transform at the source
+ *      size (none for complex input) and one at the new size only for a MAP output; equal to the reference's three-transform sequence up to rounding. */
+enum { CMBL_UD_MAP = 0, CMBL_UD_FOURIER = 1 };
+int cmbl_ud_grade(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv_pixwin, int anti_aliasing,
+                  int basis_in, const void* in, int basis_out, void* out, int npol, int nbatch);
+/* pixwin(θpix, ℓ) (src/proj_lambert.jl:200) on the context's half plane: sinc(ly Δx / 2π) * sinc(lx Δx / 2π) = sinc(ky / Ny) * sinc(kx / Nx),
+ * real (Ny/2+1, Nx) plane in the reference layout, host, double; n = (Ny/2+1) * Nx. */
+int cmbl_pixwin_host(cmbl_ctx* ctx, double* out_host, size_t n);
+
 /* ---- diagonal operators: DiagOp `*` and `\` with automatic basis conversion, BlockDiagIEB
  *      (src/specialops.jl:9-10, 61-118; src/field_vectors.jl:64-66).
  *      diag: real (Ny/2+1, Nx, npol) planes, diagonal in `basis_diag` (FOURIER or HARMONIC). */

@@ -380,6 +380,39 @@ function set_sum_accuracy_mode!(proj::ProjLambert, mode)
     chk(ccall((:cmbl_set_sum_accuracy_mode, lib), Cint, (Ptr{Cvoid}, Cint), hip_ctx(proj).h, m))
 end
 
+# `ud_grade` (src/proj_lambert.jl:533-592) for device-backed flat-sky fields: one `cmbl_ud_grade` call between the contexts of the two grids
+# (include/cmblens.h has the semantics: the reference's, with the Nyquist cut decided by integer index).  Keywords, defaults, errors and the basis
+# of the result are the reference's.  Map mode acts on maps of the QU components, so an EB field goes through its QU-Fourier form; Fourier mode
+# takes the half planes as they come (EB stays EB).
+function CMBLensing.ud_grade(f::BaseField{B,<:ProjLambert,<:Any,<:ROCArray}, θnew;
+                             mode=:map, deconv_pixwin=(mode==:map), anti_aliasing=(mode==:map)) where {B}
+    θ = f.θpix
+    θnew == θ && return f
+    (mode in (:map, :fourier)) || throw(ArgumentError("Available modes: [:map,:fourier]"))
+    down = θnew > θ
+    ratio = down ? θnew / θ : θ / θnew
+    fac = round(Int, ratio)
+    (fac >= 2 && isapprox(ratio, fac; rtol=1e-6)) || throw(ArgumentError("Can only ud_grade in integer steps"))
+    (down || mode == :map) || error("Not implemented")
+    (down || !deconv_pixwin) || error("Not implemented")
+    Ny, Nx = down ? (f.Ny ÷ fac, f.Nx ÷ fac) : (f.Ny * fac, f.Nx * fac)
+    proj = ProjLambert(; Ny, Nx, θpix=θnew, T=real(f.T), f.storage, f.rotator)
+    g = (mode == :map && basis_tag(f) == HARMONIC) ? Ð(f) : f
+    complex_out = mode == :fourier || deconv_pixwin
+    tag_out = complex_out ? (basis_tag(g) == HARMONIC ? HARMONIC : FOURIER) : MAP
+    Bg = basis_of(g)
+    Bout = complex_out ? (basis_tag(g) == MAP ? Fourier(Bg()) : Bg) : Map(Bg())      # as the reference spells it (:560, 565)
+    a = g.arr
+    out = similar(a, complex_out ? Complex{real(f.T)} : real(f.T), (complex_out ? Ny ÷ 2 + 1 : Ny, Nx, npol(g), nbatch(g)))
+    GC.@preserve a out chk(ccall((:cmbl_ud_grade, lib), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint),
+              hip_ctx(g.metadata).h, hip_ctx(proj).h, mode == :map ? 0 : 1, deconv_pixwin ? 1 : 0, anti_aliasing ? 1 : 0,
+              basis_tag(g), devptr(a), tag_out, devptr(out), npol(g), nbatch(g)))
+    keepalive(hip_ctx(g.metadata), a)
+    BaseField{Bout}(out, proj)
+end
+basis_of(::BaseField{B}) where {B} = B
+
 # device RNG for `simulate` / `randn!` (src/specialops.jl:6, src/base_fields.jl:169-170): counter-based Philox4x32-10
 mutable struct HIPPhilox <: Random.AbstractRNG
     seed   :: UInt64
