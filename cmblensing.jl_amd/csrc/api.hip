@@ -2,6 +2,7 @@
 // translation unit -- the typed bodies do_*<T> live in api_body.hpp and are compiled by tu_main_{f32,f64}.hip (api_decl.hpp has the map).
 #include "api_decl.hpp"
 #include "engine_ud.hpp"
+#include "engine_cl.hpp"
 
 namespace cmbl { thread_local std::string g_last_error; }
 using namespace cmbl;
@@ -392,6 +393,49 @@ int cmbl_pixwin_host(cmbl_ctx* ctx, double* out_host, size_t n) {
     NOTNULL(ctx); NOTNULL(out_host);
     CMBL_REQUIRE(n == (size_t)ctx->p->plane(), ERR_SHAPE, "pixwin output has the wrong length");
     pixwin_plane(*ctx->p, out_host);
+  });
+}
+
+// ---- get_Cℓ: the binning plan (host, double) and the binned sums on the device -----------------------------------------
+int cmbl_clbins_create(cmbl_ctx* ctx, const double* ledges_host, int nedges, const double* w_host, size_t nw, cmbl_clbins** out) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(ledges_host); NOTNULL(out);
+    CMBL_REQUIRE(nedges >= 2 && nedges <= 65536, ERR_ARG, "clbins: 2 <= nedges <= 65536");
+    for (int i = 0; i < nedges; ++i) CMBL_REQUIRE(std::isfinite(ledges_host[i]) && (i == 0 || ledges_host[i] > ledges_host[i - 1]), ERR_ARG, "clbins: the edges must be finite and strictly increasing");
+    if (w_host) {
+      CMBL_REQUIRE(nw == (size_t)ctx->p->plane(), ERR_SHAPE, "clbins: the weight plane has the wrong length");
+      for (size_t i = 0; i < nw; ++i) CMBL_REQUIRE(std::isfinite(w_host[i]), ERR_ARG, "clbins: the weights must be finite (apply nan2zero first)");
+    }
+    auto h = std::make_unique<cmbl_clbins>();
+    h->p = std::make_unique<ClBins>(*ctx->p, ledges_host, nedges, w_host);
+    *out = h.release();
+  });
+}
+int cmbl_clbins_destroy(cmbl_clbins* bins) { return guard([&] { delete bins; }); }
+int cmbl_clbins_info_host(cmbl_clbins* bins, int which, double* out_host, size_t n) {
+  return guard([&] {
+    NOTNULL(bins); NOTNULL(out_host);
+    const ClBins& b = *bins->p;
+    const std::vector<double>* v = which == CMBL_CL_A ? &b.A : which == CMBL_CL_SL ? &b.Sl : which == CMBL_CL_COUNT ? &b.count : nullptr;
+    CMBL_REQUIRE(v != nullptr, ERR_ARG, "clbins: bad selector");
+    CMBL_REQUIRE(n == v->size(), ERR_SHAPE, "clbins: output has the wrong length (nedges - 1)");
+    std::memcpy(out_host, v->data(), n * sizeof(double));
+  });
+}
+int cmbl_get_cl(cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, const void* f2, int P, int B, const int* pairs_host, int npairs, int moments, double* out) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(bins); NOTNULL(f1); NOTNULL(pairs_host); NOTNULL(out); BASIS_OK(basis); POLB_OK(P, B);
+    CMBL_REQUIRE(B <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
+    CMBL_REQUIRE(npairs >= 1 && npairs <= CL_MAXPAIRS, ERR_ARG, "get_cl: 1 <= npairs <= 9");
+    CMBL_REQUIRE(moments == 1 || moments == 2, ERR_ARG, "get_cl: moments must be 1 (S1) or 2 (S1, S2)");
+    ClPairs pr{};
+    pr.n = npairs;
+    for (int k = 0; k < npairs; ++k) {
+      const int a = pairs_host[2 * k], b = pairs_host[2 * k + 1];
+      CMBL_REQUIRE(a >= 0 && a < P && b >= 0 && b < P, ERR_ARG, "get_cl: a pair indexes a plane outside [0, npol)");
+      pr.a[k] = (signed char)a; pr.b[k] = (signed char)b;
+    }
+    BY_DTYPE(ctx, do_get_cl<float>(ctx, bins, basis, f1, f2, P, B, pr, moments, out), do_get_cl<double>(ctx, bins, basis, f1, f2, P, B, pr, moments, out));
   });
 }
 

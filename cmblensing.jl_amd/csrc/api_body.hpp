@@ -2,6 +2,7 @@
 #pragma once
 #include "api_decl.hpp"
 #include "engine_ud.hpp"
+#include "engine_cl.hpp"
 
 namespace cmbl {
 
@@ -231,6 +232,9 @@ template <typename T> void do_dataset_set_op(cmbl_dataset* ds, int which, const 
 template <typename T> void do_dataset_set_data(cmbl_dataset* ds, const void* d, int B) { ds_of<T>(ds)->set_data(d, B); }
 template <typename T> void do_ud_grade(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv, int aa, int bi, const void* in, int bo, void* out, int P, int B) {
   ud_grade<T>(C<T>(src), C<T>(dst), mode, deconv != 0, aa != 0, bi, in, bo, out, P, B);
+}
+template <typename T> void do_get_cl(cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, const void* f2, int P, int B, const ClPairs& pr, int moments, double* out) {
+  get_cl<T>(C<T>(ctx), *bins->p, basis, f1, f2, P, B, pr, moments, out);
 }
 
 }  // namespace cmbl

@@ -13,9 +13,11 @@
 #pragma once
 #include "engine.hpp"
 #include "drivers.hpp"
+#include "engine_cl.hpp"
 #include "../../include/cmblens.h"
 
 struct cmbl_ctx { std::unique_ptr<cmbl::CtxBase> p; };
+struct cmbl_clbins { std::unique_ptr<cmbl::ClBins> p; };
 struct cmbl_flow { cmbl_ctx* ctx; std::unique_ptr<cmbl::Flow<float>> f32; std::unique_ptr<cmbl::Flow<double>> f64; };
 struct cmbl_dataset {
   cmbl_ctx* ctx; std::unique_ptr<cmbl::Dataset<float>> f32; std::unique_ptr<cmbl::Dataset<double>> f64;
@@ -51,6 +53,7 @@ template <typename T> void do_dataset_create(cmbl_dataset* h, int npol);
 template <typename T> void do_dataset_set_op(cmbl_dataset* ds, int which, const void* planes, int nplanes);
 template <typename T> void do_dataset_set_data(cmbl_dataset* ds, const void* d, int B);
 template <typename T> void do_ud_grade(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv, int aa, int bi, const void* in, int bo, void* out, int P, int B);
+template <typename T> void do_get_cl(cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, const void* f2, int P, int B, const ClPairs& pr, int moments, double* out);
 
 #define CMBL_INSTANTIATE_API(T) \
   template void do_convert<T>(cmbl_ctx* ctx, int bi, const void* in, int bo, void* out, int P, int B); \
@@ -78,5 +81,6 @@ template <typename T> void do_ud_grade(cmbl_ctx* src, cmbl_ctx* dst, int mode, i
   template void do_dataset_create<T>(cmbl_dataset* h, int npol); \
   template void do_dataset_set_op<T>(cmbl_dataset* ds, int which, const void* planes, int nplanes); \
   template void do_dataset_set_data<T>(cmbl_dataset* ds, const void* d, int B); \
-  template void do_ud_grade<T>(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv, int aa, int bi, const void* in, int bo, void* out, int P, int B);
+  template void do_ud_grade<T>(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv, int aa, int bi, const void* in, int bo, void* out, int P, int B); \
+  template void do_get_cl<T>(cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, const void* f2, int P, int B, const ClPairs& pr, int moments, double* out);
 }  // namespace cmbl

@@ -359,6 +359,172 @@ def ud_grade(f, theta_new, mode="map", deconv_pixwin=None, anti_aliasing=None, p
     return Field(proj_new, out, basis_out)
 
 
+# ---- power spectra (src/proj_lambert.jl:415-419, 470-513; src/cls.jl:85-97) -------------------------------------------------------------
+_CL_PLANE = {1: {"I": 0}, 2: {"Q": 0, "U": 1, "E": 0, "B": 1}, 3: {"I": 0, "Q": 1, "U": 2, "E": 1, "B": 2}}
+_CL_WHICH = {1: "II", 2: ("EE", "BB"), 3: ("II", "EE", "BB", "IE", "IB", "EB")}       # the reference's defaults (:505, 510)
+
+
+class _ClPlan:
+    """binning plan of one (context, edges, weight plane): cmbl_clbins_*; A, Sℓ and the full-plane mode counts per bin are host arrays"""
+
+    def __init__(self, proj, ledges, w):
+        self.lib, self.ledges, self.nbins = proj.lib, ledges, len(ledges) - 1
+        self._h = ctypes.c_void_p()
+        pd = ctypes.POINTER(ctypes.c_double)
+        check(self.lib.cmbl_clbins_create(proj._h, ledges.ctypes.data_as(pd), len(ledges), None if w is None else w.ctypes.data_as(pd),
+                                          0 if w is None else w.size, ctypes.byref(self._h)))
+        self.A, self.Sl, self.count = (np.empty(self.nbins) for _ in range(3))
+        for which, a in enumerate((self.A, self.Sl, self.count)):
+            check(self.lib.cmbl_clbins_info_host(self._h, which, a.ctypes.data_as(pd), a.size))
+
+    def __del__(self):
+        try:
+            if self._h:
+                self.lib.cmbl_clbins_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def _cl_plan(proj, dl, ledges, Clfid):
+    """the plan of (edges, weight), made once per ProjLambert: found by the identity of `Clfid` first, else by the bytes of its weight plane"""
+    ledges = np.arange(0, 16000 + 1, dl, dtype=np.float64) if ledges is None else np.ascontiguousarray(ledges, dtype=np.float64)
+    cache = proj.__dict__.setdefault("_cl_plans", {})
+    ek = ledges.tobytes()
+    hit = cache.get((ek, id(Clfid)))
+    if hit is not None and hit[0] is Clfid:
+        return hit[1]
+    w = None
+    if Clfid is not None:                                                   # w = nan2zero((2 Cℓfid(ℓ)² / (2ℓ+1))⁻¹) (:482); a Cls is NaN outside its table
+        L = proj.lmag
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            w = 1.0 / (2 * np.asarray(Clfid(L), dtype=np.float64) ** 2 / (2 * L + 1))
+        w = np.ascontiguousarray(np.where(np.isfinite(w), w, 0.0))
+    wk = (ek, None if w is None else w.tobytes())
+    if wk not in cache:
+        cache[wk] = _ClPlan(proj, ledges, w)
+    cache[(ek, id(Clfid))] = (Clfid, cache[wk])
+    return cache[wk]
+
+
+def _cl_sums(f1, f2, names, plan, moments):
+    """S1 (and S2) of every letter pair of `names`: host array (B, len(names), moments, nbins).  Pairs of Q / U letters are read from the QU planes
+    (a MAP field goes in as it is), pairs of E / B letters from the HARMONIC planes, I from either: at most two cmbl_get_cl calls."""
+    p = f1.proj
+    P, B = p._check(f1.arr, f1.basis)
+    if f2 is not None and (f2.proj is not p or p._check(f2.arr, f2.basis) != (P, B)):
+        raise ValueError("get_Cl: the two fields must share their ProjLambert, npol and batch size")
+    letters = _CL_PLANE[P]
+    groups = {"qu": [], "eb": [], "i": []}
+    for k, n in enumerate(names):
+        if len(n) != 2 or n[0] not in letters or n[1] not in letters:
+            raise ValueError(f"get_Cl: which = {n!r}; two letters of {'/'.join(letters)} for a field of {P} plane(s)")
+        qu, eb = "Q" in n or "U" in n, "E" in n or "B" in n
+        if qu and eb:
+            raise ValueError(f"get_Cl: which = {n!r} mixes a Q / U letter with an E / B letter")
+        groups["qu" if qu else "eb" if eb else "i"].append(k)
+    for g in ("qu", "eb"):                                                  # I-only pairs ride with a call that is made anyway
+        if groups[g]:
+            groups[g], groups["i"] = sorted(groups[g] + groups["i"]), []
+            break
+    out = np.empty((B, len(names), moments, plan.nbins))
+    for g, ks in groups.items():
+        if not ks:
+            continue
+        if g == "eb":
+            a, b = f1.to(HARMONIC), (None if f2 is None else f2.to(HARMONIC))
+        elif g == "qu":
+            a, b = (f1.to(FOURIER) if f1.basis == HARMONIC else f1), (None if f2 is None else f2.to(FOURIER) if f2.basis == HARMONIC else f2)
+            if b is not None and a.basis != b.basis:
+                a, b = a.to(FOURIER), b.to(FOURIER)
+        else:
+            a, b = f1, (None if f2 is None else f2.to(f1.basis))
+        pairs = (ctypes.c_int * (2 * len(ks)))(*[letters[c] for k in ks for c in names[k]])
+        dev = torch.empty((B, len(ks), moments, plan.nbins), dtype=torch.float64, device=p.device)
+        check(p.lib.cmbl_get_cl(p._h, plan._h, a.basis, _ptr(a.arr), None if b is None else _ptr(b.arr), P, B, pairs, len(ks), moments, _ptr(dev)))
+        out[:, ks] = dev.cpu().numpy()
+    return out
+
+
+def get_Cl(f1, f2=None, *, dl=50, ledges=None, Clfid=None, err_estimate=False, which=None):
+    """get_Cℓ(f₁, f₂=f₁; Δℓ, ℓedges, Cℓfid, err_estimate, which) (src/proj_lambert.jl:470-513): binned auto- / cross-spectra of Fields of any basis, on the
+    device (`cmbl_get_cl`; include/cmblens.h has the semantics and the three places where the reference is not followed to the letter).  `which`: one
+    string ("EE") gives one `Cls`; several, a dict keyed by them; default: the reference's per spin -- "II", ("EE", "BB"),
+    ("II", "EE", "BB", "IE", "IB", "EB").  A letter is one of I Q U E B; a pair may not mix Q / U with E / B.  `Clfid`: callable or `Cls`.  A batch
+    of B > 1 gives a list of B such results.  err_estimate=True: every `Cls` comes as (Cls, σℓ) with σℓ = sqrt((S2/A − (S1/A)²)/N)."""
+    from .sim import Cls
+    P = f1.arr.shape[1]
+    which = _CL_WHICH[P] if which is None else which
+    single = isinstance(which, str)
+    names = [which] if single else list(which)
+    plan = _cl_plan(f1.proj, dl, ledges, Clfid)
+    S = _cl_sums(f1, f2, names, plan, 2 if err_estimate else 1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ell, cl = plan.Sl / plan.A, S[:, :, 0] / plan.A                     # empty bins are NaN: Cls drops them (src/cls.jl:18-23)
+        sig = np.sqrt(np.maximum(S[:, :, 1] / plan.A - cl ** 2, 0) / (plan.count / 2)) if err_estimate else None
+
+    def one(b, k):
+        c = Cls(ell, cl[b, k])
+        return (c, sig[b, k][~np.isnan(cl[b, k])]) if err_estimate else c
+
+    res = [one(b, 0) if single else {n: one(b, k) for k, n in enumerate(names)} for b in range(S.shape[0])]
+    return res[0] if len(res) == 1 else res
+
+
+def _cl_map(res, fn):
+    """apply fn(ℓ) -> factor to every Cls (and σℓ) of a get_Cl result"""
+    from .sim import Cls
+    if isinstance(res, list):
+        return [_cl_map(r, fn) for r in res]
+    if isinstance(res, dict):
+        return {k: _cl_map(v, fn) for k, v in res.items()}
+    if isinstance(res, tuple):
+        return (_cl_map(res[0], fn), res[1] * fn(res[0].ell))
+    return Cls(res.ell, res.cl * fn(res.ell))
+
+
+def get_Dl(*args, **kw):
+    """get_Dℓ = ℓ²·Cℓ/2π (src/cls.jl:86, as written: ℓ², not ℓ(ℓ+1))"""
+    return _cl_map(get_Cl(*args, **kw), lambda l: l ** 2 / (2 * np.pi))
+
+
+def get_l4Cl(*args, **kw):
+    """get_ℓ⁴Cℓ = ℓ⁴·Cℓ (src/cls.jl:87)"""
+    return _cl_map(get_Cl(*args, **kw), lambda l: l ** 4)
+
+
+def get_rhol(f1, f2=None, *, which=None, **kw):
+    """get_ρℓ(f; which) and get_ρℓ(f1, f2) (src/cls.jl:88-97): Cℓx / sqrt(Cℓ1·Cℓ2) of component a of f1 against component b of f2 (f2 = f1 when not
+    given), `which` = the two letters "ab" (default "II" for spin-0 fields)"""
+    from .sim import Cls
+    if which is None:
+        if f1.arr.shape[1] != 1:
+            raise ValueError("get_rhol: `which` (two letters) is needed for fields of more than one plane")
+        which = "II"
+    a, b = which
+    if kw.pop("err_estimate", False):
+        raise ValueError("get_rhol takes no err_estimate")
+    plan = _cl_plan(f1.proj, kw.pop("dl", 50), kw.pop("ledges", None), kw.pop("Clfid", None))
+    if kw:
+        raise TypeError(f"get_rhol: unexpected keywords {sorted(kw)}")
+    g = f1 if f2 is None else f2
+    c1, cx = _cl_sums(f1, None, [a + a], plan, 1)[:, 0, 0], _cl_sums(f1, f2, [a + b], plan, 1)[:, 0, 0]
+    c2 = _cl_sums(g, None, [b + b], plan, 1)[:, 0, 0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ell, rho = plan.Sl / plan.A, cx / np.sqrt(c1 * c2)                  # the 1/A cancel
+        rho = np.where(plan.A > 0, rho, np.nan)
+    res = [Cls(ell, r) for r in rho]
+    return res[0] if len(res) == 1 else res
+
+
+def cov_to_Cl(plane, proj, **kw):
+    """cov_to_Cℓ(C) (src/proj_lambert.jl:415-419), literally: get_Cℓ(sqrt.(diag(C)))·sqrt(α), α = Nx·Ny/Δx², for the diagonal `plane` (Nx, Nyh) of a spin-0
+    Fourier covariance.  NOT the inverse of Cℓ_to_Cov = Cℓ/Ωpix: it returns Cℓ / (Δx·sqrt(Nx·Ny))."""
+    d = np.sqrt(np.asarray(plane, dtype=np.float64)).reshape(1, 1, proj.Nx, proj.Nyh)
+    f = Field(proj, proj.tensor(d.astype(np.complex128)), FOURIER)
+    return _cl_map(get_Cl(f, **kw), lambda l: np.sqrt(proj.Nx * proj.Ny / proj.Opix))
+
+
 class _Adjoint:
     def __init__(self, L):
         self.L = L

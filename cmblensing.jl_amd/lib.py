@@ -17,7 +17,7 @@ SYMBOLS = [
     "cmbl_fourier_lmul", "cmbl_map_fma", "cmbl_randn", "cmbl_gradientf_logpdf", "cmbl_wiener_cg", "cmbl_logpdf_mixed", "cmbl_grad_logpdf_mixed",
     "cmbl_hmc_step", "cmbl_map_joint_step", "cmbl_quadratic_estimate", "cmbl_norm", "cmbl_logdet_diag", "cmbl_tr_diag", "cmbl_set_sum_accuracy_mode",
     "cmbl_timer_report", "cmbl_device_malloc", "cmbl_device_free", "cmbl_copy_to_device", "cmbl_copy_to_host",
-    "cmbl_ud_grade", "cmbl_pixwin_host",
+    "cmbl_ud_grade", "cmbl_pixwin_host", "cmbl_clbins_create", "cmbl_clbins_destroy", "cmbl_clbins_info_host", "cmbl_get_cl",
 ]
 
 
@@ -184,6 +184,10 @@ def load_library():
         "cmbl_copy_to_host": [vp, vp, vp, ctypes.c_size_t],
         "cmbl_ud_grade": [vp, vp, ci, ci, ci, ci, vp, ci, vp, ci, ci],
         "cmbl_pixwin_host": [vp, pd, ctypes.c_size_t],
+        "cmbl_clbins_create": [vp, pd, ci, pd, ctypes.c_size_t, ctypes.POINTER(vp)],
+        "cmbl_clbins_destroy": [vp],
+        "cmbl_clbins_info_host": [vp, ci, pd, ctypes.c_size_t],
+        "cmbl_get_cl": [vp, vp, ci, vp, vp, ci, ci, ctypes.POINTER(ci), ci, ci, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(lib, name)

@@ -37,6 +37,7 @@ extern "C" {
 typedef struct cmbl_ctx cmbl_ctx;
 typedef struct cmbl_flow cmbl_flow;
 typedef struct cmbl_dataset cmbl_dataset;
+typedef struct cmbl_clbins cmbl_clbins;
 
 enum { CMBL_OK = 0, CMBL_ERR_ARG = 1, CMBL_ERR_SHAPE = 2, CMBL_ERR_HIP = 3, CMBL_ERR_NAN = 4,
        CMBL_ERR_STATE = 5, CMBL_ERR_ALLOC = 6 };
@@ -172,6 +173,37 @@ int cmbl_ud_grade(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv_pixwin, int
 /* pixwin(θpix, ℓ) (src/proj_lambert.jl:200) on the context's half plane: sinc(ly Δx / 2π) * sinc(lx Δx / 2π) = sinc(ky / Ny) * sinc(kx / Nx),
  * real (Ny/2+1, Nx) plane in the reference layout, host, double; n = (Ny/2+1) * Nx. */
 int cmbl_pixwin_host(cmbl_ctx* ctx, double* out_host, size_t n);
+
+/* ---- get_Cℓ(f1, f2 = f1; Δℓ, ℓedges, Cℓfid, err_estimate) (src/proj_lambert.jl:470-513; get_Dℓ, get_ℓ⁴Cℓ, get_ρℓ of src/cls.jl:85-97 and cov_to_Cℓ,
+ *      :415-419, are host arithmetic on its result): binned auto- and cross-power spectra on the device.  Per mode of the FULL plane the reference forms
+ *      ℓ = ℓmag, CL = Re(conj(f1) f2) / α with α = Nx Ny / Δx², and w = nan2zero((2 Cℓfid(ℓ)² / (2ℓ+1))⁻¹); keeps the modes with
+ *      min(ℓedges) < ℓ < max(ℓedges) (BOTH strict, :476); histograms them into the left-closed bins [e_i, e_i+1) and returns, per bin,
+ *      ℓ = Sℓ / A and Cℓ = S1 / A with A = Σ w, Sℓ = Σ w ℓ, S1 = Σ w CL and, for err_estimate, N = (Σ 1) / 2 and S2 = Σ w CL².
+ *      ℓ and CL are equal at a mode and at its Hermitian mirror, so each sum is the HALF-plane sum weighted by λ (1 on ky = 0 and on the Nyquist row of an
+ *      even Ny, 2 elsewhere; `unfold`, src/util_fft.jl:83-97, which for odd Nx indexes one past the row -- the mirror it intends is what is computed).
+ *      A, Sℓ and the counts depend on the grid, the edges and the weight only: they are made ONCE with the binning plan, on the host, in double.
+ *   cmbl_clbins_create: `ledges_host`: nedges doubles, 2 <= nedges <= 65536, finite and strictly increasing (else CMBL_ERR_ARG).  `w_host`: the per-mode
+ *      weight w on the half plane, real (Ny/2+1, Nx) plane in the reference layout, nw = (Ny/2+1) * Nx finite doubles (another nw: CMBL_ERR_SHAPE; a
+ *      non-finite value: CMBL_ERR_ARG), or NULL (nw ignored) for Cℓfid = 1, w = (2ℓ+1)/2.  Bin membership is decided here, in double, by comparing the
+ *      numbers cmbl_ctx_geometry_host(which = 5) returns with the edges -- the reference compares a working-precision ℓmag, which in single precision
+ *      moves a few modes per megapixel across an edge.  The plan belongs to the geometry of `ctx`: used with a context of another size, pixel size or
+ *      layout it returns CMBL_ERR_SHAPE, of another precision or device CMBL_ERR_ARG.  It may outlive the context.
+ *   cmbl_clbins_info_host: per bin (n = nedges - 1, else CMBL_ERR_SHAPE) A, Sℓ, or the number of full-plane modes Σ λ (N is half of it).
+ *   cmbl_get_cl: `f1`, `f2` (NULL: f2 = f1): device fields of npol planes per batch slot in `basis`, ABI layouts.  CMBL_MAP fields are transformed into the
+ *      context's scratch first; complex fields are read where they lie, and CMBL_FOURIER / CMBL_HARMONIC only say what the planes mean to the caller.
+ *      `pairs_host`: npairs (1 ... 9, else CMBL_ERR_ARG) index pairs (a, b) into the npol planes OF THAT BASIS: plane a of f1 against plane b of f2 (an
+ *      index outside [0, npol): CMBL_ERR_ARG).  `moments`: 1 (S1) or 2 (S1 and S2), else CMBL_ERR_ARG.  nbatch <= 256.
+ *      `out`: DEVICE doubles [nbatch][npairs][moments][nedges - 1], S1 = Σ λ w CL and S2 = Σ λ w CL², written asynchronously on the context's stream
+ *      (empty bins hold 0; the caller divides by A).  All pairs come out of one pass over the fields.  Accumulation is in double in either precision and
+ *      deterministic (fixed summation order, no atomics): equal calls give bit-identical output, and a batch slot's numbers do not depend on the others.
+ *      err_estimate: the reference's line :498 forms S2/A − S1² with the un-normalised S1 (negative for any populated bin with A > 1, so its sqrt throws);
+ *      the evident intent is σℓ = sqrt((S2/A − (S1/A)²) / N), which the Python layer returns. */
+enum { CMBL_CL_A = 0, CMBL_CL_SL = 1, CMBL_CL_COUNT = 2 };
+int cmbl_clbins_create(cmbl_ctx* ctx, const double* ledges_host, int nedges, const double* w_host, size_t nw, cmbl_clbins** out);
+int cmbl_clbins_destroy(cmbl_clbins* bins);
+int cmbl_clbins_info_host(cmbl_clbins* bins, int which, double* out_host, size_t n);
+int cmbl_get_cl(cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, const void* f2, int npol, int nbatch,
+                const int* pairs_host, int npairs, int moments, double* out);
 
 /* ---- diagonal operators: DiagOp `*` and `\` with automatic basis conversion, BlockDiagIEB
  *      (src/specialops.jl:9-10, 61-118; src/field_vectors.jl:64-66).

@@ -413,6 +413,74 @@ function CMBLensing.ud_grade(f::BaseField{B,<:ProjLambert,<:Any,<:ROCArray}, θn
 end
 basis_of(::BaseField{B}) where {B} = B
 
+# `get_Cℓ` (src/proj_lambert.jl:470-513) for device-backed flat-sky fields: the binned sums S1 = Σ w·CL (and S2 with `err_estimate`) come from ONE
+# `cmbl_get_cl` call per basis instead of `adapt(Array, f)` and a host histogram; A, Sℓ and the mode counts come from the binning plan, made once
+# per (ProjLambert, ℓedges, weight plane) on the host in double (include/cmblens.h has the semantics: λ-weighted half plane, bins decided on the
+# context's ℓmag in double, σℓ as evidently intended).  Keywords, defaults and the shape of the result are the reference's.
+mutable struct HIPClBins
+    h :: Ptr{Cvoid}
+    A :: Vector{Float64}; Sℓ :: Vector{Float64}; count :: Vector{Float64}
+end
+const clbins = Dict{Any,HIPClBins}()
+function hip_clbins(proj::ProjLambert, ℓedges, Cℓfid)
+    edges = collect(Float64, ℓedges)
+    w = nothing
+    if Cℓfid !== nothing
+        L = Float64.(permutedims(CMBLensing.cpu(proj.ℓmag)))                                     # (Nx, Ny÷2+1) row-major == the ABI plane
+        w = vec(nan2zero.(inv.(2 .* Cℓfid.(L) .^ 2 ./ (2 .* L .+ 1))))
+    end
+    get!(clbins, (objectid(proj), edges, w)) do
+        h = Ref{Ptr{Cvoid}}()
+        chk(ccall((:cmbl_clbins_create, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Csize_t, Ptr{Ptr{Cvoid}}),
+                  hip_ctx(proj).h, edges, length(edges), w === nothing ? C_NULL : w, w === nothing ? 0 : length(w), h))
+        info = map(0:2) do which
+            out = Vector{Float64}(undef, length(edges) - 1)
+            chk(ccall((:cmbl_clbins_info_host, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Csize_t), h[], which, out, length(out)))
+            out
+        end
+        finalizer(b -> ccall((:cmbl_clbins_destroy, lib), Cint, (Ptr{Cvoid},), b.h), HIPClBins(h[], info...))
+    end
+end
+cl_plane(f::BaseField, x::Char) = npol(f) == 1 ? 0 : (x == 'I' ? 0 : (x in ('Q', 'E') ? 0 : 1) + (npol(f) == 3 ? 1 : 0))
+# the binned sums of the letter pairs `names`, all of ONE basis: (nbins, moments, npairs, batch)
+function cl_sums(f1::BaseField, f2::BaseField, names, bins::HIPClBins, moments)
+    ctx = hip_ctx(f1.metadata)
+    pairs = Cint[cl_plane(f1, c) for n in names for c in n]
+    a, b = f1.arr, f2.arr
+    out = similar(a, Float64, (length(bins.A), moments, length(names), nbatch(f1)))
+    GC.@preserve a b out chk(ccall((:cmbl_get_cl, lib), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Cint}, Cint, Cint, Ptr{Cvoid}),
+              ctx.h, bins.h, basis_tag(f1), devptr(a), f2 === f1 ? C_NULL : devptr(b), npol(f1), nbatch(f1), pairs, length(names), moments, devptr(out)))
+    keepalive(ctx, a, b)
+    Array(out)                                                                                   # synchronises
+end
+function CMBLensing.get_Cℓ(f₁::BaseField{B1,<:ProjLambert,<:Any,<:ROCArray}, f₂::BaseField{B2,<:ProjLambert,<:Any,<:ROCArray}=f₁;
+                           Δℓ=50, ℓedges=0:Δℓ:16000, Cℓfid=nothing, err_estimate=false,
+                           which=(npol(f₁) == 1 ? :II : npol(f₁) == 2 ? (:EE,:BB) : (:II,:EE,:BB,:IE,:IB,:EB))) where {B1,B2}
+    names = string.(CMBLensing.ensure1d(which))
+    bins = hip_clbins(f₁.metadata, ℓedges, Cℓfid)
+    moments = err_estimate ? 2 : 1
+    isqu(n) = any(in("QU"), n)
+    S = Array{Float64}(undef, length(bins.A), moments, length(names), nbatch(f₁))
+    for (sel, conv) in ((isqu, f -> basis_tag(f) == HARMONIC ? Ð(f) : f), (!isqu, f -> npol(f) == 1 ? f : harm(f)))
+        ks = findall(sel, names)
+        isempty(ks) && continue
+        g₁ = conv(f₁); g₂ = f₂ === f₁ ? g₁ : conv(f₂)
+        basis_tag(g₁) == basis_tag(g₂) || ((g₁, g₂) = (Fourier(g₁), Fourier(g₂)))
+        S[:, :, ks, :] = cl_sums(g₁, g₂, names[ks], bins, moments)
+    end
+    one(k, b) = begin
+        Cℓ = S[:, 1, k, b] ./ bins.A
+        err_estimate || return Cℓs(bins.Sℓ ./ bins.A, Cℓ)
+        σℓ = sqrt.(max.(S[:, 2, k, b] ./ bins.A .- Cℓ .^ 2, 0) ./ (bins.count ./ 2))
+        Cℓs(bins.Sℓ ./ bins.A, Cℓ .± σℓ)
+    end
+    res = map(1:nbatch(f₁)) do b
+        which isa Symbol ? one(1, b) : (; (Symbol(n) => one(k, b) for (k, n) in enumerate(names))...)
+    end
+    nbatch(f₁) == 1 ? res[1] : res
+end
+
 # device RNG for `simulate` / `randn!` (src/specialops.jl:6, src/base_fields.jl:169-170): counter-based Philox4x32-10
 mutable struct HIPPhilox <: Random.AbstractRNG
     seed   :: UInt64
