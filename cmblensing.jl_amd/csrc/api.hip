@@ -3,6 +3,7 @@
 #include "api_decl.hpp"
 #include "engine_ud.hpp"
 #include "engine_cl.hpp"
+#include "engine_bilinear.hpp"
 
 namespace cmbl { thread_local std::string g_last_error; }
 using namespace cmbl;
@@ -436,6 +437,44 @@ int cmbl_get_cl(cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, con
       pr.a[k] = (signed char)a; pr.b[k] = (signed char)b;
     }
     BY_DTYPE(ctx, do_get_cl<float>(ctx, bins, basis, f1, f2, P, B, pr, moments, out), do_get_cl<double>(ctx, bins, basis, f1, f2, P, B, pr, moments, out));
+  });
+}
+
+// ---- BilinearLens (src/bilinearlens.jl) ------------------------------------------------------------------------------
+int cmbl_bilinear_create(cmbl_ctx* ctx, cmbl_bilinear** out) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(out);
+    auto h = std::make_unique<cmbl_bilinear>();
+    h->ctx = ctx;
+    BY_DTYPE(ctx, do_bl_create<float>(h.get()), do_bl_create<double>(h.get()));
+    *out = h.release();
+  });
+}
+int cmbl_bilinear_destroy(cmbl_bilinear* L) { return guard([&] { delete L; }); }
+int cmbl_bilinear_set_phi(cmbl_bilinear* L, int basis, const void* phi, int nb) {
+  return guard([&] {
+    NOTNULL(L); NOTNULL(phi); BASIS_OK(basis); CMBL_REQUIRE(nb >= 1, ERR_SHAPE, "nbatch_phi >= 1");
+    BY_DTYPE(L->ctx, do_bl_set_phi<float>(L, basis, phi, nb), do_bl_set_phi<double>(L, basis, phi, nb));
+  });
+}
+int cmbl_bilinear_set_deflection(cmbl_bilinear* L, const void* dy_px, const void* dx_px) {
+  return guard([&] {
+    NOTNULL(L); NOTNULL(dy_px); NOTNULL(dx_px);
+    BY_DTYPE(L->ctx, do_bl_set_deflection<float>(L, dy_px, dx_px), do_bl_set_deflection<double>(L, dy_px, dx_px));
+  });
+}
+int cmbl_bilinear_apply(cmbl_bilinear* L, int mode, int bi, const void* in, int bo, void* out, int P, int B, int maxiter) {
+  return guard([&] {
+    NOTNULL(L); NOTNULL(in); NOTNULL(out); BASIS_OK(bi); BASIS_OK(bo); POLB_OK(P, B);
+    CMBL_REQUIRE(mode >= 0 && mode <= 3, ERR_ARG, "bad flow mode");
+    CMBL_REQUIRE(maxiter >= 1 && maxiter <= BL_MAXIT, ERR_ARG, "maxiter must lie in [1, 16]");
+    BY_DTYPE(L->ctx, do_bl_apply<float>(L, mode, bi, in, bo, out, P, B, maxiter), do_bl_apply<double>(L, mode, bi, in, bo, out, P, B, maxiter));
+  });
+}
+int cmbl_bilinear_grad(cmbl_bilinear* L, const void* f_lensed, int bdel, const void* delta, void* dphi, int bdf, void* df, int P, int B) {
+  return guard([&] {
+    NOTNULL(L); NOTNULL(f_lensed); NOTNULL(delta); NOTNULL(dphi); NOTNULL(df); BASIS_OK(bdel); BASIS_OK(bdf); POLB_OK(P, B);
+    BY_DTYPE(L->ctx, do_bl_grad<float>(L, f_lensed, bdel, delta, dphi, bdf, df, P, B), do_bl_grad<double>(L, f_lensed, bdel, delta, dphi, bdf, df, P, B));
   });
 }
 

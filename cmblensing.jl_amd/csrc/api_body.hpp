@@ -3,6 +3,7 @@
 #include "api_decl.hpp"
 #include "engine_ud.hpp"
 #include "engine_cl.hpp"
+#include "engine_bilinear.hpp"
 
 namespace cmbl {
 
@@ -235,6 +236,16 @@ template <typename T> void do_ud_grade(cmbl_ctx* src, cmbl_ctx* dst, int mode, i
 }
 template <typename T> void do_get_cl(cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, const void* f2, int P, int B, const ClPairs& pr, int moments, double* out) {
   get_cl<T>(C<T>(ctx), *bins->p, basis, f1, f2, P, B, pr, moments, out);
+}
+template <typename T> std::unique_ptr<Bilinear<T>>& bl_of(cmbl_bilinear* L) { if constexpr (sizeof(T) == 4) return L->f32; else return L->f64; }
+template <typename T> void do_bl_create(cmbl_bilinear* h) { bl_of<T>(h) = std::make_unique<Bilinear<T>>(C<T>(h->ctx)); }
+template <typename T> void do_bl_set_phi(cmbl_bilinear* L, int basis, const void* phi, int nb) { bl_of<T>(L)->set_phi(basis, phi, nb); }
+template <typename T> void do_bl_set_deflection(cmbl_bilinear* L, const void* dy_px, const void* dx_px) { bl_of<T>(L)->set_deflection(dy_px, dx_px); }
+template <typename T> void do_bl_apply(cmbl_bilinear* L, int mode, int bi, const void* in, int bo, void* out, int P, int B, int maxiter) {
+  bl_of<T>(L)->apply(mode, bi, in, bo, out, P, B, maxiter);
+}
+template <typename T> void do_bl_grad(cmbl_bilinear* L, const void* f_lensed, int bdel, const void* delta, void* dphi, int bdf, void* df, int P, int B) {
+  bl_of<T>(L)->grad(f_lensed, bdel, delta, dphi, bdf, df, P, B);
 }
 
 }  // namespace cmbl

@@ -1,7 +1,7 @@
 // What api.hip (the entry points) and the per-precision translation units share: the handle structs and the DECLARATIONS of the typed
 // bodies behind the entry points.  The build is split by explicit instantiation (lib.py builds the objects in parallel):
 //   api.hip                 extern "C" entry points, argument checks, error plumbing -- instantiates NO kernel
-//   tu_main_{f32,f64}.hip   every do_*<T> below (api_body.hpp) and with them Ctx<T>, Flow<T>, Dataset<T>, Drivers<T> and their kernels
+//   tu_main_{f32,f64}.hip   every do_*<T> below (api_body.hpp) and with them Ctx<T>, Flow<T>, Bilinear<T>, Dataset<T>, Drivers<T> and their kernels
 //   tu_gen_{f32,f64}.hip    the host side of the any-size transform launches (engine_gen.hpp) and the run-time-plan kernels k_gen_dft*
 //   tu_cty_{f32,f64}_{a,b}.hip   the compile-time-plan kernels of the column side and the plain transforms (engine_ct.hpp CtLaunchY: k_ct_dft,
 //                           k_ct_dftx, k_ct_flow_y, k_ct_delta_y, k_ct_adj_y), lengths of CMBL_CT_LIST_A / _B (kernels_ct.hpp)
@@ -14,11 +14,13 @@
 #include "engine.hpp"
 #include "drivers.hpp"
 #include "engine_cl.hpp"
+#include "engine_bilinear.hpp"
 #include "../../include/cmblens.h"
 
 struct cmbl_ctx { std::unique_ptr<cmbl::CtxBase> p; };
 struct cmbl_clbins { std::unique_ptr<cmbl::ClBins> p; };
 struct cmbl_flow { cmbl_ctx* ctx; std::unique_ptr<cmbl::Flow<float>> f32; std::unique_ptr<cmbl::Flow<double>> f64; };
+struct cmbl_bilinear { cmbl_ctx* ctx; std::unique_ptr<cmbl::Bilinear<float>> f32; std::unique_ptr<cmbl::Bilinear<double>> f64; };
 struct cmbl_dataset {
   cmbl_ctx* ctx; std::unique_ptr<cmbl::Dataset<float>> f32; std::unique_ptr<cmbl::Dataset<double>> f64;
   std::map<const void*, std::unique_ptr<cmbl::Drivers<float>>> drv32;        // driver scratch per (dataset, flow) pair
@@ -54,6 +56,11 @@ template <typename T> void do_dataset_set_op(cmbl_dataset* ds, int which, const 
 template <typename T> void do_dataset_set_data(cmbl_dataset* ds, const void* d, int B);
 template <typename T> void do_ud_grade(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv, int aa, int bi, const void* in, int bo, void* out, int P, int B);
 template <typename T> void do_get_cl(cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, const void* f2, int P, int B, const ClPairs& pr, int moments, double* out);
+template <typename T> void do_bl_create(cmbl_bilinear* h);
+template <typename T> void do_bl_set_phi(cmbl_bilinear* L, int basis, const void* phi, int nb);
+template <typename T> void do_bl_set_deflection(cmbl_bilinear* L, const void* dy_px, const void* dx_px);
+template <typename T> void do_bl_apply(cmbl_bilinear* L, int mode, int bi, const void* in, int bo, void* out, int P, int B, int maxiter);
+template <typename T> void do_bl_grad(cmbl_bilinear* L, const void* f_lensed, int bdel, const void* delta, void* dphi, int bdf, void* df, int P, int B);
 
 #define CMBL_INSTANTIATE_API(T) \
   template void do_convert<T>(cmbl_ctx* ctx, int bi, const void* in, int bo, void* out, int P, int B); \
@@ -82,5 +89,10 @@ template <typename T> void do_get_cl(cmbl_ctx* ctx, cmbl_clbins* bins, int basis
   template void do_dataset_set_op<T>(cmbl_dataset* ds, int which, const void* planes, int nplanes); \
   template void do_dataset_set_data<T>(cmbl_dataset* ds, const void* d, int B); \
   template void do_ud_grade<T>(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv, int aa, int bi, const void* in, int bo, void* out, int P, int B); \
+  template void do_bl_create<T>(cmbl_bilinear* h); \
+  template void do_bl_set_phi<T>(cmbl_bilinear* L, int basis, const void* phi, int nb); \
+  template void do_bl_set_deflection<T>(cmbl_bilinear* L, const void* dy_px, const void* dx_px); \
+  template void do_bl_apply<T>(cmbl_bilinear* L, int mode, int bi, const void* in, int bo, void* out, int P, int B, int maxiter); \
+  template void do_bl_grad<T>(cmbl_bilinear* L, const void* f_lensed, int bdel, const void* delta, void* dphi, int bdf, void* df, int P, int B); \
   template void do_get_cl<T>(cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, const void* f2, int P, int B, const ClPairs& pr, int moments, double* out);
 }  // namespace cmbl

@@ -612,6 +612,87 @@ class LenseFlow:
         return Field(self.proj, dphi, FOURIER), Field(self.proj, df, basis_df), Field(self.proj, fstart, MAP)
 
 
+class _BilinearAdjoint:
+    def __init__(self, L):
+        self.L = L
+
+    def __mul__(self, g):            # L' * g
+        return self.L._apply(FLOW_ADJ, g)
+
+    def ldiv(self, g, maxiter=5):    # L' \\ g
+        return self.L._apply(FLOW_INVADJ, g, maxiter=maxiter)
+
+
+class BilinearLens:
+    """`BilinearLens(ϕ)` (src/bilinearlens.jl): lensing by bilinear interpolation, with the surface of `LenseFlow`.  `L(ϕ)` rebuilds the
+    interpolation table only when ϕ is a different object; one ϕ serves any number of batch slots of f (a batched ϕ raises, :40)."""
+
+    def __init__(self, proj):
+        self.proj = proj
+        self.lib = proj.lib
+        self._h = ctypes.c_void_p()
+        check(self.lib.cmbl_bilinear_create(proj._h, ctypes.byref(self._h)))
+        self._phi = None
+
+    def __del__(self):
+        try:
+            if self._h:
+                self.lib.cmbl_bilinear_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def __call__(self, phi):
+        """phi: Field (any basis, P=1, B=1)."""
+        if self._phi is not phi:
+            P, B = self.proj._check(phi.arr, phi.basis)
+            assert P == 1
+            check(self.lib.cmbl_bilinear_set_phi(self._h, phi.basis, _ptr(phi.arr), B))
+            self._phi = phi
+        return self
+
+    def set_deflection(self, dy, dx):
+        """Lensing by a given displacement: pixel (i, j) reads (i + dy, j + dx), `dy` along Ny and `dx` along Nx in pixels, maps of shape (Nx, Ny)."""
+        dy, dx = (self.proj.tensor(a).reshape(1, 1, self.proj.Nx, self.proj.Ny) for a in (dy, dx))
+        self.proj._check(dy, MAP), self.proj._check(dx, MAP)
+        check(self.lib.cmbl_bilinear_set_deflection(self._h, _ptr(dy), _ptr(dx)))
+        self._phi = None
+        return self
+
+    def invalidate(self):
+        self._phi = None
+
+    @property
+    def phi(self):
+        return self._phi
+
+    def _apply(self, mode, f, basis_out=MAP, maxiter=5):
+        P, B = self.proj._check(f.arr, f.basis)
+        out = self.proj.empty(basis_out, P, B)                          # the reference returns Ł fields from all four (:109-114)
+        check(self.lib.cmbl_bilinear_apply(self._h, mode, f.basis, _ptr(f.arr), basis_out, _ptr(out), P, B, int(maxiter)))
+        return Field(self.proj, out, basis_out)
+
+    def __mul__(self, f):            # L * f
+        return self._apply(FLOW_FWD, f)
+
+    def ldiv(self, f, maxiter=5):    # L \\ f
+        return self._apply(FLOW_INV, f, maxiter=maxiter)
+
+    @property
+    def adjoint(self):
+        return _BilinearAdjoint(self)
+
+    def gradient(self, f_lensed, delta, basis_df=None):
+        """Pullback of `L*f` (src/bilinearlens.jl:165-171).  f_lensed: the primal output (map Field); delta: cotangent.  Returns (δϕ [FOURIER], δf)."""
+        P, B = self.proj._check(f_lensed.arr, MAP)
+        self.proj._check(delta.arr, delta.basis)
+        basis_df = delta.basis if basis_df is None else basis_df
+        dphi = self.proj.empty(FOURIER, 1, B)
+        df = self.proj.empty(basis_df, P, B)
+        check(self.lib.cmbl_bilinear_grad(self._h, _ptr(f_lensed.arr), delta.basis, _ptr(delta.arr), _ptr(dphi), basis_df, _ptr(df), P, B))
+        return Field(self.proj, dphi, FOURIER), Field(self.proj, df, basis_df)
+
+
 class BaseDataSet:
     """`BaseDataSet` at fiducial θ (src/dataset.jl:37-57) with the operators resident on the device.
 

@@ -18,6 +18,7 @@ SYMBOLS = [
     "cmbl_hmc_step", "cmbl_map_joint_step", "cmbl_quadratic_estimate", "cmbl_norm", "cmbl_logdet_diag", "cmbl_tr_diag", "cmbl_set_sum_accuracy_mode",
     "cmbl_timer_report", "cmbl_device_malloc", "cmbl_device_free", "cmbl_copy_to_device", "cmbl_copy_to_host",
     "cmbl_ud_grade", "cmbl_pixwin_host", "cmbl_clbins_create", "cmbl_clbins_destroy", "cmbl_clbins_info_host", "cmbl_get_cl",
+    "cmbl_bilinear_create", "cmbl_bilinear_destroy", "cmbl_bilinear_set_phi", "cmbl_bilinear_set_deflection", "cmbl_bilinear_apply", "cmbl_bilinear_grad",
 ]
 
 
@@ -188,6 +189,12 @@ def load_library():
         "cmbl_clbins_destroy": [vp],
         "cmbl_clbins_info_host": [vp, ci, pd, ctypes.c_size_t],
         "cmbl_get_cl": [vp, vp, ci, vp, vp, ci, ci, ctypes.POINTER(ci), ci, ci, vp],
+        "cmbl_bilinear_create": [vp, ctypes.POINTER(vp)],
+        "cmbl_bilinear_destroy": [vp],
+        "cmbl_bilinear_set_phi": [vp, ci, vp, ci],
+        "cmbl_bilinear_set_deflection": [vp, vp, vp],
+        "cmbl_bilinear_apply": [vp, ci, ci, vp, ci, vp, ci, ci, ci],
+        "cmbl_bilinear_grad": [vp, vp, ci, vp, vp, ci, vp, ci, ci],
     }
     for name, argtypes in sig.items():
         fn = getattr(lib, name)

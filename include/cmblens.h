@@ -38,6 +38,7 @@ typedef struct cmbl_ctx cmbl_ctx;
 typedef struct cmbl_flow cmbl_flow;
 typedef struct cmbl_dataset cmbl_dataset;
 typedef struct cmbl_clbins cmbl_clbins;
+typedef struct cmbl_bilinear cmbl_bilinear;
 
 enum { CMBL_OK = 0, CMBL_ERR_ARG = 1, CMBL_ERR_SHAPE = 2, CMBL_ERR_HIP = 3, CMBL_ERR_NAN = 4,
        CMBL_ERR_STATE = 5, CMBL_ERR_ALLOC = 6 };
@@ -259,6 +260,31 @@ int cmbl_lenseflow_grad(cmbl_flow* L, int mode, const void* f_end, int basis_del
 /* get_max_lensing_step(phi, eta) (src/lenseflow.jl:242-256): largest alpha keeping I + grad grad(phi + alpha eta)
  * non-singular, one value per batch slot. */
 int cmbl_max_lensing_step(cmbl_flow* L, int basis, const void* phi, const void* eta, int nbatch, double* out_host);
+
+/* ---- BilinearLens: lensing by bilinear interpolation (src/bilinearlens.jl) with the reference's gmres (src/numerical_algorithms.jl:193-214).
+ * One phi, any number of (pol, batch) slices of f; pixel (i, j) -- i along Ny, j along Nx -- reads its four neighbours at
+ * (i + d_y phi / dx, j + d_x phi / dx), wrapped periodically, with the closed-form bilinear weights (:42-74).  The pixel index is added in integers
+ * after floor and fraction are taken from the deflection alone (the reference adds 1:Ny in the working precision, :44-45).
+ *   cmbl_bilinear_create / _destroy: BilinearLens (:24-28) on a context.
+ *   cmbl_bilinear_set_phi: BilinearLens(phi) (:31-87).  nbatch_phi != 1 is CMBL_ERR_SHAPE (:40).  norm(phi) == 0 makes every action a copy (:34).
+ *        The tables of BilinearLens(-phi) (:92-97) and the transposed operators are made on first use and kept until the next set_phi.
+ *   cmbl_bilinear_set_deflection: the same operator from two device MAPs (Nx x Ny reals each, the context's precision) of the deflection in
+ *        PIXELS along Ny (dy_px) and along Nx (dx_px) -- lensing by an arbitrary displacement (compute_row!, :55-74, on given positions).
+ *   cmbl_bilinear_apply: mode CMBL_FLOW_FWD L*f (:107-115), _ADJ L'*f (:117-125; summed in a fixed order: bit-identical between runs), _INV L\f
+ *        (:127-138) and _INVADJ L'\f (:140-151): per slice gmres(A, b, Pl = BilinearLens(-phi), maxiter), formed as Arnoldi with modified
+ *        Gram-Schmidt; 1 <= maxiter <= 16 (the reference uses 5), ignored by the other modes.  Fields in any basis, ABI
+ *        layouts; the work is done on maps (:109).  Before any set_phi / set_deflection: CMBL_ERR_STATE, as cmbl_lenseflow_apply.
+ *   cmbl_bilinear_grad: the pullback of L*f (:165-171) from the primal output f_lensed (MAP) and the cotangent delta (basis_delta):
+ *        df_out = L' delta in basis_df, dphi_out = grad' . (sum_pol delta * grad f_lensed) (FOURIER, (Ny/2+1, Nx, 1, nbatch)), with the spectral
+ *        gradient of f_lensed as in the reference. */
+int cmbl_bilinear_create(cmbl_ctx* ctx, cmbl_bilinear** out);
+int cmbl_bilinear_destroy(cmbl_bilinear* L);
+int cmbl_bilinear_set_phi(cmbl_bilinear* L, int basis, const void* phi, int nbatch_phi);
+int cmbl_bilinear_set_deflection(cmbl_bilinear* L, const void* dy_px, const void* dx_px);
+int cmbl_bilinear_apply(cmbl_bilinear* L, int mode, int basis_in, const void* in, int basis_out, void* out,
+                        int npol, int nbatch, int maxiter);
+int cmbl_bilinear_grad(cmbl_bilinear* L, const void* f_lensed, int basis_delta, const void* delta,
+                       void* dphi_out, int basis_df, void* df_out, int npol, int nbatch);
 
 /* ---- small helpers used by the drivers above the hot kernels
  * axpby: out = a[b]*x + b[b]*y per batch slot (y may be NULL) -- the FieldTuple / Field broadcasts of the CG, line-search

@@ -26,7 +26,7 @@
 module CMBLensingHIPExt
 
 using CMBLensing, AMDGPU, Adapt, LinearAlgebra, Random, Zygote
-using CMBLensing: FlowOpWithAdjoint, BaseDataSet, DataSet, Mixed, Field, BaseField, ProjLambert, Map, Fourier, EBFourier, IEBFourier,
+using CMBLensing: FlowOpWithAdjoint, ImplicitOp, BaseDataSet, DataSet, Mixed, Field, BaseField, ProjLambert, Map, Fourier, EBFourier, IEBFourier,
                   QUFourier, IQUFourier, Ł, Ð, BlockDiagIEB, LazyBinaryOp, FieldTuple, batch_length, batch, unbatch, nan2zero, diag
 import CMBLensing: precompute!!, getϕ, gradientf_logpdf, argmaxf_logpdf, logpdf
 import Base: *, \, adjoint
@@ -208,6 +208,69 @@ Zygote.@adjoint function \(Lϕ::HIPLenseFlow, f̃::Field{B}) where {B}
 end
 # `L(ϕ)` inside a differentiated function: the cotangent of the operator is the cotangent of ϕ (src/flowops.jl:18-19)
 Zygote.@adjoint (Lϕ::HIPLenseFlow)(ϕ′) = Lϕ(ϕ′), Δ -> (nothing, Δ)
+
+# ---- 2b. BilinearLens (src/bilinearlens.jl) ------------------------------------------------------------------------------------
+# the reference's second lensing operator: one ϕ (a batched ϕ errors like upstream, :40), `*`, `\`, `'` and the pullback of `*`;
+# `load_sim(L = HIPBilinearLens)` takes it where upstream takes `BilinearLens`
+mutable struct HIPBilinearLens{T} <: ImplicitOp{T}
+    ϕ      :: Field
+    ctx    :: HIPContext
+    h      :: Ptr{Cvoid}
+    cached :: Any                       # the ϕ object the device tables were built from
+    maxiter :: Int                      # gmres iterations of `\` (:134, 147)
+end
+function HIPBilinearLens(ϕ::Field; maxiter::Int=5)
+    T = real(eltype(ϕ))
+    ctx = hip_ctx(ϕ.metadata)
+    h = Ref{Ptr{Cvoid}}()
+    chk(ccall((:cmbl_bilinear_create, lib), Cint, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}), ctx.h, h))
+    L = HIPBilinearLens{T}(ϕ, ctx, h[], nothing, maxiter)
+    finalizer(L -> ccall((:cmbl_bilinear_destroy, lib), Cint, (Ptr{Cvoid},), L.h), L)
+end
+getϕ(L::HIPBilinearLens) = L.ϕ
+(L::HIPBilinearLens)(ϕ::Field) = (L.ϕ === ϕ) ? L : (L.ϕ = ϕ; L)
+function precompute!!(L::HIPBilinearLens)
+    if L.cached !== L.ϕ
+        ϕ′ = (basis_tag(L.ϕ) == MAP) ? L.ϕ : Fourier(L.ϕ)
+        a = ϕ′.arr
+        GC.@preserve a chk(ccall((:cmbl_bilinear_set_phi, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint),
+                                 L.h, basis_tag(ϕ′), devptr(a), nbatch(ϕ′)))
+        keepalive(L.ctx, a)
+        L.cached = L.ϕ
+    end
+    L
+end
+function bilinear(L::HIPBilinearLens, mode, f::BaseField, out::BaseField)
+    precompute!!(L)
+    a, o = f.arr, out.arr
+    GC.@preserve a o chk(ccall((:cmbl_bilinear_apply, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint, Cint),
+                               L.h, mode, basis_tag(f), devptr(a), basis_tag(out), devptr(o), npol(f), nbatch(f), L.maxiter))
+    keepalive(L.ctx, a)
+    out
+end
+# all four act on and return Ł fields (:107-151)
+*(L::HIPBilinearLens, f::Field) = (g = Ł(f); bilinear(L, FLOW_FWD, g, similar(g)))
+\(L::HIPBilinearLens, f::Field) = (g = Ł(f); bilinear(L, FLOW_INV, g, similar(g)))
+*(L::Adjoint{<:Any,<:HIPBilinearLens}, f::Field) = (g = Ł(f); bilinear(parent(L), FLOW_ADJ, g, similar(g)))
+\(L::Adjoint{<:Any,<:HIPBilinearLens}, f::Field) = (g = Ł(f); bilinear(parent(L), FLOW_INVADJ, g, similar(g)))
+
+# :163-171
+Zygote.@adjoint HIPBilinearLens(ϕ) = HIPBilinearLens(ϕ), Δ -> (Δ,)
+Zygote.@adjoint function *(Lϕ::HIPBilinearLens, f::Field{B}) where {B}
+    f̃ = Lϕ * f
+    function back(Δ)
+        precompute!!(Lϕ)
+        Δm = Ł(Δ)
+        δf, δϕ = similar(Δm), similar_ϕ(Lϕ.ϕ, f̃)
+        a, b, c, d = f̃.arr, Δm.arr, δϕ.arr, δf.arr
+        GC.@preserve a b c d chk(ccall((:cmbl_bilinear_grad, lib), Cint,
+                  (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint),
+                  Lϕ.h, devptr(a), basis_tag(Δm), devptr(b), devptr(c), basis_tag(δf), devptr(d), npol(f̃), nbatch(f̃)))
+        keepalive(Lϕ.ctx, a, b)
+        δϕ, B(δf)
+    end
+    f̃, back
+end
 
 # ---- 3. data model, Wiener filter, mixed posterior ------------------------------------------------------------------------
 # include/cmblens.h: CMBL_OP_*
