@@ -1,9 +1,7 @@
-// C ABI of libcmblens_hip.so (see include/cmblens.h): entry points, argument checks and error plumbing.  No kernel is instantiated in this
-// translation unit -- the typed bodies do_*<T> live in api_body.hpp and are compiled by tu_main_{f32,f64}.hip (api_decl.hpp has the map).
+// C ABI of libcmblens_hip.so (see include/cmblens.h): entry points, argument checks and error plumbing.  No kernel and no typed class is
+// instantiated in this translation unit: an entry point calls a virtual member of the precision-free object its handle owns, or BY_DTYPE(ctx,
+// do_x, args...) for a typed body of api_body.hpp, which tu_main_{f32,f64}.hip compile (api_decl.hpp has the map and the list of bodies).
 #include "api_decl.hpp"
-#include "engine_ud.hpp"
-#include "engine_cl.hpp"
-#include "engine_bilinear.hpp"
 
 namespace cmbl { thread_local std::string g_last_error; }
 using namespace cmbl;
@@ -15,10 +13,7 @@ static std::mutex g_ds_mtx;
 static std::vector<cmbl_dataset*> g_datasets;
 static void registry_add(cmbl_dataset* d) { std::lock_guard<std::mutex> l(g_ds_mtx); g_datasets.push_back(d); }
 static void registry_remove(cmbl_dataset* d) { std::lock_guard<std::mutex> l(g_ds_mtx); g_datasets.erase(std::remove(g_datasets.begin(), g_datasets.end(), d), g_datasets.end()); }
-static void registry_drop_flow(const void* f32, const void* f64) {
-  std::lock_guard<std::mutex> l(g_ds_mtx);
-  for (cmbl_dataset* d : g_datasets) { if (f32) d->drv32.erase(f32); if (f64) d->drv64.erase(f64); }
-}
+static void registry_drop_flow(const FlowApi* f) { std::lock_guard<std::mutex> l(g_ds_mtx); for (cmbl_dataset* d : g_datasets) d->drv.erase(f); }
 
 template <typename F>
 static int guard(F&& f) {
@@ -30,13 +25,14 @@ static int guard(F&& f) {
 #define NOTNULL(p) CMBL_REQUIRE((p) != nullptr, ERR_ARG, "null pointer argument: " #p)
 #define BASIS_OK(b) CMBL_REQUIRE((b) >= 0 && (b) <= 2, ERR_ARG, "bad basis: " #b)
 #define POLB_OK(P, B) CMBL_REQUIRE((P) >= 1 && (P) <= 3 && (B) >= 1, ERR_SHAPE, "npol must be 1..3 and nbatch >= 1")
-#define BY_DTYPE(ctx, expr32, expr64) do { if ((ctx)->p->dtype == CMBL_F32) { expr32; } else { expr64; } } while (0)
+#define SAME_CTX(ds, L) CMBL_REQUIRE((ds)->ctx == (L)->ctx, ERR_ARG, "dataset and flow belong to different contexts")
 
 #ifdef CMBL_STAMPS
+#define CMBL_STAMPS_UNITS(X) X(main_f32) X(main_f64) X(gen_f32) X(gen_f64) X(small_f32) X(small_f64) X(cty_f32_a) X(cty_f32_b) X(cty_f64_a) X(cty_f64_b) \
+    X(ctx_f32_a) X(ctx_f32_b) X(ctx_f64_a) X(ctx_f64_b)
 namespace cmbl {
 #define CMBL_X(unit) int stamps_read_##unit(unsigned long long* out_host, int n);
-CMBL_X(main_f32) CMBL_X(main_f64) CMBL_X(gen_f32) CMBL_X(gen_f64) CMBL_X(small_f32) CMBL_X(small_f64) CMBL_X(cty_f32_a) CMBL_X(cty_f32_b) CMBL_X(cty_f64_a) CMBL_X(cty_f64_b) \
-    CMBL_X(ctx_f32_a) CMBL_X(ctx_f32_b) CMBL_X(ctx_f64_a) CMBL_X(ctx_f64_b)
+CMBL_STAMPS_UNITS(CMBL_X)
 #undef CMBL_X
 }
 #endif
@@ -55,8 +51,7 @@ int cmbl_ctx_create(int Ny, int Nx, double theta, int dtype, int device, void* s
     if (e != hipSuccess || ndev == 0) fail(ERR_HIP, "no HIP device available (this library has no CPU fallback)");
     CMBL_REQUIRE(device >= 0 && device < ndev, ERR_ARG, "device index out of range");
     auto h = std::make_unique<cmbl_ctx>();
-    if (dtype == CMBL_F32) h->p.reset(do_ctx_create<float>(Ny, Nx, theta, device, stream));
-    else h->p.reset(do_ctx_create<double>(Ny, Nx, theta, device, stream));
+    BY_DTYPE_CODE(dtype, do_ctx_create, h.get(), Ny, Nx, theta, device, stream);
     *out = h.release();
   });
 }
@@ -144,7 +139,7 @@ int cmbl_ctx_geometry_host(cmbl_ctx* ctx, int which, double* out, size_t n) {
 int cmbl_convert(cmbl_ctx* ctx, int bi, const void* in, int bo, void* out, int P, int B) {
   return guard([&] {
     NOTNULL(ctx); NOTNULL(in); NOTNULL(out); BASIS_OK(bi); BASIS_OK(bo); POLB_OK(P, B);
-    BY_DTYPE(ctx, do_convert<float>(ctx, bi, in, bo, out, P, B), do_convert<double>(ctx, bi, in, bo, out, P, B));
+    BY_DTYPE(ctx, do_convert, ctx, bi, in, bo, out, P, B);
   });
 }
 int cmbl_rfft(cmbl_ctx* ctx, const void* map, void* fourier, int P, int B) { return cmbl_convert(ctx, CMBL_MAP, map, CMBL_FOURIER, fourier, P, B); }
@@ -156,21 +151,20 @@ int cmbl_diag_apply(cmbl_ctx* ctx, int kind, int bd, const void* diag, int bi, c
     NOTNULL(ctx); NOTNULL(diag); NOTNULL(in); NOTNULL(out); BASIS_OK(bi); BASIS_OK(bo); POLB_OK(P, B);
     CMBL_REQUIRE(kind == CMBL_DIAG_MUL || kind == CMBL_DIAG_DIV_NAN2ZERO, ERR_ARG, "kind must be CMBL_DIAG_MUL or CMBL_DIAG_DIV_NAN2ZERO");
     CMBL_REQUIRE(bd == CMBL_FOURIER || bd == CMBL_HARMONIC, ERR_ARG, "operator must be diagonal in FOURIER or HARMONIC");
-    BY_DTYPE(ctx, do_diag<float>(ctx, kind, bd, diag, P, false, bi, in, bo, out, P, B), do_diag<double>(ctx, kind, bd, diag, P, false, bi, in, bo, out, P, B));
+    BY_DTYPE(ctx, do_diag, ctx, kind, bd, diag, P, false, bi, in, bo, out, P, B);
   });
 }
 int cmbl_blockdiag_ieb_apply(cmbl_ctx* ctx, const void* te_bb, int transpose, int bi, const void* in, int bo, void* out, int B) {
   return guard([&] {
     NOTNULL(ctx); NOTNULL(te_bb); NOTNULL(in); NOTNULL(out); BASIS_OK(bi); BASIS_OK(bo); POLB_OK(3, B);
-    BY_DTYPE(ctx, do_diag<float>(ctx, 2, B_HARMONIC, te_bb, 5, transpose != 0, bi, in, bo, out, 3, B),
-             do_diag<double>(ctx, 2, B_HARMONIC, te_bb, 5, transpose != 0, bi, in, bo, out, 3, B));
+    BY_DTYPE(ctx, do_diag, ctx, 2, B_HARMONIC, te_bb, 5, transpose != 0, bi, in, bo, out, 3, B);
   });
 }
 
 int cmbl_dot(cmbl_ctx* ctx, int basis, const void* a, const void* b, int P, int B, double* out) {
   return guard([&] {
     NOTNULL(ctx); NOTNULL(a); NOTNULL(b); NOTNULL(out); BASIS_OK(basis); POLB_OK(P, B);
-    BY_DTYPE(ctx, do_dot<float>(ctx, basis, a, b, P, B, out), do_dot<double>(ctx, basis, a, b, P, B, out));
+    BY_DTYPE(ctx, do_dot, ctx, basis, a, b, P, B, out);
   });
 }
 int cmbl_norm(cmbl_ctx* ctx, int basis, const void* a, int P, int B, double* out) {
@@ -181,13 +175,13 @@ int cmbl_norm(cmbl_ctx* ctx, int basis, const void* a, int P, int B, double* out
 int cmbl_logdet_diag(cmbl_ctx* ctx, int basis, const void* d, int P, int B, double* out) {
   return guard([&] {
     NOTNULL(ctx); NOTNULL(d); NOTNULL(out); BASIS_OK(basis); POLB_OK(P, B);
-    BY_DTYPE(ctx, do_diag_reduce<float>(ctx, 0, basis, d, P, B, out), do_diag_reduce<double>(ctx, 0, basis, d, P, B, out));
+    BY_DTYPE(ctx, do_diag_reduce, ctx, 0, basis, d, P, B, out);
   });
 }
 int cmbl_tr_diag(cmbl_ctx* ctx, int basis, const void* d, int P, int B, double* out) {
   return guard([&] {
     NOTNULL(ctx); NOTNULL(d); NOTNULL(out); BASIS_OK(basis); POLB_OK(P, B);
-    BY_DTYPE(ctx, do_diag_reduce<float>(ctx, 1, basis, d, P, B, out), do_diag_reduce<double>(ctx, 1, basis, d, P, B, out));
+    BY_DTYPE(ctx, do_diag_reduce, ctx, 1, basis, d, P, B, out);
   });
 }
 int cmbl_set_sum_accuracy_mode(cmbl_ctx* ctx, int mode) {
@@ -200,7 +194,7 @@ int cmbl_set_sum_accuracy_mode(cmbl_ctx* ctx, int mode) {
 int cmbl_logdet(cmbl_ctx* ctx, const void* d, int nplanes, double* out) {
   return guard([&] {
     NOTNULL(ctx); NOTNULL(d); NOTNULL(out); CMBL_REQUIRE(nplanes >= 1, ERR_ARG, "nplanes >= 1");
-    BY_DTYPE(ctx, do_logdet<float>(ctx, d, nplanes, out), do_logdet<double>(ctx, d, nplanes, out));
+    BY_DTYPE(ctx, do_logdet, ctx, d, nplanes, out);
   });
 }
 
@@ -210,22 +204,22 @@ int cmbl_lenseflow_create(cmbl_ctx* ctx, int nsteps, cmbl_flow** out) {
     NOTNULL(ctx); NOTNULL(out);
     auto h = std::make_unique<cmbl_flow>();
     h->ctx = ctx;
-    BY_DTYPE(ctx, do_flow_create<float>(h.get(), nsteps), do_flow_create<double>(h.get(), nsteps));
+    BY_DTYPE(ctx, do_flow_create, h.get(), nsteps);
     *out = h.release();
   });
 }
-int cmbl_lenseflow_destroy(cmbl_flow* L) { return guard([&] { if (L) registry_drop_flow(L->f32.get(), L->f64.get()); delete L; }); }
+int cmbl_lenseflow_destroy(cmbl_flow* L) { return guard([&] { if (L) registry_drop_flow(L->p.get()); delete L; }); }
 int cmbl_lenseflow_set_phi(cmbl_flow* L, int basis, const void* phi, int nb) {
   return guard([&] {
     NOTNULL(L); NOTNULL(phi); BASIS_OK(basis); CMBL_REQUIRE(nb >= 1, ERR_SHAPE, "nbatch_phi >= 1");
-    BY_DTYPE(L->ctx, do_flow_set_phi<float>(L, basis, phi, nb), do_flow_set_phi<double>(L, basis, phi, nb));
+    L->p->set_phi(basis, phi, nb);
   });
 }
 int cmbl_lenseflow_apply(cmbl_flow* L, int mode, int bi, const void* in, int bo, void* out, int P, int B) {
   return guard([&] {
     NOTNULL(L); NOTNULL(in); NOTNULL(out); BASIS_OK(bi); BASIS_OK(bo); POLB_OK(P, B);
     CMBL_REQUIRE(mode >= 0 && mode <= 3, ERR_ARG, "bad flow mode");
-    BY_DTYPE(L->ctx, do_flow_apply<float>(L, mode, bi, in, bo, out, P, B), do_flow_apply<double>(L, mode, bi, in, bo, out, P, B));
+    L->p->apply(mode, bi, in, bo, out, P, B);
   });
 }
 int cmbl_lenseflow_grad(cmbl_flow* L, int mode, const void* f_end, int bdel, const void* delta, void* dphi, int bdf, void* df,
@@ -233,15 +227,14 @@ int cmbl_lenseflow_grad(cmbl_flow* L, int mode, const void* f_end, int bdel, con
   return guard([&] {
     NOTNULL(L); NOTNULL(f_end); NOTNULL(delta); NOTNULL(dphi); NOTNULL(df); BASIS_OK(bdel); BASIS_OK(bdf); POLB_OK(P, B);
     CMBL_REQUIRE(mode == CMBL_FLOW_FWD || mode == CMBL_FLOW_INV, ERR_ARG, "grad mode must be CMBL_FLOW_FWD or CMBL_FLOW_INV");
-    BY_DTYPE(L->ctx, do_flow_grad<float>(L, mode, f_end, bdel, delta, dphi, bdf, df, f_start, P, B, quirk),
-             do_flow_grad<double>(L, mode, f_end, bdel, delta, dphi, bdf, df, f_start, P, B, quirk));
+    L->p->grad(mode, f_end, bdel, delta, dphi, bdf, df, f_start, P, B, quirk != 0);
   });
 }
 
 int cmbl_max_lensing_step(cmbl_flow* L, int basis, const void* phi, const void* eta, int nb, double* out) {
   return guard([&] {
     NOTNULL(L); NOTNULL(phi); NOTNULL(eta); NOTNULL(out); BASIS_OK(basis); CMBL_REQUIRE(nb >= 1, ERR_SHAPE, "nbatch >= 1");
-    BY_DTYPE(L->ctx, do_max_lensing_step<float>(L, basis, phi, eta, nb, out), do_max_lensing_step<double>(L, basis, phi, eta, nb, out));
+    L->p->max_lensing_step(basis, phi, eta, nb, out);
   });
 }
 
@@ -251,26 +244,26 @@ int cmbl_axpby(cmbl_ctx* ctx, int basis, const double* a, const void* x, const d
     NOTNULL(ctx); NOTNULL(a); NOTNULL(x); NOTNULL(out); BASIS_OK(basis); POLB_OK(P, B);
     CMBL_REQUIRE(y == nullptr || b != nullptr, ERR_ARG, "b is required when y is given");
     const long n = (basis == B_MAP ? ctx->p->npix() : 2 * ctx->p->plane()) * P;
-    BY_DTYPE(ctx, do_axpby<float>(ctx, a, x, b, y, out, n, B), do_axpby<double>(ctx, a, x, b, y, out, n, B));
+    BY_DTYPE(ctx, do_axpby, ctx, a, x, b, y, out, n, B);
   });
 }
 int cmbl_qe_leg(cmbl_ctx* ctx, const void* in_fourier, int n, int p1, int p2, void* out_map, int B) {
   return guard([&] {
     NOTNULL(ctx); NOTNULL(in_fourier); NOTNULL(out_map); CMBL_REQUIRE(B >= 1 && n >= 0 && p1 >= 0 && p2 >= 0, ERR_ARG, "bad leg indices");
-    BY_DTYPE(ctx, do_qe_leg<float>(ctx, in_fourier, n, p1, p2, out_map, B), do_qe_leg<double>(ctx, in_fourier, n, p1, p2, out_map, B));
+    BY_DTYPE(ctx, do_qe_leg, ctx, in_fourier, n, p1, p2, out_map, B);
   });
 }
 int cmbl_fourier_lmul(cmbl_ctx* ctx, const void* in_map, int p1, int p2, int take_abs, void* out_fourier, int B) {
   return guard([&] {
     NOTNULL(ctx); NOTNULL(in_map); NOTNULL(out_fourier); CMBL_REQUIRE(B >= 1 && p1 >= 0 && p2 >= 0, ERR_ARG, "bad exponents");
-    BY_DTYPE(ctx, do_fourier_lmul<float>(ctx, in_map, p1, p2, take_abs, out_fourier, B), do_fourier_lmul<double>(ctx, in_map, p1, p2, take_abs, out_fourier, B));
+    BY_DTYPE(ctx, do_fourier_lmul, ctx, in_map, p1, p2, take_abs, out_fourier, B);
   });
 }
 int cmbl_map_fma(cmbl_ctx* ctx, const void* a, const void* b, double scale, void* out, int accumulate, int nslices) {
   return guard([&] {
     NOTNULL(ctx); NOTNULL(a); NOTNULL(b); NOTNULL(out); CMBL_REQUIRE(nslices >= 1, ERR_SHAPE, "nslices >= 1");
     const long n = ctx->p->npix() * nslices;
-    BY_DTYPE(ctx, do_map_fma<float>(ctx, a, b, scale, out, accumulate, n), do_map_fma<double>(ctx, a, b, scale, out, accumulate, n));
+    BY_DTYPE(ctx, do_map_fma, ctx, a, b, scale, out, accumulate, n);
   });
 }
 
@@ -278,7 +271,7 @@ int cmbl_randn(cmbl_ctx* ctx, const uint64_t* seeds, int nslots, uint64_t stream
   return guard([&] {
     NOTNULL(ctx); NOTNULL(seeds); NOTNULL(out);
     CMBL_REQUIRE(nslots >= 1 && n_per_slot >= 1, ERR_SHAPE, "nslots >= 1 and n_per_slot >= 1");
-    BY_DTYPE(ctx, do_randn<float>(ctx, seeds, nslots, stream, out, n_per_slot), do_randn<double>(ctx, seeds, nslots, stream, out, n_per_slot));
+    BY_DTYPE(ctx, do_randn, ctx, seeds, nslots, stream, out, n_per_slot);
   });
 }
 
@@ -288,27 +281,27 @@ int cmbl_dataset_create(cmbl_ctx* ctx, int npol, cmbl_dataset** out) {
     NOTNULL(ctx); NOTNULL(out);
     auto h = std::make_unique<cmbl_dataset>();
     h->ctx = ctx;
-    BY_DTYPE(ctx, do_dataset_create<float>(h.get(), npol), do_dataset_create<double>(h.get(), npol));
+    BY_DTYPE(ctx, do_dataset_create, h.get(), npol);
     registry_add(h.get());
     *out = h.release();
   });
 }
 int cmbl_dataset_destroy(cmbl_dataset* ds) { return guard([&] { if (ds) registry_remove(ds); delete ds; }); }
 int cmbl_dataset_set_op(cmbl_dataset* ds, int which, const void* planes, int nplanes) {
-  return guard([&] { NOTNULL(ds); NOTNULL(planes); BY_DTYPE(ds->ctx, do_dataset_set_op<float>(ds, which, planes, nplanes), do_dataset_set_op<double>(ds, which, planes, nplanes)); });
+  return guard([&] { NOTNULL(ds); NOTNULL(planes); ds->p->set_op(which, planes, nplanes); });
 }
 int cmbl_dataset_set_data(cmbl_dataset* ds, const void* d, int B) {
-  return guard([&] { NOTNULL(ds); NOTNULL(d); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1"); BY_DTYPE(ds->ctx, do_dataset_set_data<float>(ds, d, B), do_dataset_set_data<double>(ds, d, B)); });
+  return guard([&] { NOTNULL(ds); NOTNULL(d); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1"); ds->p->set_data(d, B); });
 }
 int cmbl_dataset_set_logdet(cmbl_dataset* ds, double v) {
-  return guard([&] { NOTNULL(ds); BY_DTYPE(ds->ctx, ds->f32->logdet_sum = v, ds->f64->logdet_sum = v); });
+  return guard([&] { NOTNULL(ds); ds->p->logdet_sum = v; });
 }
 
 int cmbl_gradientf_logpdf(cmbl_dataset* ds, cmbl_flow* L, const void* f, const void* d, int zero_d, void* out, int B) {
   return guard([&] {
     NOTNULL(ds); NOTNULL(L); NOTNULL(f); NOTNULL(out); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1");
-    CMBL_REQUIRE(ds->ctx == L->ctx, ERR_ARG, "dataset and flow belong to different contexts");
-    BY_DTYPE(ds->ctx, do_gradf<float>(ds, L, f, d, zero_d, out, B), do_gradf<double>(ds, L, f, d, zero_d, out, B));
+    SAME_CTX(ds, L);
+    BY_DTYPE(ds->ctx, do_gradf, ds, L, f, d, zero_d, out, B);
   });
 }
 
@@ -317,24 +310,23 @@ int cmbl_wiener_cg(cmbl_dataset* ds, cmbl_flow* L, const void* d, const void* fs
   return guard([&] {
     NOTNULL(ds); NOTNULL(L); NOTNULL(f_out); NOTNULL(hist); NOTNULL(nit);
     CMBL_REQUIRE(B >= 1 && maxit >= 1, ERR_ARG, "nbatch >= 1 and maxit >= 1");
-    CMBL_REQUIRE(ds->ctx == L->ctx, ERR_ARG, "dataset and flow belong to different contexts");
-    BY_DTYPE(ds->ctx, do_cg<float>(ds, L, d, fstart, tol, maxit, f_out, hist, nit, B),
-             do_cg<double>(ds, L, d, fstart, tol, maxit, f_out, hist, nit, B));
+    SAME_CTX(ds, L);
+    BY_DTYPE(ds->ctx, do_cg, ds, L, d, fstart, tol, maxit, f_out, hist, nit, B);
   });
 }
 
 int cmbl_logpdf_mixed(cmbl_dataset* ds, cmbl_flow* L, const void* fo, const void* phio, double* lp, int B) {
   return guard([&] {
     NOTNULL(ds); NOTNULL(L); NOTNULL(fo); NOTNULL(phio); NOTNULL(lp); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1");
-    CMBL_REQUIRE(ds->ctx == L->ctx, ERR_ARG, "dataset and flow belong to different contexts");
-    BY_DTYPE(ds->ctx, do_lpm<float>(ds, L, fo, phio, lp, nullptr, nullptr, B, 0), do_lpm<double>(ds, L, fo, phio, lp, nullptr, nullptr, B, 0));
+    SAME_CTX(ds, L);
+    BY_DTYPE(ds->ctx, do_lpm, ds, L, fo, phio, lp, nullptr, nullptr, B, 0);
   });
 }
 int cmbl_grad_logpdf_mixed(cmbl_dataset* ds, cmbl_flow* L, const void* fo, const void* phio, double* lp, void* gfo, void* gphio, int B, int quirk) {
   return guard([&] {
     NOTNULL(ds); NOTNULL(L); NOTNULL(fo); NOTNULL(phio); NOTNULL(lp); NOTNULL(gfo); NOTNULL(gphio); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1");
-    CMBL_REQUIRE(ds->ctx == L->ctx, ERR_ARG, "dataset and flow belong to different contexts");
-    BY_DTYPE(ds->ctx, do_lpm<float>(ds, L, fo, phio, lp, gfo, gphio, B, quirk), do_lpm<double>(ds, L, fo, phio, lp, gfo, gphio, B, quirk));
+    SAME_CTX(ds, L);
+    BY_DTYPE(ds->ctx, do_lpm, ds, L, fo, phio, lp, gfo, gphio, B, quirk);
   });
 }
 
@@ -344,9 +336,8 @@ int cmbl_hmc_step(cmbl_dataset* ds, cmbl_flow* L, const void* fo, const void* ph
   return guard([&] {
     NOTNULL(ds); NOTNULL(L); NOTNULL(fo); NOTNULL(phio); NOTNULL(mass); NOTNULL(phio_out); NOTNULL(dH_host); NOTNULL(accept_host);
     CMBL_REQUIRE(B >= 1 && B <= MAXBATCH && nleap >= 1, ERR_ARG, "1 <= nbatch <= 256 and nleap >= 1");
-    CMBL_REQUIRE(ds->ctx == L->ctx, ERR_ARG, "dataset and flow belong to different contexts");
-    BY_DTYPE(ds->ctx, do_hmc<float>(ds, L, fo, phio, mass, white_p, log_u_host, seeds_host, step, nleap, eps, always_accept, alias_quirk, B, phio_out, dH_host, accept_host),
-             do_hmc<double>(ds, L, fo, phio, mass, white_p, log_u_host, seeds_host, step, nleap, eps, always_accept, alias_quirk, B, phio_out, dH_host, accept_host));
+    SAME_CTX(ds, L);
+    BY_DTYPE(ds->ctx, do_hmc, ds, L, fo, phio, mass, white_p, log_u_host, seeds_host, step, nleap, eps, always_accept, alias_quirk, B, phio_out, dH_host, accept_host);
   });
 }
 int cmbl_map_joint_step(cmbl_dataset* ds, cmbl_flow* L, const void* phi, const void* fstart, const void* hinv, double alpha_max, double alpha_tol,
@@ -355,9 +346,8 @@ int cmbl_map_joint_step(cmbl_dataset* ds, cmbl_flow* L, const void* phi, const v
   return guard([&] {
     NOTNULL(ds); NOTNULL(L); NOTNULL(phi); NOTNULL(hinv); NOTNULL(f_out); NOTNULL(phi_out); NOTNULL(logpdf_host); NOTNULL(alpha_host); NOTNULL(ncg_host); NOTNULL(nls_host);
     CMBL_REQUIRE(B >= 1 && B <= MAXBATCH && cg_maxit >= 1 && alpha_max > 0 && alpha_tol > 0, ERR_ARG, "1 <= nbatch <= 256, cg_maxit >= 1, alpha_max > 0, alpha_tol > 0");
-    CMBL_REQUIRE(ds->ctx == L->ctx, ERR_ARG, "dataset and flow belong to different contexts");
-    BY_DTYPE(ds->ctx, do_map_step<float>(ds, L, phi, fstart, hinv, alpha_max, alpha_tol, cg_tol, cg_maxit, alias_quirk, B, f_out, phi_out, logpdf_host, alpha_host, ncg_host, nls_host),
-             do_map_step<double>(ds, L, phi, fstart, hinv, alpha_max, alpha_tol, cg_tol, cg_maxit, alias_quirk, B, f_out, phi_out, logpdf_host, alpha_host, ncg_host, nls_host));
+    SAME_CTX(ds, L);
+    BY_DTYPE(ds->ctx, do_map_step, ds, L, phi, fstart, hinv, alpha_max, alpha_tol, cg_tol, cg_maxit, alias_quirk, B, f_out, phi_out, logpdf_host, alpha_host, ncg_host, nls_host);
   });
 }
 
@@ -367,8 +357,7 @@ int cmbl_quadratic_estimate(cmbl_dataset* ds, int which, const double* Cf_host, 
     NOTNULL(ds); NOTNULL(Cf_host); NOTNULL(Cftilde_host); NOTNULL(Cn_host); NOTNULL(TF_host); NOTNULL(Cphi_host); NOTNULL(phiqe_out);
     CMBL_REQUIRE(which >= 0 && which <= 2, ERR_ARG, "which: 0 = TT, 1 = EE, 2 = EB (src/quadratic_estimate.jl:41: the others are not implemented by the reference either)");
     CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1");
-    BY_DTYPE(ds->ctx, do_qe<float>(ds, which, Cf_host, Cftilde_host, Cn_host, TF_host, Cphi_host, wiener_filtered, AL_in_host, phiqe_out, AL_out_host, B),
-             do_qe<double>(ds, which, Cf_host, Cftilde_host, Cn_host, TF_host, Cphi_host, wiener_filtered, AL_in_host, phiqe_out, AL_out_host, B));
+    BY_DTYPE(ds->ctx, do_qe, ds, which, Cf_host, Cftilde_host, Cn_host, TF_host, Cphi_host, wiener_filtered, AL_in_host, phiqe_out, AL_out_host, B);
   });
 }
 
@@ -385,8 +374,7 @@ int cmbl_ud_grade(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv_pixwin, int
     const char* a = (const char*)in; const char* b = (const char*)out;
     const size_t na = sl * el * (bi == B_MAP ? (size_t)s.npix() : 2 * (size_t)s.plane()), nb = sl * el * (bo == B_MAP ? (size_t)d.npix() : 2 * (size_t)d.plane());
     CMBL_REQUIRE(a + na <= b || b + nb <= a, ERR_ARG, "ud_grade: in and out must not alias");
-    BY_DTYPE(src, do_ud_grade<float>(src, dst, mode, deconv_pixwin, anti_aliasing, bi, in, bo, out, P, B),
-             do_ud_grade<double>(src, dst, mode, deconv_pixwin, anti_aliasing, bi, in, bo, out, P, B));
+    BY_DTYPE(src, do_ud_grade, src, dst, mode, deconv_pixwin, anti_aliasing, bi, in, bo, out, P, B);
   });
 }
 int cmbl_pixwin_host(cmbl_ctx* ctx, double* out_host, size_t n) {
@@ -436,7 +424,7 @@ int cmbl_get_cl(cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, con
       CMBL_REQUIRE(a >= 0 && a < P && b >= 0 && b < P, ERR_ARG, "get_cl: a pair indexes a plane outside [0, npol)");
       pr.a[k] = (signed char)a; pr.b[k] = (signed char)b;
     }
-    BY_DTYPE(ctx, do_get_cl<float>(ctx, bins, basis, f1, f2, P, B, pr, moments, out), do_get_cl<double>(ctx, bins, basis, f1, f2, P, B, pr, moments, out));
+    BY_DTYPE(ctx, do_get_cl, ctx, bins, basis, f1, f2, P, B, pr, moments, out);
   });
 }
 
@@ -446,7 +434,7 @@ int cmbl_bilinear_create(cmbl_ctx* ctx, cmbl_bilinear** out) {
     NOTNULL(ctx); NOTNULL(out);
     auto h = std::make_unique<cmbl_bilinear>();
     h->ctx = ctx;
-    BY_DTYPE(ctx, do_bl_create<float>(h.get()), do_bl_create<double>(h.get()));
+    BY_DTYPE(ctx, do_bl_create, h.get());
     *out = h.release();
   });
 }
@@ -454,13 +442,13 @@ int cmbl_bilinear_destroy(cmbl_bilinear* L) { return guard([&] { delete L; }); }
 int cmbl_bilinear_set_phi(cmbl_bilinear* L, int basis, const void* phi, int nb) {
   return guard([&] {
     NOTNULL(L); NOTNULL(phi); BASIS_OK(basis); CMBL_REQUIRE(nb >= 1, ERR_SHAPE, "nbatch_phi >= 1");
-    BY_DTYPE(L->ctx, do_bl_set_phi<float>(L, basis, phi, nb), do_bl_set_phi<double>(L, basis, phi, nb));
+    L->p->set_phi(basis, phi, nb);
   });
 }
 int cmbl_bilinear_set_deflection(cmbl_bilinear* L, const void* dy_px, const void* dx_px) {
   return guard([&] {
     NOTNULL(L); NOTNULL(dy_px); NOTNULL(dx_px);
-    BY_DTYPE(L->ctx, do_bl_set_deflection<float>(L, dy_px, dx_px), do_bl_set_deflection<double>(L, dy_px, dx_px));
+    L->p->set_deflection(dy_px, dx_px);
   });
 }
 int cmbl_bilinear_apply(cmbl_bilinear* L, int mode, int bi, const void* in, int bo, void* out, int P, int B, int maxiter) {
@@ -468,13 +456,13 @@ int cmbl_bilinear_apply(cmbl_bilinear* L, int mode, int bi, const void* in, int 
     NOTNULL(L); NOTNULL(in); NOTNULL(out); BASIS_OK(bi); BASIS_OK(bo); POLB_OK(P, B);
     CMBL_REQUIRE(mode >= 0 && mode <= 3, ERR_ARG, "bad flow mode");
     CMBL_REQUIRE(maxiter >= 1 && maxiter <= BL_MAXIT, ERR_ARG, "maxiter must lie in [1, 16]");
-    BY_DTYPE(L->ctx, do_bl_apply<float>(L, mode, bi, in, bo, out, P, B, maxiter), do_bl_apply<double>(L, mode, bi, in, bo, out, P, B, maxiter));
+    L->p->apply(mode, bi, in, bo, out, P, B, maxiter);
   });
 }
 int cmbl_bilinear_grad(cmbl_bilinear* L, const void* f_lensed, int bdel, const void* delta, void* dphi, int bdf, void* df, int P, int B) {
   return guard([&] {
     NOTNULL(L); NOTNULL(f_lensed); NOTNULL(delta); NOTNULL(dphi); NOTNULL(df); BASIS_OK(bdel); BASIS_OK(bdf); POLB_OK(P, B);
-    BY_DTYPE(L->ctx, do_bl_grad<float>(L, f_lensed, bdel, delta, dphi, bdf, df, P, B), do_bl_grad<double>(L, f_lensed, bdel, delta, dphi, bdf, df, P, B));
+    L->p->grad(f_lensed, bdel, delta, dphi, bdf, df, P, B);
   });
 }
 
@@ -487,8 +475,7 @@ int cmbl_debug_stamps(unsigned long long* out_host, int n) {
     const std::string u = e ? e : "main_f32";
     int rc = -1;
 #define CMBL_X(unit) if (u == #unit) rc = cmbl::stamps_read_##unit(out_host, n);
-    CMBL_X(main_f32) CMBL_X(main_f64) CMBL_X(gen_f32) CMBL_X(gen_f64) CMBL_X(small_f32) CMBL_X(small_f64) CMBL_X(cty_f32_a) CMBL_X(cty_f32_b) CMBL_X(cty_f64_a) CMBL_X(cty_f64_b) \
-    CMBL_X(ctx_f32_a) CMBL_X(ctx_f32_b) CMBL_X(ctx_f64_a) CMBL_X(ctx_f64_b)
+    CMBL_STAMPS_UNITS(CMBL_X)
 #undef CMBL_X
     CMBL_REQUIRE(rc == 0, ERR_ARG, "CMBL_STAMPS_TU: main_{f32,f64} | gen_{f32,f64} | small_{f32,f64} | cty_{f32,f64}_{a,b} | ctx_{f32,f64}_{a,b}");
   });

@@ -1,16 +1,12 @@
 // The typed bodies behind the C ABI (declared in api_decl.hpp); included by tu_main_{f32,f64}.hip only, which instantiate them.
 #pragma once
 #include "api_decl.hpp"
-#include "engine_ud.hpp"
-#include "engine_cl.hpp"
-#include "engine_bilinear.hpp"
 
 namespace cmbl {
 
-template <typename T> std::unique_ptr<Flow<T>>& flow_of(cmbl_flow* L) { if constexpr (sizeof(T) == 4) return L->f32; else return L->f64; }
-template <typename T> std::unique_ptr<Dataset<T>>& ds_of(cmbl_dataset* d) { if constexpr (sizeof(T) == 4) return d->f32; else return d->f64; }
-template <typename T> std::map<const void*, std::unique_ptr<Drivers<T>>>& drv_of(cmbl_dataset* d) { if constexpr (sizeof(T) == 4) return d->drv32; else return d->drv64; }
-template <typename T> Ctx<T>* C(cmbl_ctx* c) { return static_cast<Ctx<T>*>(c->p.get()); }
+// the typed object behind a handle: typed<Flow<T>>(L), typed<Dataset<T>>(ds) -- T is the precision of the handle's context (BY_DTYPE)
+template <typename X, typename H> X& typed(H* h) { return *static_cast<X*>(h->p.get()); }
+template <typename T> Ctx<T>* C(cmbl_ctx* c) { return &typed<Ctx<T>>(c); }
 
 template <typename T> void do_convert(cmbl_ctx* ctx, int bi, const void* in, int bo, void* out, int P, int B) {
   Ctx<T>* c = C<T>(ctx);
@@ -70,7 +66,7 @@ template <typename T> void do_logdet(cmbl_ctx* ctx, const void* d, int nplanes, 
 }
 template <typename T>
 void do_gradf(cmbl_dataset* dsh, cmbl_flow* Lh, const void* f, const void* d, int zero_d, void* out, int B) {
-  Dataset<T>& ds = *ds_of<T>(dsh); Flow<T>& L = *flow_of<T>(Lh);
+  Dataset<T>& ds = typed<Dataset<T>>(dsh); Flow<T>& L = typed<Flow<T>>(Lh);
   Ctx<T>* c = ds.c;
   const long n = ds.fsize(B);
   ds.cvt.ensure(sizeof(cx<T>) * 3 * n);
@@ -86,7 +82,7 @@ void do_gradf(cmbl_dataset* dsh, cmbl_flow* Lh, const void* f, const void* d, in
 }
 template <typename T>
 void do_cg(cmbl_dataset* dsh, cmbl_flow* Lh, const void* d, const void* fstart, double tol, int maxit, void* f_out, double* hist, int* nit, int B) {
-  Dataset<T>& ds = *ds_of<T>(dsh); Flow<T>& L = *flow_of<T>(Lh);
+  Dataset<T>& ds = typed<Dataset<T>>(dsh); Flow<T>& L = typed<Flow<T>>(Lh);
   Ctx<T>* c = ds.c;
   const long n = ds.fsize(B);
   ds.cvt.ensure(sizeof(cx<T>) * 3 * n);
@@ -102,7 +98,7 @@ void do_cg(cmbl_dataset* dsh, cmbl_flow* Lh, const void* d, const void* fstart, 
 }
 template <typename T>
 void do_lpm(cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, double* lp, void* gfo, void* gphio, int B, int quirk) {
-  Dataset<T>& ds = *ds_of<T>(dsh); Flow<T>& L = *flow_of<T>(Lh);
+  Dataset<T>& ds = typed<Dataset<T>>(dsh); Flow<T>& L = typed<Flow<T>>(Lh);
   Ctx<T>* c = ds.c;
   const long pl = c->plane();
   ds.cvt.ensure(sizeof(cx<T>) * 2 * B * pl);
@@ -113,15 +109,15 @@ void do_lpm(cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, 
   CMBL_HIP(hipStreamSynchronize(c->stream));
 }
 
-template <typename T> Drivers<T>& drivers_of(std::map<const void*, std::unique_ptr<Drivers<T>>>& m, Dataset<T>& ds, Flow<T>& L) {
-  auto& p = m[&L];
-  if (!p) p = std::make_unique<Drivers<T>>(ds, L);
-  return *p;
+template <typename T> Drivers<T>& drivers_of(cmbl_dataset* dsh, cmbl_flow* Lh) {
+  auto& p = dsh->drv[Lh->p.get()];
+  if (!p) p = std::make_shared<Drivers<T>>(typed<Dataset<T>>(dsh), typed<Flow<T>>(Lh));
+  return *static_cast<Drivers<T>*>(p.get());
 }
 template <typename T>
 void do_hmc(cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, const void* mass, const void* white_p, const double* log_u, const uint64_t* seeds,
                    uint64_t step, int nleap, double eps, int always, int quirk, int B, void* phio_out, double* dH, int* accept) {
-  Drivers<T>& dr = drivers_of(drv_of<T>(dsh), *ds_of<T>(dsh), *flow_of<T>(Lh));
+  Drivers<T>& dr = drivers_of<T>(dsh, Lh);
   Dataset<T>& ds = dr.ds;
   Ctx<T>* c = ds.c;
   const long pl = c->plane(), np = c->npix();
@@ -148,7 +144,7 @@ void do_hmc(cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, 
 template <typename T>
 void do_map_step(cmbl_dataset* dsh, cmbl_flow* Lh, const void* phi, const void* fstart, const void* hinv, double amax, double atol, double cg_tol, int cg_maxit, int quirk,
                         int B, void* f_out, void* phi_out, double* logpdf, double* alpha, int* ncg, int* nls) {
-  Drivers<T>& dr = drivers_of(drv_of<T>(dsh), *ds_of<T>(dsh), *flow_of<T>(Lh));
+  Drivers<T>& dr = drivers_of<T>(dsh, Lh);
   Dataset<T>& ds = dr.ds;
   Ctx<T>* c = ds.c;
   const long pl = c->plane(), n = ds.fsize(B);
@@ -179,7 +175,7 @@ void do_map_step(cmbl_dataset* dsh, cmbl_flow* Lh, const void* phi, const void* 
 template <typename T>
 void do_qe(cmbl_dataset* dsh, int which, const double* Cf, const double* Cft, const double* Cn, const double* TF, const double* Cphi, int wiener,
                   const double* AL_in, void* phiqe_out, double* AL_out, int B) {
-  Dataset<T>& ds = *ds_of<T>(dsh); auto& pool = dsh->qe_pool;
+  Dataset<T>& ds = typed<Dataset<T>>(dsh); auto& pool = dsh->qe_pool;
   Ctx<T>* c = ds.c;
   const long pl = c->plane();
   CMBL_REQUIRE(ds.Bd == B, ERR_SHAPE, "dataset data batch size differs from nbatch");
@@ -204,8 +200,11 @@ void do_qe(cmbl_dataset* dsh, int which, const double* Cf, const double* Cft, co
 }
 
 
-// ---- the members the entry points used to call directly (api.hip must not instantiate a launching member: see api_decl.hpp) ----------
-template <typename T> CtxBase* do_ctx_create(int Ny, int Nx, double theta, int device, void* stream) { return new Ctx<T>(Ny, Nx, theta, device, stream); }
+// ---- the creators, and the members that take typed pointers (api.hip must not instantiate a launching member: see api_decl.hpp) ----------
+template <typename T> void do_ctx_create(cmbl_ctx* h, int Ny, int Nx, double theta, int device, void* stream) { h->p = std::make_unique<Ctx<T>>(Ny, Nx, theta, device, stream); }
+template <typename T> void do_flow_create(cmbl_flow* h, int nsteps) { h->p = std::make_unique<Flow<T>>(C<T>(h->ctx), nsteps); }
+template <typename T> void do_dataset_create(cmbl_dataset* h, int npol) { h->p = std::make_unique<Dataset<T>>(C<T>(h->ctx), npol); }
+template <typename T> void do_bl_create(cmbl_bilinear* h) { h->p = std::make_unique<Bilinear<T>>(C<T>(h->ctx)); }
 template <typename T> void do_axpby(cmbl_ctx* ctx, const double* a, const void* x, const double* b, const void* y, void* out, long n, int B) {
   C<T>(ctx)->lincomb((T*)out, (const T*)x, (const T*)y, a, b, n, B);
 }
@@ -221,31 +220,11 @@ template <typename T> void do_map_fma(cmbl_ctx* ctx, const void* a, const void* 
 template <typename T> void do_randn(cmbl_ctx* ctx, const uint64_t* seeds, int nslots, uint64_t stream, void* out, long n_per_slot) {
   C<T>(ctx)->randn((T*)out, seeds, nslots, stream, n_per_slot);
 }
-template <typename T> void do_flow_create(cmbl_flow* h, int nsteps) { flow_of<T>(h) = std::make_unique<Flow<T>>(C<T>(h->ctx), nsteps); }
-template <typename T> void do_flow_set_phi(cmbl_flow* L, int basis, const void* phi, int nb) { flow_of<T>(L)->set_phi(basis, phi, nb); }
-template <typename T> void do_flow_apply(cmbl_flow* L, int mode, int bi, const void* in, int bo, void* out, int P, int B) { flow_of<T>(L)->apply(mode, bi, in, bo, out, P, B); }
-template <typename T> void do_flow_grad(cmbl_flow* L, int mode, const void* f_end, int bdel, const void* delta, void* dphi, int bdf, void* df, void* f_start, int P, int B, int quirk) {
-  flow_of<T>(L)->grad(mode, f_end, bdel, delta, dphi, bdf, df, f_start, P, B, quirk != 0);
-}
-template <typename T> void do_max_lensing_step(cmbl_flow* L, int basis, const void* phi, const void* eta, int nb, double* out) { flow_of<T>(L)->max_lensing_step(basis, phi, eta, nb, out); }
-template <typename T> void do_dataset_create(cmbl_dataset* h, int npol) { ds_of<T>(h) = std::make_unique<Dataset<T>>(C<T>(h->ctx), npol); }
-template <typename T> void do_dataset_set_op(cmbl_dataset* ds, int which, const void* planes, int nplanes) { ds_of<T>(ds)->set_op(which, planes, nplanes); }
-template <typename T> void do_dataset_set_data(cmbl_dataset* ds, const void* d, int B) { ds_of<T>(ds)->set_data(d, B); }
 template <typename T> void do_ud_grade(cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv, int aa, int bi, const void* in, int bo, void* out, int P, int B) {
   ud_grade<T>(C<T>(src), C<T>(dst), mode, deconv != 0, aa != 0, bi, in, bo, out, P, B);
 }
 template <typename T> void do_get_cl(cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, const void* f2, int P, int B, const ClPairs& pr, int moments, double* out) {
   get_cl<T>(C<T>(ctx), *bins->p, basis, f1, f2, P, B, pr, moments, out);
-}
-template <typename T> std::unique_ptr<Bilinear<T>>& bl_of(cmbl_bilinear* L) { if constexpr (sizeof(T) == 4) return L->f32; else return L->f64; }
-template <typename T> void do_bl_create(cmbl_bilinear* h) { bl_of<T>(h) = std::make_unique<Bilinear<T>>(C<T>(h->ctx)); }
-template <typename T> void do_bl_set_phi(cmbl_bilinear* L, int basis, const void* phi, int nb) { bl_of<T>(L)->set_phi(basis, phi, nb); }
-template <typename T> void do_bl_set_deflection(cmbl_bilinear* L, const void* dy_px, const void* dx_px) { bl_of<T>(L)->set_deflection(dy_px, dx_px); }
-template <typename T> void do_bl_apply(cmbl_bilinear* L, int mode, int bi, const void* in, int bo, void* out, int P, int B, int maxiter) {
-  bl_of<T>(L)->apply(mode, bi, in, bo, out, P, B, maxiter);
-}
-template <typename T> void do_bl_grad(cmbl_bilinear* L, const void* f_lensed, int bdel, const void* delta, void* dphi, int bdf, void* df, int P, int B) {
-  bl_of<T>(L)->grad(f_lensed, bdel, delta, dphi, bdf, df, P, B);
 }
 
 }  // namespace cmbl

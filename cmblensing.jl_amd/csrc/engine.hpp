@@ -863,8 +863,19 @@ struct Ctx : CtxBase {
 
 // =================================================================================================
 // LenseFlow operator  (src/lenseflow.jl, src/flowops.jl)
+// What the C ABI (api.hip) holds of a flow: the members whose signatures carry no precision, as CtxBase does for Ctx<T>.  One virtual call per
+// ABI call; nothing below the boundary calls through it.
+struct FlowApi {
+  virtual ~FlowApi() = default;
+  virtual void set_phi(int basis, const void* phi, int nb) = 0;
+  virtual void max_lensing_step(int basis, const void* phi, const void* eta, int nb, double* out_host) = 0;
+  virtual void apply(int mode, int basis_in, const void* in, int basis_out, void* out, int P, int B) = 0;
+  virtual void grad(int mode, const void* f_end, int basis_delta, const void* delta, void* dphi_out, int basis_df, void* df_out,
+                    void* f_start_out, int P, int B, bool quirk) = 0;
+};
+
 template <typename T>
-struct Flow {
+struct Flow : FlowApi {
   Ctx<T>* c;
   int n;                                  // RK4 steps (src/lenseflow.jl:29 default 7)
   int Bphi = 0;
@@ -977,7 +988,7 @@ struct Flow {
       CMBL_LAUNCH(c, K_GRADHESS, (k_pcache<T>), dim3(gx), 0, c->stream, ph(), pcache.as<T>(), (long)ntot, 2 * n);
     }
   }
-  void set_phi(int basis, const void* phi, int nb) {
+  void set_phi(int basis, const void* phi, int nb) override {
     CMBL_REQUIRE(basis == B_MAP || basis == B_FOURIER || basis == B_HARMONIC, ERR_ARG, "bad basis");
     phiF.ensure(sizeof(cx<T>) * nb * c->plane());
     c->to_F(basis, phi, phiF.as<cx<T>>(), B_FOURIER, 1, nb);
@@ -993,7 +1004,7 @@ struct Flow {
     c->F_to_map(gh.as<cx<T>>(), maps, 5L * nb);
   }
   // get_max_lensing_step (src/lenseflow.jl:242-256); does not touch the flow's own phi cache
-  void max_lensing_step(int basis, const void* phi, const void* eta, int nb, double* out_host) {
+  void max_lensing_step(int basis, const void* phi, const void* eta, int nb, double* out_host) override {
     CMBL_REQUIRE(nb <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
     const long np = c->npix();
     DevBuf &mp = mls_p, &me = mls_e, &pf = mls_f;                           // pooled: called once per line-search evaluation
@@ -1472,7 +1483,7 @@ struct Flow {
   }
 
   // ---- boundary-level entry points ---------------------------------------------------------------
-  void apply(int mode, int basis_in, const void* in, int basis_out, void* out, int P, int B) {
+  void apply(int mode, int basis_in, const void* in, int basis_out, void* out, int P, int B) override {
     const long slices = (long)P * B, pl = c->plane(), np = c->npix();
     if (mode == F_FWD || mode == F_INV) {
       y0.ensure(sizeof(T) * slices * np);
@@ -1498,7 +1509,7 @@ struct Flow {
   }
 
   void grad(int mode, const void* f_end, int basis_delta, const void* delta, void* dphi_out, int basis_df, void* df_out,
-            void* f_start_out, int P, int B, bool quirk) {
+            void* f_start_out, int P, int B, bool quirk) override {
     const long slices = (long)P * B, pl = c->plane(), np = c->npix();
     y0.ensure(sizeof(T) * slices * np); Y0.ensure(sizeof(cx<T>) * slices * pl); P0.ensure(sizeof(cx<T>) * B * pl);
     T* f = f_start_out ? (T*)f_start_out : y0.as<T>();
@@ -1514,20 +1525,26 @@ struct Flow {
 // Data model, Wiener filter, posterior   (src/dataset.jl, src/maximization.jl, src/numerical_algorithms.jl)
 enum OpId { OP_CF_INV = 0, OP_CN_INV, OP_B, OP_MF, OP_D, OP_D_INV, OP_PRECOND_INV, OP_CPHI_INV, OP_G_INV, OP_MPIX, OP_COUNT };
 
+struct DatasetApi {                        // what the C ABI (api.hip) holds of a dataset (see FlowApi)
+  double logdet_sum = 0;
+  virtual ~DatasetApi() = default;
+  virtual void set_op(int which, const void* planes, int nplanes) = 0;
+  virtual void set_data(const void* d_ref, int B) = 0;
+};
+
 template <typename T>
-struct Dataset {
+struct Dataset : DatasetApi {
   Ctx<T>* c;
   int P;
   struct Op { DevBuf buf; int nplanes = 0; const T* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; int kind = 0; };
   Op ops[OP_COUNT];
   DevBuf d_h; int Bd = 0;                  // data, F layout harmonic
-  double logdet_sum = 0;
   // scratch
   DevBuf t1, t2, t3, mp, mp2, xs, rs, zs, ps, aps, best, bb, phiF, gphi, dphi1, dphi2, fh, fhat, ftil, cvt;
 
   Dataset(Ctx<T>* ctx, int npol) : c(ctx), P(npol) { CMBL_REQUIRE(npol >= 1 && npol <= 3, ERR_ARG, "npol must be 1, 2 or 3"); }
 
-  void set_op(int which, const void* planes, int nplanes) {
+  void set_op(int which, const void* planes, int nplanes) override {
     CMBL_REQUIRE(which >= 0 && which < OP_COUNT, ERR_ARG, "bad operator id");
     Op& o = ops[which];
     if (which == OP_MPIX) {
@@ -1554,7 +1571,7 @@ struct Dataset {
     const Op& o = op(which);
     c->harm(in, out, Pp < 0 ? P : Pp, B, o.kind, o.d, transpose, in_qu, out_qu, z, alpha, beta);
   }
-  void set_data(const void* d_ref, int B) {
+  void set_data(const void* d_ref, int B) override {
     d_h.ensure(sizeof(cx<T>) * (long)P * B * c->plane());
     c->ref2F((const cx<T>*)d_ref, d_h.template as<cx<T>>(), (long)P * B);
     Bd = B;

@@ -17,8 +17,16 @@ namespace cmbl {
 // the table of one operator and, once asked for, the CSR of its transpose
 struct BlTab { DevBuf base, fr, rowstart, col, val; bool rows = false, csr = false; };
 
+struct BilinearApi {                         // what the C ABI (api.hip) holds of a BilinearLens (see FlowApi in engine.hpp)
+  virtual ~BilinearApi() = default;
+  virtual void set_phi(int basis, const void* phi, int nb) = 0;
+  virtual void set_deflection(const void* dy_px, const void* dx_px) = 0;
+  virtual void apply(int mode, int bi, const void* in, int bo, void* out, int P, int B, int maxiter) = 0;
+  virtual void grad(const void* f_lensed, int bdel, const void* delta, void* dphi, int bdf, void* df, int P, int B) = 0;
+};
+
 template <typename T>
-struct Bilinear {
+struct Bilinear : BilinearApi {
   Ctx<T>* c;
   bool ready = false, identity = false;
   T div = 1;                                 // the deflection maps are divided by this (Δx for ∇ϕ, 1 for pixel-unit maps)
@@ -74,7 +82,7 @@ struct Bilinear {
     else CMBL_LAUNCH(c, K_BL, (k_bl_gather<T>), dim3(pgrid()), 0, c->stream, t.base.as<unsigned>(), t.fr.as<cx<T>>(), in, out, c->Ny, c->Nx, S);
   }
 
-  void set_phi(int basis, const void* phi, int nb) {
+  void set_phi(int basis, const void* phi, int nb) override {
     CMBL_REQUIRE(nb == 1, ERR_SHAPE, "BilinearLens with batched phi is not implemented (src/bilinearlens.jl:40)");
     const long np = c->npix(), pl = c->plane(), n = basis == B_MAP ? np : 2 * pl;
     flag.ensure(sizeof(int));
@@ -95,7 +103,7 @@ struct Bilinear {
     div = (T)(c->theta / 60.0 * M_PI / 180.0);                              // Δx in T (src/proj_lambert.jl:58)
     rows(fwd, (T)1);
   }
-  void set_deflection(const void* dy_px, const void* dx_px) {
+  void set_deflection(const void* dy_px, const void* dx_px) override {
     const long np = c->npix();
     defl.ensure(sizeof(T) * 2 * np);
     CMBL_HIP(hipMemcpyAsync(defl.as<T>(), dx_px, sizeof(T) * np, hipMemcpyDeviceToDevice, c->stream));
@@ -164,7 +172,7 @@ struct Bilinear {
     c->from_F(cvt.as<cx<T>>(), carry, bo, out, P, B);
   }
 
-  void apply(int mode, int bi, const void* in, int bo, void* out, int P, int B, int maxiter) {
+  void apply(int mode, int bi, const void* in, int bo, void* out, int P, int B, int maxiter) override {
     check_ready();
     if (identity) return convert(bi, in, bo, out, P, B);                    // sparse_repr === I && return f (:108, 118, 128, 141)
     const int S = P * B;
@@ -181,7 +189,7 @@ struct Bilinear {
   }
 
   // pullback of L*f (:165-171): δf = L'Δ in `bdf`; δϕ = ∇'·(Σ_pol Ł(Δ) Ł(∇f̃)), a Fourier plane per batch slot (ABI layout)
-  void grad(const void* f_lensed, int bdel, const void* delta, void* dphi, int bdf, void* df, int P, int B) {
+  void grad(const void* f_lensed, int bdel, const void* delta, void* dphi, int bdf, void* df, int P, int B) override {
     check_ready();
     const int S = P * B;
     const long np = c->npix(), pl = c->plane();

@@ -7,19 +7,81 @@ import time
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
-# every symbol include/cmblens.h declares (tests/test_boundary.py checks the .so exports exactly these)
-SYMBOLS = [
-    "cmbl_last_error", "cmbl_version", "cmbl_abi_version", "cmbl_ctx_set_option", "cmbl_ctx_get_option", "cmbl_ctx_create", "cmbl_ctx_destroy",
-    "cmbl_ctx_synchronize", "cmbl_ctx_geometry_host", "cmbl_prof_enable", "cmbl_prof_reset", "cmbl_prof_count", "cmbl_prof_name", "cmbl_prof_get",
-    "cmbl_rfft", "cmbl_irfft", "cmbl_convert", "cmbl_diag_apply", "cmbl_blockdiag_ieb_apply", "cmbl_dot", "cmbl_logdet", "cmbl_lenseflow_create",
-    "cmbl_lenseflow_destroy", "cmbl_lenseflow_set_phi", "cmbl_lenseflow_apply", "cmbl_lenseflow_grad", "cmbl_dataset_create", "cmbl_dataset_destroy",
-    "cmbl_dataset_set_op", "cmbl_dataset_set_data", "cmbl_dataset_set_logdet", "cmbl_max_lensing_step", "cmbl_axpby", "cmbl_qe_leg",
-    "cmbl_fourier_lmul", "cmbl_map_fma", "cmbl_randn", "cmbl_gradientf_logpdf", "cmbl_wiener_cg", "cmbl_logpdf_mixed", "cmbl_grad_logpdf_mixed",
-    "cmbl_hmc_step", "cmbl_map_joint_step", "cmbl_quadratic_estimate", "cmbl_norm", "cmbl_logdet_diag", "cmbl_tr_diag", "cmbl_set_sum_accuracy_mode",
-    "cmbl_timer_report", "cmbl_device_malloc", "cmbl_device_free", "cmbl_copy_to_device", "cmbl_copy_to_host",
-    "cmbl_ud_grade", "cmbl_pixwin_host", "cmbl_clbins_create", "cmbl_clbins_destroy", "cmbl_clbins_info_host", "cmbl_get_cl",
-    "cmbl_bilinear_create", "cmbl_bilinear_destroy", "cmbl_bilinear_set_phi", "cmbl_bilinear_set_deflection", "cmbl_bilinear_apply", "cmbl_bilinear_grad",
-]
+# The binding: every function include/cmblens.h declares, once.  SIGNATURES: the functions that return a status code (int), with their
+# argument types; OTHER_RETURNS: (restype, argtypes) of the few that return something else.  tests/test_boundary.py checks that SYMBOLS is
+# exactly what the header declares and the .so exports.
+_vp, _ci, _cd, _sz, _l, _u64, _str = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_long, ctypes.c_uint64, ctypes.c_char_p
+_pvp, _pci, _pd, _pl, _pu64 = (ctypes.POINTER(t) for t in (_vp, _ci, _cd, _l, _u64))
+OTHER_RETURNS = {
+    "cmbl_last_error": (_str, []),
+    "cmbl_version": (_ci, []),
+    "cmbl_abi_version": (_ci, []),
+    "cmbl_prof_count": (_ci, []),
+    "cmbl_prof_name": (_str, [_ci]),
+}
+SIGNATURES = {
+    "cmbl_ctx_create": [_ci, _ci, _cd, _ci, _ci, _vp, _pvp],
+    "cmbl_ctx_destroy": [_vp],
+    "cmbl_ctx_set_option": [_vp, _str, _ci],
+    "cmbl_ctx_get_option": [_vp, _str, _pci],
+    "cmbl_ctx_synchronize": [_vp],
+    "cmbl_ctx_geometry_host": [_vp, _ci, _pd, _sz],
+    "cmbl_prof_enable": [_vp, _ci],
+    "cmbl_prof_reset": [_vp],
+    "cmbl_prof_get": [_vp, _ci, _pd, _pl],
+    "cmbl_rfft": [_vp, _vp, _vp, _ci, _ci],
+    "cmbl_irfft": [_vp, _vp, _vp, _ci, _ci],
+    "cmbl_convert": [_vp, _ci, _vp, _ci, _vp, _ci, _ci],
+    "cmbl_diag_apply": [_vp, _ci, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _ci],
+    "cmbl_blockdiag_ieb_apply": [_vp, _vp, _ci, _ci, _vp, _ci, _vp, _ci],
+    "cmbl_dot": [_vp, _ci, _vp, _vp, _ci, _ci, _pd],
+    "cmbl_logdet": [_vp, _vp, _ci, _pd],
+    "cmbl_lenseflow_create": [_vp, _ci, _pvp],
+    "cmbl_lenseflow_destroy": [_vp],
+    "cmbl_lenseflow_set_phi": [_vp, _ci, _vp, _ci],
+    "cmbl_lenseflow_apply": [_vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci],
+    "cmbl_lenseflow_grad": [_vp, _ci, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _ci, _ci],
+    "cmbl_max_lensing_step": [_vp, _ci, _vp, _vp, _ci, _pd],
+    "cmbl_axpby": [_vp, _ci, _pd, _vp, _pd, _vp, _vp, _ci, _ci],
+    "cmbl_qe_leg": [_vp, _vp, _ci, _ci, _ci, _vp, _ci],
+    "cmbl_fourier_lmul": [_vp, _vp, _ci, _ci, _ci, _vp, _ci],
+    "cmbl_map_fma": [_vp, _vp, _vp, _cd, _vp, _ci, _ci],
+    "cmbl_randn": [_vp, _pu64, _ci, _u64, _vp, _l],
+    "cmbl_dataset_create": [_vp, _ci, _pvp],
+    "cmbl_dataset_destroy": [_vp],
+    "cmbl_dataset_set_op": [_vp, _ci, _vp, _ci],
+    "cmbl_dataset_set_data": [_vp, _vp, _ci],
+    "cmbl_dataset_set_logdet": [_vp, _cd],
+    "cmbl_gradientf_logpdf": [_vp, _vp, _vp, _vp, _ci, _vp, _ci],
+    "cmbl_wiener_cg": [_vp, _vp, _vp, _vp, _cd, _ci, _vp, _pd, _pci, _ci],
+    "cmbl_logpdf_mixed": [_vp, _vp, _vp, _vp, _pd, _ci],
+    "cmbl_grad_logpdf_mixed": [_vp, _vp, _vp, _vp, _pd, _vp, _vp, _ci, _ci],
+    "cmbl_hmc_step": [_vp, _vp, _vp, _vp, _vp, _vp, _pd, _pu64, _u64, _ci, _cd, _ci, _ci, _ci, _vp, _pd, _pci],
+    "cmbl_quadratic_estimate": [_vp, _ci, _pd, _pd, _pd, _pd, _pd, _ci, _pd, _vp, _pd, _ci],
+    "cmbl_map_joint_step": [_vp, _vp, _vp, _vp, _vp, _cd, _cd, _cd, _ci, _ci, _ci, _vp, _vp, _pd, _pd, _pci, _pci],
+    "cmbl_norm": [_vp, _ci, _vp, _ci, _ci, _pd],
+    "cmbl_logdet_diag": [_vp, _ci, _vp, _ci, _ci, _pd],
+    "cmbl_tr_diag": [_vp, _ci, _vp, _ci, _ci, _pd],
+    "cmbl_set_sum_accuracy_mode": [_vp, _ci],
+    "cmbl_timer_report": [_vp, _str, _sz],
+    "cmbl_device_malloc": [_vp, _sz, _pvp],
+    "cmbl_device_free": [_vp, _vp],
+    "cmbl_copy_to_device": [_vp, _vp, _vp, _sz],
+    "cmbl_copy_to_host": [_vp, _vp, _vp, _sz],
+    "cmbl_ud_grade": [_vp, _vp, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _ci, _ci],
+    "cmbl_pixwin_host": [_vp, _pd, _sz],
+    "cmbl_clbins_create": [_vp, _pd, _ci, _pd, _sz, _pvp],
+    "cmbl_clbins_destroy": [_vp],
+    "cmbl_clbins_info_host": [_vp, _ci, _pd, _sz],
+    "cmbl_get_cl": [_vp, _vp, _ci, _vp, _vp, _ci, _ci, _pci, _ci, _ci, _vp],
+    "cmbl_bilinear_create": [_vp, _pvp],
+    "cmbl_bilinear_destroy": [_vp],
+    "cmbl_bilinear_set_phi": [_vp, _ci, _vp, _ci],
+    "cmbl_bilinear_set_deflection": [_vp, _vp, _vp],
+    "cmbl_bilinear_apply": [_vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _ci],
+    "cmbl_bilinear_grad": [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _ci, _ci],
+}
+SYMBOLS = list(OTHER_RETURNS) + list(SIGNATURES)
 
 
 ABI_VERSION = 3          # CMBL_ABI_VERSION of include/cmblens.h this binding was written against
@@ -121,85 +183,11 @@ def load_library():
         raise ImportError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
     lib = ctypes.CDLL(path)
-    vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-    pd = ctypes.POINTER(ctypes.c_double)
-    lib.cmbl_last_error.restype = ctypes.c_char_p
-    lib.cmbl_last_error.argtypes = []
-    lib.cmbl_version.restype = ci
-    lib.cmbl_abi_version.restype = ci
-    lib.cmbl_abi_version.argtypes = []
+    for name, (restype, argtypes) in list(OTHER_RETURNS.items()) + [(n, (_ci, a)) for n, a in SIGNATURES.items()]:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.cmbl_abi_version() != ABI_VERSION:
         raise ImportError(f"{path}: ABI version {lib.cmbl_abi_version()} but this package binds version {ABI_VERSION} (include/cmblens.h): rebuild")
-    lib.cmbl_prof_count.restype = ci
-    lib.cmbl_prof_count.argtypes = []
-    lib.cmbl_prof_name.restype = ctypes.c_char_p
-    lib.cmbl_prof_name.argtypes = [ci]
-    sig = {
-        "cmbl_ctx_create": [ci, ci, cd, ci, ci, vp, ctypes.POINTER(vp)],
-        "cmbl_ctx_destroy": [vp],
-        "cmbl_ctx_set_option": [vp, ctypes.c_char_p, ci],
-        "cmbl_ctx_get_option": [vp, ctypes.c_char_p, ctypes.POINTER(ci)],
-        "cmbl_ctx_synchronize": [vp],
-        "cmbl_ctx_geometry_host": [vp, ci, pd, ctypes.c_size_t],
-        "cmbl_prof_enable": [vp, ci],
-        "cmbl_prof_reset": [vp],
-        "cmbl_prof_get": [vp, ci, pd, ctypes.POINTER(ctypes.c_long)],
-        "cmbl_rfft": [vp, vp, vp, ci, ci],
-        "cmbl_irfft": [vp, vp, vp, ci, ci],
-        "cmbl_convert": [vp, ci, vp, ci, vp, ci, ci],
-        "cmbl_diag_apply": [vp, ci, ci, vp, ci, vp, ci, vp, ci, ci],
-        "cmbl_blockdiag_ieb_apply": [vp, vp, ci, ci, vp, ci, vp, ci],
-        "cmbl_dot": [vp, ci, vp, vp, ci, ci, pd],
-        "cmbl_logdet": [vp, vp, ci, pd],
-        "cmbl_lenseflow_create": [vp, ci, ctypes.POINTER(vp)],
-        "cmbl_lenseflow_destroy": [vp],
-        "cmbl_lenseflow_set_phi": [vp, ci, vp, ci],
-        "cmbl_lenseflow_apply": [vp, ci, ci, vp, ci, vp, ci, ci],
-        "cmbl_lenseflow_grad": [vp, ci, vp, ci, vp, vp, ci, vp, vp, ci, ci, ci],
-        "cmbl_max_lensing_step": [vp, ci, vp, vp, ci, pd],
-        "cmbl_axpby": [vp, ci, pd, vp, pd, vp, vp, ci, ci],
-        "cmbl_qe_leg": [vp, vp, ci, ci, ci, vp, ci],
-        "cmbl_fourier_lmul": [vp, vp, ci, ci, ci, vp, ci],
-        "cmbl_map_fma": [vp, vp, vp, cd, vp, ci, ci],
-        "cmbl_randn": [vp, ctypes.POINTER(ctypes.c_uint64), ci, ctypes.c_uint64, vp, ctypes.c_long],
-        "cmbl_dataset_create": [vp, ci, ctypes.POINTER(vp)],
-        "cmbl_dataset_destroy": [vp],
-        "cmbl_dataset_set_op": [vp, ci, vp, ci],
-        "cmbl_dataset_set_data": [vp, vp, ci],
-        "cmbl_dataset_set_logdet": [vp, cd],
-        "cmbl_gradientf_logpdf": [vp, vp, vp, vp, ci, vp, ci],
-        "cmbl_wiener_cg": [vp, vp, vp, vp, cd, ci, vp, pd, ctypes.POINTER(ci), ci],
-        "cmbl_logpdf_mixed": [vp, vp, vp, vp, pd, ci],
-        "cmbl_grad_logpdf_mixed": [vp, vp, vp, vp, pd, vp, vp, ci, ci],
-        "cmbl_hmc_step": [vp, vp, vp, vp, vp, vp, pd, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64, ci, cd, ci, ci, ci, vp, pd, ctypes.POINTER(ci)],
-        "cmbl_quadratic_estimate": [vp, ci, pd, pd, pd, pd, pd, ci, pd, vp, pd, ci],
-        "cmbl_map_joint_step": [vp, vp, vp, vp, vp, cd, cd, cd, ci, ci, ci, vp, vp, pd, pd, ctypes.POINTER(ci), ctypes.POINTER(ci)],
-        "cmbl_norm": [vp, ci, vp, ci, ci, pd],
-        "cmbl_logdet_diag": [vp, ci, vp, ci, ci, pd],
-        "cmbl_tr_diag": [vp, ci, vp, ci, ci, pd],
-        "cmbl_set_sum_accuracy_mode": [vp, ci],
-        "cmbl_timer_report": [vp, ctypes.c_char_p, ctypes.c_size_t],
-        "cmbl_device_malloc": [vp, ctypes.c_size_t, ctypes.POINTER(vp)],
-        "cmbl_device_free": [vp, vp],
-        "cmbl_copy_to_device": [vp, vp, vp, ctypes.c_size_t],
-        "cmbl_copy_to_host": [vp, vp, vp, ctypes.c_size_t],
-        "cmbl_ud_grade": [vp, vp, ci, ci, ci, ci, vp, ci, vp, ci, ci],
-        "cmbl_pixwin_host": [vp, pd, ctypes.c_size_t],
-        "cmbl_clbins_create": [vp, pd, ci, pd, ctypes.c_size_t, ctypes.POINTER(vp)],
-        "cmbl_clbins_destroy": [vp],
-        "cmbl_clbins_info_host": [vp, ci, pd, ctypes.c_size_t],
-        "cmbl_get_cl": [vp, vp, ci, vp, vp, ci, ci, ctypes.POINTER(ci), ci, ci, vp],
-        "cmbl_bilinear_create": [vp, ctypes.POINTER(vp)],
-        "cmbl_bilinear_destroy": [vp],
-        "cmbl_bilinear_set_phi": [vp, ci, vp, ci],
-        "cmbl_bilinear_set_deflection": [vp, vp, vp],
-        "cmbl_bilinear_apply": [vp, ci, ci, vp, ci, vp, ci, ci, ci],
-        "cmbl_bilinear_grad": [vp, vp, ci, vp, vp, ci, vp, ci, ci],
-    }
-    for name, argtypes in sig.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = ci
     _LIB = lib
     return lib
 

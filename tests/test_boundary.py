@@ -172,3 +172,18 @@ def test_transform_branch_list_of_the_gpu_tests_covers_the_header_s():
     assert want <= classes, sorted(want - classes)
     assert {lgl(n) for n, f in sizes if f} >= {3, 4, 5}                  # reachable only when forced
     assert any(f and n == 4096 for n, f in sizes)                        # L = 8192 = 2N exactly
+
+
+def test_entry_point_unit_instantiates_no_kernel_and_no_typed_class(libpath):
+    """csrc/api_decl.hpp: api.hip reaches typed code through the virtual members of the precision-free bases and through the bodies do_*<T>
+    only.  hipcc names the host stub of every kernel a unit instantiates `__device_stub__...`; a member of a typed class (a destructor that
+    a handle instantiates, say) shows up as a reference to `cmbl::Flow<...>::...`.  The object of api.hip has neither."""
+    obj = os.path.join(ROOT, "build", "obj", "api.o")
+    assert os.path.exists(obj), obj
+    out = subprocess.run(["nm", "-C", obj], capture_output=True, text=True, check=True).stdout
+    syms = [m.groups() for m in re.finditer(r"^(?:[0-9a-f]+)?\s+(\w) (.*)$", out, flags=re.M)]       # (type, demangled name); type U: referenced only
+    assert len(syms) > 100 and ("T", "cmbl_lenseflow_apply") in syms                               # nm read the object and demangled it
+    stubs = [n for t, n in syms if t != "U" and "__device_stub__" in n]
+    assert not stubs, stubs[:5]
+    typed = [n for t, n in syms if any(k in n for k in ("cmbl::Flow<", "cmbl::Dataset<", "cmbl::Drivers<", "cmbl::Bilinear<"))]
+    assert not typed, typed[:8]
