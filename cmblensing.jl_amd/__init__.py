@@ -6,7 +6,7 @@ the reference's names (ProjLambert, LenseFlow, BaseDataSet, argmaxf_logpdf, ...)
 There is NO CPU fallback: without the built library or without a GPU every compute call raises.
 """
 from .lib import load_library, library_path, CmblError, build            # noqa: F401
-from .engine import (ProjLambert, LenseFlow, BilinearLens, BaseDataSet, Field, MAP, FOURIER, HARMONIC,   # noqa: F401
+from .engine import (ProjLambert, LenseFlow, BilinearLens, PowerLens, Taylens, antilensing, BaseDataSet, Field, MAP, FOURIER, HARMONIC,   # noqa: F401
                      FLOW_FWD, FLOW_INV, FLOW_ADJ, FLOW_INVADJ, reference_exact, ud_grade, pixwin, UD_MAP, UD_FOURIER,
                      get_Cl, get_Dl, get_l4Cl, get_rhol, cov_to_Cl)
 from .sim import (Cls, load_sim, noise_cls, beam_cls, lowpass, cl_to_2d, HarmOp, border_mask)   # noqa: F401

@@ -466,6 +466,39 @@ int cmbl_bilinear_grad(cmbl_bilinear* L, const void* f_lensed, int bdel, const v
   });
 }
 
+// ---- PowerLens / Taylens (src/powerlens.jl, src/taylens.jl) ------------------------------------------------------------
+int cmbl_powerlens_create(cmbl_ctx* ctx, int order, int kind, cmbl_powerlens** out) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(out);
+    CMBL_REQUIRE(order >= 0 && order <= PL_MAXORDER, ERR_ARG, "order must lie in [0, 12] (PowerLens(phi, order), src/powerlens.jl:22-29)");
+    CMBL_REQUIRE(kind == CMBL_POWERLENS || kind == CMBL_TAYLENS, ERR_ARG, "kind must be CMBL_POWERLENS (src/powerlens.jl) or CMBL_TAYLENS (src/taylens.jl)");
+    auto h = std::make_unique<cmbl_powerlens>();
+    h->ctx = ctx;
+    BY_DTYPE(ctx, do_pl_create, h.get(), order, kind);
+    *out = h.release();
+  });
+}
+int cmbl_powerlens_destroy(cmbl_powerlens* L) { return guard([&] { delete L; }); }
+int cmbl_powerlens_set_phi(cmbl_powerlens* L, int basis, const void* phi, int nb) {
+  return guard([&] {
+    NOTNULL(L); NOTNULL(phi); BASIS_OK(basis);
+    L->p->set_phi(basis, phi, nb);
+  });
+}
+int cmbl_powerlens_set_deflection(cmbl_powerlens* L, const void* dy_rad, const void* dx_rad) {
+  return guard([&] {
+    NOTNULL(L); NOTNULL(dy_rad); NOTNULL(dx_rad);
+    L->p->set_deflection(dy_rad, dx_rad);
+  });
+}
+int cmbl_powerlens_apply(cmbl_powerlens* L, int mode, int bi, const void* in, int bo, void* out, int P, int B) {
+  return guard([&] {
+    NOTNULL(L); NOTNULL(in); NOTNULL(out); BASIS_OK(bi); BASIS_OK(bo); POLB_OK(P, B);
+    CMBL_REQUIRE(mode >= 0 && mode <= 3, ERR_ARG, "bad flow mode");
+    L->p->apply(mode, bi, in, bo, out, P, B);
+  });
+}
+
 #ifdef CMBL_STAMPS
 // phase timestamps of the last stamped launch (tools/gpu_stamps*.py) of the translation unit CMBL_STAMPS_TU (kernels_fft.hpp CMBL_STAMPS_READER)
 int cmbl_debug_stamps(unsigned long long* out_host, int n) {

@@ -205,6 +205,7 @@ template <typename T> void do_ctx_create(cmbl_ctx* h, int Ny, int Nx, double the
 template <typename T> void do_flow_create(cmbl_flow* h, int nsteps) { h->p = std::make_unique<Flow<T>>(C<T>(h->ctx), nsteps); }
 template <typename T> void do_dataset_create(cmbl_dataset* h, int npol) { h->p = std::make_unique<Dataset<T>>(C<T>(h->ctx), npol); }
 template <typename T> void do_bl_create(cmbl_bilinear* h) { h->p = std::make_unique<Bilinear<T>>(C<T>(h->ctx)); }
+template <typename T> void do_pl_create(cmbl_powerlens* h, int order, int kind) { h->p = std::make_unique<PowerLens<T>>(C<T>(h->ctx), order, kind); }
 template <typename T> void do_axpby(cmbl_ctx* ctx, const double* a, const void* x, const double* b, const void* y, void* out, long n, int B) {
   C<T>(ctx)->lincomb((T*)out, (const T*)x, (const T*)y, a, b, n, B);
 }

@@ -1,8 +1,8 @@
 // What api.hip (the entry points) and the per-precision translation units share: the handle structs, the list of the typed bodies behind the
 // entry points and the dispatch on a context's precision.  The build is split by explicit instantiation (lib.py builds the objects in parallel):
 //   api.hip                 extern "C" entry points, argument checks, error plumbing -- instantiates NO kernel and nothing of Flow<T>, Bilinear<T>,
-//                           Dataset<T> or Drivers<T> (tests/test_boundary.py reads the object's symbols)
-//   tu_main_{f32,f64}.hip   every body of CMBL_API_BODIES (api_body.hpp) and with them Ctx<T>, Flow<T>, Bilinear<T>, Dataset<T>, Drivers<T>, their
+//                           PowerLens<T>, Dataset<T> or Drivers<T> (tests/test_boundary.py reads the object's symbols)
+//   tu_main_{f32,f64}.hip   every body of CMBL_API_BODIES (api_body.hpp) and with them Ctx<T>, Flow<T>, Bilinear<T>, PowerLens<T>, Dataset<T>, Drivers<T>, their
 //                           vtables and their kernels
 //   tu_gen_{f32,f64}.hip    the host side of the any-size transform launches (engine_gen.hpp) and the run-time-plan kernels k_gen_dft*
 //   tu_cty_{f32,f64}_{a,b}.hip   the compile-time-plan kernels of the column side and the plain transforms (engine_ct.hpp CtLaunchY: k_ct_dft,
@@ -11,7 +11,7 @@
 //   tu_small_{f32,f64}.hip  the one-launch flows of small maps (engine_small.hpp: k_small_flow, k_small_adj)
 // An entry point reaches typed code in two ways only, and neither makes api.hip instantiate a member of a typed class (members defined in class
 // are inline, and an explicit instantiation DECLARATION does not stop inline functions from being instantiated -- [temp.explicit]/10):
-//   * a virtual member of the precision-free base its handle owns (CtxBase, FlowApi, DatasetApi, BilinearApi): set_phi, apply, grad, ... and the
+//   * a virtual member of the precision-free base its handle owns (CtxBase, FlowApi, DatasetApi, BilinearApi, PowerLensApi): set_phi, apply, grad, ... and the
 //     destructors.  The typed objects are made by the creators below, so their vtables are emitted in tu_main_* alone.
 //   * BY_DTYPE(ctx, do_x, args...): a body of the list below, for what takes typed pointers or needs the typed object (which it gets back from
 //     the handle with typed<Flow<T>>(L) etc., a static_cast).
@@ -21,12 +21,14 @@
 #include "engine_ud.hpp"
 #include "engine_cl.hpp"
 #include "engine_bilinear.hpp"
+#include "engine_powerlens.hpp"
 #include "../../include/cmblens.h"
 
 struct cmbl_ctx { std::unique_ptr<cmbl::CtxBase> p; };
 struct cmbl_clbins { std::unique_ptr<cmbl::ClBins> p; };
 struct cmbl_flow { cmbl_ctx* ctx; std::unique_ptr<cmbl::FlowApi> p; };
 struct cmbl_bilinear { cmbl_ctx* ctx; std::unique_ptr<cmbl::BilinearApi> p; };
+struct cmbl_powerlens { cmbl_ctx* ctx; std::unique_ptr<cmbl::PowerLensApi> p; };
 struct cmbl_dataset {
   cmbl_ctx* ctx; std::unique_ptr<cmbl::DatasetApi> p;
   std::map<const cmbl::FlowApi*, std::shared_ptr<void>> drv;                 // driver scratch (a Drivers<T>, deleter and all) per (dataset, flow) pair
@@ -50,6 +52,7 @@ namespace cmbl {
   X(T, do_flow_create, (cmbl_flow* h, int nsteps)) \
   X(T, do_dataset_create, (cmbl_dataset* h, int npol)) \
   X(T, do_bl_create, (cmbl_bilinear* h)) \
+  X(T, do_pl_create, (cmbl_powerlens* h, int order, int kind)) \
   X(T, do_gradf, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* f, const void* d, int zero_d, void* out, int B)) \
   X(T, do_cg, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* d, const void* fstart, double tol, int maxit, void* f_out, double* hist, int* nit, int B)) \
   X(T, do_lpm, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, double* lp, void* gfo, void* gphio, int B, int quirk)) \

@@ -693,6 +693,92 @@ class BilinearLens:
         return Field(self.proj, dphi, FOURIER), Field(self.proj, df, basis_df)
 
 
+class _PowerLensAdjoint:
+    def __init__(self, L):
+        self.L = L
+
+    def __mul__(self, g):            # L' * g, in the Fourier basis as the reference returns it (src/powerlens.jl:54)
+        return self.L._apply(FLOW_ADJ, g, basis_out=FOURIER)
+
+
+class PowerLens:
+    """`PowerLens(ϕ, order)` (src/powerlens.jl): lensing by the Taylor series in ∇ϕ up to `order` (0 ... 12), with the part of `BilinearLens`'
+    surface that the reference defines: `L(ϕ)` / `set_phi`, `set_deflection`, `L * f` and `L.adjoint * g`.  One ϕ serves any number of
+    batch slots of f (a batched ϕ raises, :25)."""
+    _kind = 0                        # CMBL_POWERLENS
+
+    def __init__(self, proj, order):
+        self.proj, self.order = proj, int(order)
+        self.lib = proj.lib
+        self._h = ctypes.c_void_p()
+        check(self.lib.cmbl_powerlens_create(proj._h, self.order, self._kind, ctypes.byref(self._h)))
+        self._phi = self._defl = None
+
+    def __del__(self):
+        try:
+            if self._h:
+                self.lib.cmbl_powerlens_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def __call__(self, phi):
+        """phi: Field (any basis, P=1, B=1)."""
+        if self._phi is not phi:
+            P, B = self.proj._check(phi.arr, phi.basis)
+            assert P == 1
+            check(self.lib.cmbl_powerlens_set_phi(self._h, phi.basis, _ptr(phi.arr), B))
+            self._phi, self._defl = phi, None
+        return self
+
+    set_phi = __call__
+
+    def set_deflection(self, dy, dx):
+        """`PowerLens(d::FieldVector, order)` (:24): the deflection along Ny (`dy`) and along Nx (`dx`) in RADIANS, maps of shape (Nx, Ny)."""
+        dy, dx = (self.proj.tensor(a).reshape(1, 1, self.proj.Nx, self.proj.Ny) for a in (dy, dx))
+        self.proj._check(dy, MAP), self.proj._check(dx, MAP)
+        check(self.lib.cmbl_powerlens_set_deflection(self._h, _ptr(dy), _ptr(dx)))
+        self._phi, self._defl = None, (dy, dx)
+        return self
+
+    @property
+    def phi(self):
+        return self._phi
+
+    def _apply(self, mode, f, basis_out=MAP):
+        P, B = self.proj._check(f.arr, f.basis)
+        out = self.proj.empty(basis_out, P, B)
+        check(self.lib.cmbl_powerlens_apply(self._h, mode, f.basis, _ptr(f.arr), basis_out, _ptr(out), P, B))
+        return Field(self.proj, out, basis_out)
+
+    def __mul__(self, f):            # L * f
+        return self._apply(FLOW_FWD, f)
+
+    @property
+    def adjoint(self):
+        return _PowerLensAdjoint(self)
+
+
+class Taylens(PowerLens):
+    """`Taylens(ϕ, order)` (src/taylens.jl): the nearest-pixel permutation followed by the Taylor series in the residual displacement.  The
+    reference defines `L * f` alone: `adjoint` raises."""
+    _kind = 1                        # CMBL_TAYLENS
+
+    @property
+    def adjoint(self):
+        raise NotImplementedError("the reference defines no adjoint of Taylens (src/taylens.jl)")
+
+
+def antilensing(L):
+    """`antilensing(L)` (src/powerlens.jl:32-38): a new operator of the same kind and order that lenses by -ϕ (by -d after `set_deflection`)."""
+    A = type(L)(L.proj, L.order)
+    if L._phi is not None:
+        return A(Field(L.proj, -L._phi.arr, L._phi.basis))
+    if L._defl is None:
+        raise CmblError(5, "antilensing: the operator has no ϕ or deflection yet")
+    return A.set_deflection(-L._defl[0], -L._defl[1])
+
+
 class BaseDataSet:
     """`BaseDataSet` at fiducial θ (src/dataset.jl:37-57) with the operators resident on the device.
 

@@ -80,6 +80,11 @@ SIGNATURES = {
     "cmbl_bilinear_set_deflection": [_vp, _vp, _vp],
     "cmbl_bilinear_apply": [_vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _ci],
     "cmbl_bilinear_grad": [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _ci, _ci],
+    "cmbl_powerlens_create": [_vp, _ci, _ci, _pvp],
+    "cmbl_powerlens_destroy": [_vp],
+    "cmbl_powerlens_set_phi": [_vp, _ci, _vp, _ci],
+    "cmbl_powerlens_set_deflection": [_vp, _vp, _vp],
+    "cmbl_powerlens_apply": [_vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci],
 }
 SYMBOLS = list(OTHER_RETURNS) + list(SIGNATURES)
 

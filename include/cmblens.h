@@ -39,6 +39,7 @@ typedef struct cmbl_flow cmbl_flow;
 typedef struct cmbl_dataset cmbl_dataset;
 typedef struct cmbl_clbins cmbl_clbins;
 typedef struct cmbl_bilinear cmbl_bilinear;
+typedef struct cmbl_powerlens cmbl_powerlens;
 
 enum { CMBL_OK = 0, CMBL_ERR_ARG = 1, CMBL_ERR_SHAPE = 2, CMBL_ERR_HIP = 3, CMBL_ERR_NAN = 4,
        CMBL_ERR_STATE = 5, CMBL_ERR_ALLOC = 6 };
@@ -269,7 +270,7 @@ int cmbl_max_lensing_step(cmbl_flow* L, int basis, const void* phi, const void* 
  *   cmbl_bilinear_set_phi: BilinearLens(phi) (:31-87).  nbatch_phi != 1 is CMBL_ERR_SHAPE (:40).  norm(phi) == 0 makes every action a copy (:34).
  *        The tables of BilinearLens(-phi) (:92-97) and the transposed operators are made on first use and kept until the next set_phi.
  *   cmbl_bilinear_set_deflection: the same operator from two device MAPs (Nx x Ny reals each, the context's precision) of the deflection in
- *        PIXELS along Ny (dy_px) and along Nx (dx_px) -- lensing by an arbitrary displacement (compute_row!, :55-74, on given positions).
+ *        PIXELS (cmbl_powerlens_set_deflection takes radians) along Ny (dy_px) and along Nx (dx_px) -- lensing by an arbitrary displacement (compute_row!, :55-74, on given positions).
  *   cmbl_bilinear_apply: mode CMBL_FLOW_FWD L*f (:107-115), _ADJ L'*f (:117-125; summed in a fixed order: bit-identical between runs), _INV L\f
  *        (:127-138) and _INVADJ L'\f (:140-151): per slice gmres(A, b, Pl = BilinearLens(-phi), maxiter), formed as Arnoldi with modified
  *        Gram-Schmidt; 1 <= maxiter <= 16 (the reference uses 5), ignored by the other modes.  Fields in any basis, ABI
@@ -285,6 +286,33 @@ int cmbl_bilinear_apply(cmbl_bilinear* L, int mode, int basis_in, const void* in
                         int npol, int nbatch, int maxiter);
 int cmbl_bilinear_grad(cmbl_bilinear* L, const void* f_lensed, int basis_delta, const void* delta,
                        void* dphi_out, int basis_df, void* df_out, int npol, int nbatch);
+
+/* ---- PowerLens and Taylens: lensing by a Taylor series in the deflection (src/powerlens.jl, src/taylens.jl).
+ * With d = (dx, dy) the deflection and the derivatives applied in Fourier space as (i lx)^a (i ly)^b:
+ *   PowerLens(order) f  = f + sum_{n=1..order} sum_{a+b=n} dx^a dy^b / (a! b!) irfft((i lx)^a (i ly)^b rfft f)             (src/powerlens.jl:40-48)
+ *   PowerLens(order)' g = rfft g + sum_n (-1)^n sum_{a+b=n} (i lx)^a (i ly)^b rfft(dx^a dy^b g) / (a! b!)                   (:50-58)
+ *   Taylens(order) f    = the same sum with the residual d - round(d / dx_pix) dx_pix in place of d, f and every derivative map read at
+ *                         the pixel round(d / dx_pix) away, round half to even (src/taylens.jl:25-66).  Taylens(0) is that permutation alone.
+ * The engine forms every term in pixel units (l dx_pix and d / dx_pix): the same number term for term, and no power leaves the range of
+ * single precision (as written, l^10 overflows Float32 at 2' pixels).  One deflection, any number of (pol, batch) slices of f; nothing
+ * synchronises with the host and the sums run in a fixed order: results are bit-identical between runs.
+ *   cmbl_powerlens_create: order in [0, 12], kind CMBL_POWERLENS or CMBL_TAYLENS; anything else is CMBL_ERR_ARG.
+ *   cmbl_powerlens_set_phi: PowerLens(phi, order) (:23), d = grad phi.  nbatch_phi != 1 is CMBL_ERR_SHAPE (require_unbatched, :25).
+ *   cmbl_powerlens_set_deflection: PowerLens(d::FieldVector, order) (:24) from two device MAPs (Nx x Ny reals each, the context's precision)
+ *        of the deflection along Ny (dy_rad) and along Nx (dx_rad), argument order as cmbl_bilinear_set_deflection -- but in RADIANS, the
+ *        unit of the reference's constructor, where cmbl_bilinear_set_deflection takes pixels.
+ *   cmbl_powerlens_apply: mode CMBL_FLOW_FWD L*f or, for a PowerLens, CMBL_FLOW_ADJ L'*g (which the reference returns in the Fourier
+ *        basis).  _ADJ on a Taylens and _INV / _INVADJ on either are CMBL_ERR_ARG: the reference defines none of them.  Fields in any
+ *        basis, ABI layouts, `in` and `out` may be the same array.  Before any set_phi / set_deflection: CMBL_ERR_STATE.
+ * antilensing(L) (:36-38; the line as written cannot run) is the operator of -d: set_phi / set_deflection of a second handle with the negated
+ * argument. */
+enum { CMBL_POWERLENS = 0, CMBL_TAYLENS = 1 };
+int cmbl_powerlens_create(cmbl_ctx* ctx, int order, int kind, cmbl_powerlens** out);
+int cmbl_powerlens_destroy(cmbl_powerlens* L);
+int cmbl_powerlens_set_phi(cmbl_powerlens* L, int basis, const void* phi, int nbatch_phi);
+int cmbl_powerlens_set_deflection(cmbl_powerlens* L, const void* dy_rad, const void* dx_rad);
+int cmbl_powerlens_apply(cmbl_powerlens* L, int mode, int basis_in, const void* in, int basis_out, void* out,
+                         int npol, int nbatch);
 
 /* ---- small helpers used by the drivers above the hot kernels
  * axpby: out = a[b]*x + b[b]*y per batch slot (y may be NULL) -- the FieldTuple / Field broadcasts of the CG, line-search

@@ -272,6 +272,57 @@ Zygote.@adjoint function *(Lϕ::HIPBilinearLens, f::Field{B}) where {B}
     f̃, back
 end
 
+# ---- 2c. PowerLens and Taylens (src/powerlens.jl, src/taylens.jl) ---------------------------------------------------------------
+# lensing by the Taylor series in ∇ϕ up to `order` (0 ... 12): one ϕ, `*` for both and `'` for PowerLens (the reference defines no more);
+# the adjoint returns a Fourier field like upstream (src/powerlens.jl:54)
+const KIND_POWERLENS, KIND_TAYLENS = Cint(0), Cint(1)
+mutable struct HIPTaylorLens{T,K} <: ImplicitOp{T}
+    ϕ      :: Field
+    order  :: Int
+    ctx    :: HIPContext
+    h      :: Ptr{Cvoid}
+    cached :: Any                       # the ϕ object the device table was built from
+end
+const HIPPowerLens{T} = HIPTaylorLens{T,KIND_POWERLENS}
+const HIPTaylens{T} = HIPTaylorLens{T,KIND_TAYLENS}
+function taylorlens(K, ϕ::Field, order::Int)
+    T = real(eltype(ϕ))
+    ctx = hip_ctx(ϕ.metadata)
+    h = Ref{Ptr{Cvoid}}()
+    chk(ccall((:cmbl_powerlens_create, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Cvoid}}), ctx.h, order, K, h))
+    L = HIPTaylorLens{T,K}(ϕ, order, ctx, h[], nothing)
+    finalizer(L -> ccall((:cmbl_powerlens_destroy, lib), Cint, (Ptr{Cvoid},), L.h), L)
+end
+HIPPowerLens(ϕ::Field, order::Int) = taylorlens(KIND_POWERLENS, ϕ, order)
+HIPTaylens(ϕ::Field, order::Int) = taylorlens(KIND_TAYLENS, ϕ, order)
+HIPPowerLens(order::Int) = ϕ -> HIPPowerLens(ϕ, order)
+HIPTaylens(order::Int) = ϕ -> HIPTaylens(ϕ, order)
+getϕ(L::HIPTaylorLens) = L.ϕ
+(L::HIPTaylorLens)(ϕ::Field) = (L.ϕ === ϕ) ? L : (L.ϕ = ϕ; L)
+# antilensing (src/powerlens.jl:36-38 cannot run as written: `N` is undefined and ∇1ϕᵖ is passed twice): the operator of -ϕ, as its doc string says
+antilensing(L::HIPTaylorLens{T,K}) where {T,K} = taylorlens(K, -L.ϕ, L.order)
+function precompute!!(L::HIPTaylorLens)
+    if L.cached !== L.ϕ
+        ϕ′ = (basis_tag(L.ϕ) == MAP) ? L.ϕ : Fourier(L.ϕ)
+        a = ϕ′.arr
+        GC.@preserve a chk(ccall((:cmbl_powerlens_set_phi, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint),
+                                 L.h, basis_tag(ϕ′), devptr(a), nbatch(ϕ′)))
+        keepalive(L.ctx, a)
+        L.cached = L.ϕ
+    end
+    L
+end
+function taylorlens_apply(L::HIPTaylorLens, mode, f::BaseField, out::BaseField)
+    precompute!!(L)
+    a, o = f.arr, out.arr
+    GC.@preserve a o chk(ccall((:cmbl_powerlens_apply, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint),
+                               L.h, mode, basis_tag(f), devptr(a), basis_tag(out), devptr(o), npol(f), nbatch(f)))
+    keepalive(L.ctx, a)
+    out
+end
+*(L::HIPTaylorLens, f::Field) = (g = Ł(f); taylorlens_apply(L, FLOW_FWD, g, similar(g)))
+*(L::Adjoint{<:Any,<:HIPPowerLens}, f::Field) = (g = Ł(f); taylorlens_apply(parent(L), FLOW_ADJ, g, similar(Ð(g))))
+
 # ---- 3. data model, Wiener filter, mixed posterior ------------------------------------------------------------------------
 # include/cmblens.h: CMBL_OP_*
 const OP_CF_INV, OP_CN_INV, OP_B, OP_MF, OP_D, OP_D_INV, OP_PRECOND_INV, OP_CPHI_INV, OP_G_INV, OP_MPIX = Cint.(0:9)
