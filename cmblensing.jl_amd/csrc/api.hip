@@ -499,6 +499,30 @@ int cmbl_powerlens_apply(cmbl_powerlens* L, int mode, int bi, const void* in, in
   });
 }
 
+// ---- make_mask (src/masking.jl:1-67) -------------------------------------------------------------------------------------
+int cmbl_edt_sq(cmbl_ctx* ctx, const uint8_t* feat_dev, int32_t* d2_dev) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(feat_dev); NOTNULL(d2_dev);
+    BY_DTYPE(ctx, do_edt_sq, ctx, feat_dev, d2_dev);
+  });
+}
+int cmbl_make_mask(cmbl_ctx* ctx, const int32_t* src_yx_host, int nsrc, int pad, int apod_w, int round_w, int src_w, void* out_map_dev) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(out_map_dev);
+    const CtxBase& c = *ctx->p;
+    CMBL_REQUIRE(nsrc >= 0 && pad >= 0 && apod_w >= 0 && round_w >= 0 && src_w >= 0, ERR_ARG, "make_mask: the source count and the widths must not be negative");
+    CMBL_REQUIRE(apod_w == 0 || pad > 0, ERR_ARG, "make_mask: apodisation needs edge padding (without it there is no masked pixel to measure the distance to)");
+    CMBL_REQUIRE(nsrc == 0 || src_w > 0, ERR_ARG, "make_mask: point sources need a radius of at least one pixel");
+    CMBL_REQUIRE(nsrc == 0 || src_yx_host != nullptr, ERR_ARG, "make_mask: nsrc > 0 needs src_yx_host");
+    CMBL_REQUIRE(round_w <= MASK_MAXSIGMA, ERR_ARG, "make_mask: round_w must not exceed 1024 pixels");
+    CMBL_REQUIRE(pad <= EDT_MAXN && apod_w <= (1 << 20) && src_w <= 2 * EDT_MAXN, ERR_ARG, "make_mask: a width far beyond the largest map");
+    for (int s = 0; s < nsrc; ++s)
+      CMBL_REQUIRE(src_yx_host[2 * s] >= 0 && src_yx_host[2 * s] < c.Ny && src_yx_host[2 * s + 1] >= 0 && src_yx_host[2 * s + 1] < c.Nx, ERR_ARG, "make_mask: a point source lies outside the map");
+    const MaskArgs m{src_yx_host, nsrc, pad, apod_w, round_w, src_w};
+    BY_DTYPE(ctx, do_make_mask, ctx, m, out_map_dev);
+  });
+}
+
 #ifdef CMBL_STAMPS
 // phase timestamps of the last stamped launch (tools/gpu_stamps*.py) of the translation unit CMBL_STAMPS_TU (kernels_fft.hpp CMBL_STAMPS_READER)
 int cmbl_debug_stamps(unsigned long long* out_host, int n) {

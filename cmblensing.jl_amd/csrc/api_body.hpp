@@ -227,5 +227,7 @@ template <typename T> void do_ud_grade(cmbl_ctx* src, cmbl_ctx* dst, int mode, i
 template <typename T> void do_get_cl(cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, const void* f2, int P, int B, const ClPairs& pr, int moments, double* out) {
   get_cl<T>(C<T>(ctx), *bins->p, basis, f1, f2, P, B, pr, moments, out);
 }
+template <typename T> void do_edt_sq(cmbl_ctx* ctx, const uint8_t* feat, int32_t* d2) { edt_sq_checked<T>(C<T>(ctx), feat, d2); }
+template <typename T> void do_make_mask(cmbl_ctx* ctx, const MaskArgs& m, void* out) { make_mask<T>(C<T>(ctx), m, (T*)out); }
 
 }  // namespace cmbl

@@ -22,6 +22,7 @@
 #include "engine_cl.hpp"
 #include "engine_bilinear.hpp"
 #include "engine_powerlens.hpp"
+#include "engine_mask.hpp"
 #include "../../include/cmblens.h"
 
 struct cmbl_ctx { std::unique_ptr<cmbl::CtxBase> p; };
@@ -60,7 +61,9 @@ namespace cmbl {
   X(T, do_map_step, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* phi, const void* fstart, const void* hinv, double amax, double atol, double cg_tol, int cg_maxit, int quirk, int B, void* f_out, void* phi_out, double* logpdf, double* alpha, int* ncg, int* nls)) \
   X(T, do_qe, (cmbl_dataset* dsh, int which, const double* Cf, const double* Cft, const double* Cn, const double* TF, const double* Cphi, int wiener, const double* AL_in, void* phiqe_out, double* AL_out, int B)) \
   X(T, do_ud_grade, (cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv, int aa, int bi, const void* in, int bo, void* out, int P, int B)) \
-  X(T, do_get_cl, (cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, const void* f2, int P, int B, const ClPairs& pr, int moments, double* out))
+  X(T, do_get_cl, (cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, const void* f2, int P, int B, const ClPairs& pr, int moments, double* out)) \
+  X(T, do_edt_sq, (cmbl_ctx* ctx, const uint8_t* feat, int32_t* d2)) \
+  X(T, do_make_mask, (cmbl_ctx* ctx, const MaskArgs& m, void* out))
 
 #define CMBL_API_DECLARE(T, name, params) template <typename T> void name params;
 #define CMBL_API_INSTANTIATE(T, name, params) template void name<T> params;

@@ -359,6 +359,85 @@ def ud_grade(f, theta_new, mode="map", deconv_pixwin=None, anti_aliasing=None, p
     return Field(proj_new, out, basis_out)
 
 
+# ---- make_mask (src/masking.jl:1-67) ---------------------------------------------------------------------------------------------------
+def edt_sq(proj, feat):
+    """Squared Euclidean distance from every pixel to the nearest non-zero pixel of `feat` (a (Nx, Ny) array or tensor, the layout of a map
+    plane), exact: int32 device tensor (Nx, Ny) (`cmbl_edt_sq`; ImageMorphology.feature_transform + norm in src/masking.jl:42-43).  ValueError
+    when `feat` has no non-zero pixel."""
+    f = (feat if torch.is_tensor(feat) else torch.from_numpy(np.ascontiguousarray(np.asarray(feat) != 0))).to(device=proj.device)
+    f = (f != 0).to(torch.uint8).contiguous()
+    if tuple(f.shape) != (proj.Nx, proj.Ny):
+        raise ValueError(f"edt_sq: the feature plane has shape {tuple(f.shape)}, expected {(proj.Nx, proj.Ny)}")
+    out = torch.empty((proj.Nx, proj.Ny), dtype=torch.int32, device=proj.device)
+    try:
+        check(proj.lib.cmbl_edt_sq(proj._h, _ptr(f), _ptr(out)))
+    except CmblError as e:
+        if e.code == 1:
+            raise ValueError(str(e)) from e
+        raise
+    return out
+
+
+def mask_npix(theta_pix, edge_padding_deg=2, edge_rounding_deg=1, apodization_deg=1, ptsrc_radius_arcmin=7):
+    """The pixel widths (pad, apod_w, round_w, src_w) of make_mask's keywords: deg2npix(x) = round(Int, x / θpix * 60) and arcmin2npix(x) =
+    round(Int, x / θpix) (src/masking.jl:11-12), round half to even like Julia's."""
+    deg2npix = lambda x: int(round(float(x) / theta_pix * 60))
+    return deg2npix(edge_padding_deg), deg2npix(apodization_deg), deg2npix(edge_rounding_deg), int(round(float(ptsrc_radius_arcmin) / theta_pix))
+
+
+def draw_ptsrcs(Ny, Nx, n, seed=0):
+    """sim_ptsrcs (src/masking.jl:60-67) with NumPy's generator: `n` positions (y, x), 0-based, int32 (n, 2), drawn on the host from
+    np.random.Generator(PCG64(seed)), y then x per source; duplicates are allowed, as there."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    yx = np.empty((int(n), 2), dtype=np.int32)
+    for i in range(int(n)):
+        yx[i, 0] = rng.integers(0, Ny)
+        yx[i, 1] = rng.integers(0, Nx)
+    return yx
+
+
+def make_mask(Nside_or_proj, theta_pix=None, *, edge_padding_deg=2, edge_rounding_deg=1, apodization_deg=1, ptsrc_radius_arcmin=7,
+              num_ptsrcs=None, seed=0, ptsrcs=None, T=torch.float32, device=0):
+    """`make_mask(rng, Nside, θpix; ...)` (src/masking.jl:1-24): cosine-apodised border mask with rounded corners and apodised point-source
+    holes, made on the device (`cmbl_make_mask`; include/cmblens.h has the semantics).  `Nside_or_proj`: a ProjLambert (the reference's
+    `make_mask(f::LambertField)`, src/proj_lambert.jl:464), or Nside / (Ny, Nx) with `theta_pix` in arcmin (then `T` and `device` make the
+    ProjLambert).  Keywords, defaults and the unit conversion are the reference's; `num_ptsrcs` defaults to round(Ny Nx (θpix/60)² 120/100),
+    `apodization_deg` 0 / False gives the boolean mask.  `ptsrcs`: explicit (n, 2) integer (y, x) positions, 0-based, which override
+    `num_ptsrcs` and `seed`; otherwise `draw_ptsrcs(Ny, Nx, num_ptsrcs, seed)`.  The reference draws from a Julia RNG whose stream cannot be
+    reproduced here, so the holes of a given seed are NOT where the reference puts them -- pass `ptsrcs=` to compare.  The values are float32
+    numbers whatever `T` (Float32.(...), :23).  Returns a MAP Field with P = 1, B = 1.  ValueError where the reference's result is undefined."""
+    if isinstance(Nside_or_proj, ProjLambert):
+        proj = Nside_or_proj
+        if theta_pix is not None and float(theta_pix) != proj.theta_pix:
+            raise ValueError("make_mask: theta_pix differs from the ProjLambert's")
+    else:
+        if theta_pix is None:
+            raise ValueError("make_mask: theta_pix is required with Nside")
+        Ny, Nx = (Nside_or_proj, Nside_or_proj) if np.isscalar(Nside_or_proj) else Nside_or_proj
+        proj = ProjLambert(Ny, Nx, theta_pix, T, device)
+    Ny, Nx, theta = proj.Ny, proj.Nx, proj.theta_pix
+    pad, apod_w, round_w, src_w = mask_npix(theta, edge_padding_deg, edge_rounding_deg or 0, apodization_deg or 0, ptsrc_radius_arcmin)
+    if apodization_deg and apod_w == 0:
+        raise ValueError("make_mask: apodization_deg is below half a pixel (the profile would be 0 / 0); pass 0 for the boolean mask")
+    if ptsrcs is not None:
+        yx = np.ascontiguousarray(np.asarray(ptsrcs).reshape(-1, 2), dtype=np.int32)
+        if not np.array_equal(yx, np.asarray(ptsrcs).reshape(-1, 2)):
+            raise ValueError("make_mask: ptsrcs must be integer (y, x) positions")
+    else:
+        n = int(round(Ny * Nx * (theta / 60) ** 2 * 120 / 100)) if num_ptsrcs is None else int(num_ptsrcs)
+        if n < 0:
+            raise ValueError("make_mask: num_ptsrcs must not be negative")
+        yx = draw_ptsrcs(Ny, Nx, n, seed)
+    out = proj.empty(MAP, 1, 1)
+    try:
+        check(proj.lib.cmbl_make_mask(proj._h, yx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if len(yx) else None, len(yx), pad, apod_w, round_w, src_w, _ptr(out)))
+    except CmblError as e:
+        if e.code == 1:                                                     # CMBL_ERR_ARG: what the reference leaves undefined
+            raise ValueError(str(e)) from e
+        raise
+    return Field(proj, out, MAP)
+
+
 # ---- power spectra (src/proj_lambert.jl:415-419, 470-513; src/cls.jl:85-97) -------------------------------------------------------------
 _CL_PLANE = {1: {"I": 0}, 2: {"Q": 0, "U": 1, "E": 0, "B": 1}, 3: {"I": 0, "Q": 1, "U": 2, "E": 1, "B": 2}}
 _CL_WHICH = {1: "II", 2: ("EE", "BB"), 3: ("II", "EE", "BB", "IE", "IB", "EB")}       # the reference's defaults (:505, 510)

@@ -85,6 +85,8 @@ SIGNATURES = {
     "cmbl_powerlens_set_phi": [_vp, _ci, _vp, _ci],
     "cmbl_powerlens_set_deflection": [_vp, _vp, _vp],
     "cmbl_powerlens_apply": [_vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci],
+    "cmbl_edt_sq": [_vp, _vp, _vp],
+    "cmbl_make_mask": [_vp, _pci, _ci, _ci, _ci, _ci, _ci, _vp],
 }
 SYMBOLS = list(OTHER_RETURNS) + list(SIGNATURES)
 

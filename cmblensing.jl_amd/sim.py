@@ -9,7 +9,7 @@ planes are built once on the host; everything applied per iteration lives on the
 import numpy as np
 import torch
 
-from .engine import ProjLambert, BaseDataSet, Field, MAP, FOURIER, HARMONIC
+from .engine import ProjLambert, BaseDataSet, Field, MAP, FOURIER, HARMONIC, make_mask
 
 
 class Cls:
@@ -142,11 +142,16 @@ def white_noise(seed, shape):
 
 def load_sim(theta_pix, Nside, pol, cls, T=torch.float32, device=0, muK_arcmin_T=3.0, lknee=100.0, alphaknee=3.0,
              beam_fwhm=0.0, pixel_mask=None, bandpass_lmax=3000, nsteps=7, Nbatch=1, seeds=(1, 2, 3),
-             Nphi=None, Nphi_fac=2, G=None, rng="host"):
+             Nphi=None, Nphi_fac=2, G=None, rng="host", pixel_mask_kwargs=None):
     # Nphi: None / "qe" -> N⁰ of the quadratic estimator like the reference; "flat" -> cheap flat level; or an [x,ky] plane
     """`load_sim` (src/dataset.jl:186-338).  `cls`: dict group -> dict {TT,EE,BB,TE,pp} of Cls for the groups
     'unlensed_scalar', 'tensor', 'total' (e.g. decoded from the reference's dat/default_camb_Cls.jld2).
+    `pixel_mask_kwargs`: a dict of `make_mask` keywords: Mpix = make_mask(proj; ...) made on the device (:279-281), its point sources drawn
+    with `seed` = seeds[0] unless the dict says otherwise (the reference hands make_mask a copy of the simulation's rng).  `pixel_mask`: the
+    keywords of the deterministic `border_mask` instead; giving both is a ValueError.
     Returns dict(f, phi, ftilde, d, ds, proj) with Fields on the device."""
+    if pixel_mask is not None and pixel_mask_kwargs is not None:
+        raise ValueError("load_sim: give pixel_mask (border_mask) or pixel_mask_kwargs (make_mask), not both")
     Ny, Nx = (Nside, Nside) if np.isscalar(Nside) else Nside
     proj = ProjLambert(Ny, Nx, theta_pix, T, device)
     P = {"I": 1, "P": 2, "IP": 3}[pol]
@@ -162,6 +167,8 @@ def load_sim(theta_pix, Nside, pol, cls, T=torch.float32, device=0, muK_arcmin_T
     bcl = beam_cls(beam_fwhm, lmax)
     Bop = mk(Cls(bcl.ell, np.sqrt(bcl.cl)), units=1, te_zero=True)              # :300
     Mpix = border_mask(proj, **pixel_mask) if pixel_mask is not None else None
+    if pixel_mask_kwargs is not None:
+        Mpix = make_mask(proj, **{"seed": seeds[0], **pixel_mask_kwargs}).arr[0, 0].cpu().numpy().astype(np.float64)   # host form [x, y], like border_mask's
 
     qe_nphi = Nphi is None or (isinstance(Nphi, str) and Nphi == "qe")
     if qe_nphi or (isinstance(Nphi, str) and Nphi == "flat"):                   # provisional flat level until the data exist (see below)

@@ -314,6 +314,28 @@ int cmbl_powerlens_set_deflection(cmbl_powerlens* L, const void* dy_rad, const v
 int cmbl_powerlens_apply(cmbl_powerlens* L, int mode, int basis_in, const void* in, int basis_out, void* out,
                          int npol, int nbatch);
 
+/* ---- make_mask(Nside, θpix; edge_padding_deg, edge_rounding_deg, apodization_deg, ptsrc_radius_arcmin, num_ptsrcs) (src/masking.jl:1-67;
+ *      load_sim's pixel_mask_kwargs, src/dataset.jl:279-281): apodised border and point-source mask on the device.  Widths are in PIXELS: the
+ *      host converts with deg2npix(x) = round(x / θpix * 60) and arcmin2npix(x) = round(x / θpix), round half to even (:11-12).  All arithmetic
+ *      is int32 or double whatever the context's precision; nothing is accumulated with atomics, results are bit-identical between runs.
+ *   cmbl_edt_sq: d2[x][y] (int32, laid out like a map plane) = squared Euclidean distance from pixel (y, x) to the nearest non-zero byte of
+ *      feat[x][y] (ImageMorphology.feature_transform + norm, :42-43, 48-49), exact.  A plane without a feature is CMBL_ERR_ARG (d2 is then
+ *      not meaningful).  Synchronises the context's stream.
+ *   cmbl_make_mask: `src_yx_host`: nsrc pairs (y, x), 0-based, on the HOST (sim_ptsrcs, :60-67, with the positions given; duplicates allowed);
+ *      `out_map_dev`: one map plane (Ny, Nx, 1, 1) in the context's precision.  With boundary = all pixels but the outer `pad` rows and columns
+ *      (:31-38), bleed = d(nearest source) < src_w (:40-44, decided as d2 < src_w^2 on integers), ptsrc = !bleed and
+ *      cos_apod(img, w, s) = (1 - cos(min(d, w) / w * pi)) / 2, d the distance to the nearest false pixel of img, filtered (s > 0) BEFORE the
+ *      clamp with Kernel.gaussian(s) of ImageFiltering.jl: per axis 4 s + 1 taps exp(-x^2 / 2 s^2) normalised to sum 1, border "replicate" (:46-54):
+ *        apod_w == 0:  boundary & ptsrc, values in {0, 1} (:17; round_w is ignored)
+ *        apod_w  > 0:  cos_apod(boundary, apod_w, round_w) * cos_apod(ptsrc, src_w) (:19-20); round_w == 0: no filter (`0 != false` is false)
+ *      nsrc == 0: the point-source factor is 1 (:14, 19).  The result is rounded to float32 whatever the precision (Float32.(...), :23; a
+ *      float64 context stores those values widened, T.(...) in src/dataset.jl:280).  2 pad >= min(Ny, Nx) is legal: an all-zero mask.
+ *      What the reference leaves undefined is CMBL_ERR_ARG, checked before any launch: a negative width or count; apod_w > 0 with pad == 0 (no
+ *      false pixel to measure to); nsrc > 0 with src_w == 0; a source outside the map; nsrc > 0 without positions.  round_w > 1024 (4097 taps,
+ *      wider than any map) is CMBL_ERR_ARG as well.  Synchronises the context's stream; the scratch planes live for the call only. */
+int cmbl_edt_sq(cmbl_ctx* ctx, const uint8_t* feat_dev, int32_t* d2_dev);
+int cmbl_make_mask(cmbl_ctx* ctx, const int32_t* src_yx_host, int nsrc, int pad, int apod_w, int round_w, int src_w, void* out_map_dev);
+
 /* ---- small helpers used by the drivers above the hot kernels
  * axpby: out = a[b]*x + b[b]*y per batch slot (y may be NULL) -- the FieldTuple / Field broadcasts of the CG, line-search
  *        and leapfrog updates (src/numerical_algorithms.jl:102-107, src/sampling.jl:29-31).

@@ -595,6 +595,33 @@ function CMBLensing.get_Cℓ(f₁::BaseField{B1,<:ProjLambert,<:Any,<:ROCArray},
     nbatch(f₁) == 1 ? res[1] : res
 end
 
+# `make_mask` (src/masking.jl:1-24; `make_mask(f::LambertField)`, src/proj_lambert.jl:464) for device-backed flat-sky fields: ONE `cmbl_make_mask`
+# call (include/cmblens.h has the semantics) instead of ImageMorphology / ImageFiltering on the host.  Keywords, defaults, the unit conversion and
+# the draw of the point sources (`rand(rng, 1:Ny)`, then `rand(rng, 1:Nx)`, per source) are the reference's, so a given `rng` puts the holes where the
+# reference does; the mask comes back on the device in the field's precision, its values Float32 numbers like upstream's.
+function CMBLensing.make_mask(rng::Random.AbstractRNG, f::BaseField{B,<:ProjLambert,<:Any,<:ROCArray};
+                              edge_padding_deg=2, edge_rounding_deg=1, apodization_deg=1, ptsrc_radius_arcmin=7,
+                              num_ptsrcs=round(Int, f.Ny * f.Nx * (f.θpix/60)^2 * 120/100)) where {B}
+    θpix = f.θpix
+    deg2npix(x) = round(Int, x/θpix*60)
+    arcmin2npix(x) = round(Int, x/θpix)
+    yx = Cint[]
+    for i in 1:num_ptsrcs
+        push!(yx, rand(rng, 1:f.Ny) - 1)
+        push!(yx, rand(rng, 1:f.Nx) - 1)
+    end
+    boolean = apodization_deg in (false, 0)
+    apod_w = boolean ? 0 : deg2npix(apodization_deg)
+    (boolean || apod_w > 0) || throw(ArgumentError("apodization_deg is below half a pixel"))
+    round_w = edge_rounding_deg == false ? 0 : deg2npix(edge_rounding_deg)
+    out = similar(f.arr, real(f.T), (f.Ny, f.Nx))
+    GC.@preserve yx out chk(ccall((:cmbl_make_mask, lib), Cint, (Ptr{Cvoid}, Ptr{Cint}, Cint, Cint, Cint, Cint, Cint, Ptr{Cvoid}),
+                                  hip_ctx(f.metadata).h, isempty(yx) ? C_NULL : yx, num_ptsrcs, deg2npix(edge_padding_deg), apod_w, round_w,
+                                  arcmin2npix(ptsrc_radius_arcmin), devptr(out)))
+    BaseField{Map}(out, f.metadata)
+end
+CMBLensing.make_mask(f::BaseField{B,<:ProjLambert,<:Any,<:ROCArray}; kwargs...) where {B} = CMBLensing.make_mask(Random.default_rng(), f; kwargs...)
+
 # device RNG for `simulate` / `randn!` (src/specialops.jl:6, src/base_fields.jl:169-170): counter-based Philox4x32-10
 mutable struct HIPPhilox <: Random.AbstractRNG
     seed   :: UInt64
