@@ -523,6 +523,76 @@ int cmbl_make_mask(cmbl_ctx* ctx, const int32_t* src_yx_host, int nsrc, int pad,
   });
 }
 
+// ---- ProjEquiRect (src/proj_equirect.jl) -----------------------------------------------------------------------------------
+// ProjEquiRect(; Ny, Nx, θspan, φspan) (:71-81, 112-120): host, double, no context
+int cmbl_equirect_geometry_host(int Ny, int Nx, const double* theta_span, const double* phi_span, double* theta, double* phi,
+                                double* theta_edges, double* phi_edges, double* omega, double* lx) {
+  return guard([&] {
+    NOTNULL(theta_span); NOTNULL(phi_span);
+    CMBL_REQUIRE(Ny >= 2 && Nx >= 2 && Ny <= 4096 && Nx <= 4096, ERR_SHAPE, "Ny and Nx must lie in [2, 4096]");
+    CMBL_REQUIRE(theta_span[0] != theta_span[1] && phi_span[0] != phi_span[1], ERR_ARG, "equirect_geometry: an empty span");
+    equirect_geometry(Ny, Nx, theta_span, phi_span, theta, phi, theta_edges, phi_edges, omega, lx);
+  });
+}
+// AzFourier / Map (:149-157), QUAzFourier / QUMap (:160-178)
+int cmbl_equirect_convert(cmbl_ctx* ctx, int bi, const void* in, int bo, void* out, int npol, int B) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(in); NOTNULL(out);
+    CMBL_REQUIRE((bi == CMBL_MAP || bi == CMBL_AZFOURIER) && (bo == CMBL_MAP || bo == CMBL_AZFOURIER), ERR_ARG, "equirect_convert: the bases are CMBL_MAP and CMBL_AZFOURIER");
+    CMBL_REQUIRE(npol == 1 || npol == 2, ERR_ARG, "equirect_convert: npol must be 1 or 2 (IQUAzFourier has no transform in the reference)");
+    CMBL_REQUIRE(B >= 1 && B <= 65535, ERR_SHAPE, "equirect_convert: nbatch must lie in [1, 65535]");
+    CMBL_REQUIRE(npol == 1 || ctx->p->Nx % 2 == 0, ERR_SHAPE, "equirect_convert: QUAzFourier needs an even Nx (src/proj_equirect.jl:166 is a dimension mismatch otherwise)");
+    CMBL_REQUIRE(in != out, ERR_ARG, "equirect_convert: in and out must not be the same array");
+    BY_DTYPE(ctx, do_eq_convert, ctx, bi, in, bo, out, npol, B);
+  });
+}
+#define EQ_N_OK(ctx, n) CMBL_REQUIRE((n) == (ctx)->p->Ny || (n) == 2 * (ctx)->p->Ny, ERR_SHAPE, "equirect: n must be Ny or 2 Ny")
+// M * f, M' * f (:230-240)
+int cmbl_equirect_block_apply(cmbl_ctx* ctx, const void* blocks, int blocks_complex, int n, int adjoint, const void* in, void* out, int B) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(blocks); NOTNULL(in); NOTNULL(out);
+    EQ_N_OK(ctx, n);
+    CMBL_REQUIRE(B >= 1, ERR_SHAPE, "equirect_block_apply: nbatch >= 1");
+    CMBL_REQUIRE(in != out && blocks != out, ERR_ARG, "equirect_block_apply: out must not alias an input");
+    BY_DTYPE(ctx, do_eq_apply, ctx, blocks, blocks_complex != 0, n, adjoint != 0, in, out, B);
+  });
+}
+// M1 * M2, M1' * M2, M1 * M2' (:254-269)
+int cmbl_equirect_block_matmul(cmbl_ctx* ctx, const void* A, int adjA, const void* B, int adjB, int blocks_complex, int n, void* out) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(A); NOTNULL(B); NOTNULL(out);
+    EQ_N_OK(ctx, n);
+    CMBL_REQUIRE(!(adjA && adjB), ERR_ARG, "equirect_block_matmul: the reference has no product of two adjoints");
+    CMBL_REQUIRE(out != A && out != B, ERR_ARG, "equirect_block_matmul: out must not alias an input");
+    BY_DTYPE(ctx, do_eq_matmul, ctx, A, adjA != 0, B, adjB != 0, blocks_complex != 0, n, out);
+  });
+}
+// dot(M1', M2) (:358-360)
+int cmbl_equirect_block_dot(cmbl_ctx* ctx, const void* A, const void* B, int blocks_complex, int n, double* out_host) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(A); NOTNULL(B); NOTNULL(out_host);
+    EQ_N_OK(ctx, n);
+    BY_DTYPE(ctx, do_eq_dot, ctx, A, B, blocks_complex != 0, n, out_host);
+  });
+}
+// Cℓ_to_Beam(:I) (:505-515): blocks[j, k, m] *= w[k]
+int cmbl_equirect_block_scale_columns(cmbl_ctx* ctx, void* blocks, int blocks_complex, int n, const double* w_host, int nw) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(blocks); NOTNULL(w_host);
+    EQ_N_OK(ctx, n);
+    CMBL_REQUIRE(nw == n, ERR_SHAPE, "equirect_block_scale_columns: one weight per column");
+    BY_DTYPE(ctx, do_eq_scale_columns, ctx, blocks, blocks_complex != 0, n, w_host);
+  });
+}
+// Cℓ_to_Beam(:P) (:517-533): [B 0; 0 B] * diag(Ω, Ω)
+int cmbl_equirect_beam_pol(cmbl_ctx* ctx, const void* blocksI_real, const double* omega_host, void* out_complex) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(blocksI_real); NOTNULL(omega_host); NOTNULL(out_complex);
+    CMBL_REQUIRE(blocksI_real != out_complex, ERR_ARG, "equirect_beam_pol: out must not alias the input");
+    BY_DTYPE(ctx, do_eq_beam_pol, ctx, blocksI_real, omega_host, out_complex);
+  });
+}
+
 #ifdef CMBL_STAMPS
 // phase timestamps of the last stamped launch (tools/gpu_stamps*.py) of the translation unit CMBL_STAMPS_TU (kernels_fft.hpp CMBL_STAMPS_READER)
 int cmbl_debug_stamps(unsigned long long* out_host, int n) {

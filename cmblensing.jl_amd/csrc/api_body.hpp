@@ -229,5 +229,11 @@ template <typename T> void do_get_cl(cmbl_ctx* ctx, cmbl_clbins* bins, int basis
 }
 template <typename T> void do_edt_sq(cmbl_ctx* ctx, const uint8_t* feat, int32_t* d2) { edt_sq_checked<T>(C<T>(ctx), feat, d2); }
 template <typename T> void do_make_mask(cmbl_ctx* ctx, const MaskArgs& m, void* out) { make_mask<T>(C<T>(ctx), m, (T*)out); }
+template <typename T> void do_eq_convert(cmbl_ctx* ctx, int bi, const void* in, int bo, void* out, int npol, int B) { equirect_convert<T>(C<T>(ctx), bi, in, bo, out, npol, B); }
+template <typename T> void do_eq_apply(cmbl_ctx* ctx, const void* blocks, bool cplx, int n, bool adjoint, const void* in, void* out, int B) { equirect_block_apply<T>(C<T>(ctx), blocks, cplx, n, adjoint, in, out, B); }
+template <typename T> void do_eq_matmul(cmbl_ctx* ctx, const void* A, bool adjA, const void* Bm, bool adjB, bool cplx, int n, void* out) { equirect_block_matmul<T>(C<T>(ctx), A, adjA, Bm, adjB, cplx, n, out); }
+template <typename T> void do_eq_dot(cmbl_ctx* ctx, const void* A, const void* Bm, bool cplx, int n, double* out) { equirect_block_dot<T>(C<T>(ctx), A, Bm, cplx, n, out); }
+template <typename T> void do_eq_scale_columns(cmbl_ctx* ctx, void* blocks, bool cplx, int n, const double* w) { equirect_scale_columns<T>(C<T>(ctx), blocks, cplx, n, w); }
+template <typename T> void do_eq_beam_pol(cmbl_ctx* ctx, const void* blocksI, const double* omega, void* out) { equirect_beam_pol<T>(C<T>(ctx), blocksI, omega, out); }
 
 }  // namespace cmbl

@@ -23,6 +23,7 @@
 #include "engine_bilinear.hpp"
 #include "engine_powerlens.hpp"
 #include "engine_mask.hpp"
+#include "engine_equirect.hpp"
 #include "../../include/cmblens.h"
 
 struct cmbl_ctx { std::unique_ptr<cmbl::CtxBase> p; };
@@ -63,7 +64,13 @@ namespace cmbl {
   X(T, do_ud_grade, (cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv, int aa, int bi, const void* in, int bo, void* out, int P, int B)) \
   X(T, do_get_cl, (cmbl_ctx* ctx, cmbl_clbins* bins, int basis, const void* f1, const void* f2, int P, int B, const ClPairs& pr, int moments, double* out)) \
   X(T, do_edt_sq, (cmbl_ctx* ctx, const uint8_t* feat, int32_t* d2)) \
-  X(T, do_make_mask, (cmbl_ctx* ctx, const MaskArgs& m, void* out))
+  X(T, do_make_mask, (cmbl_ctx* ctx, const MaskArgs& m, void* out)) \
+  X(T, do_eq_convert, (cmbl_ctx* ctx, int bi, const void* in, int bo, void* out, int npol, int B)) \
+  X(T, do_eq_apply, (cmbl_ctx* ctx, const void* blocks, bool cplx, int n, bool adjoint, const void* in, void* out, int B)) \
+  X(T, do_eq_matmul, (cmbl_ctx* ctx, const void* A, bool adjA, const void* Bm, bool adjB, bool cplx, int n, void* out)) \
+  X(T, do_eq_dot, (cmbl_ctx* ctx, const void* A, const void* Bm, bool cplx, int n, double* out)) \
+  X(T, do_eq_scale_columns, (cmbl_ctx* ctx, void* blocks, bool cplx, int n, const double* w)) \
+  X(T, do_eq_beam_pol, (cmbl_ctx* ctx, const void* blocksI, const double* omega, void* out))
 
 #define CMBL_API_DECLARE(T, name, params) template <typename T> void name params;
 #define CMBL_API_INSTANTIATE(T, name, params) template void name<T> params;

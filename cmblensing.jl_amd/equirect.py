@@ -1,0 +1,340 @@
+"""The reference's second Cartesian projection (src/proj_equirect.jl) on top of the C ABI: `ProjEquiRect`, fields in the Map / AzFourier
+(QUMap / QUAzFourier) bases and the block-diagonal operators `BlockDiagEquiRect`.
+
+Tensor layouts are the reference's arrays read row-major: maps (B, P, Nx, Ny) real == Julia (Ny, Nx, P, B); AzFourier fields (B, Nx//2+1, n)
+complex == Julia (n, Nx÷2+1, B) with n = Ny (I) or 2 Ny (QU); operator blocks (Nx//2+1, n, n) indexed [m, q, p] == Julia blocks[p, q, m].
+`blocks_from_ref` / `blocks_to_ref` move between that and NumPy arrays indexed [p, q, m] like the reference's.
+
+On the device: the four transforms, `M * f`, `M' * f`, the three operator products, `dot(M1', M2)` and the beams.  On the host, once per
+operator, in float64 and batched over m (numpy.linalg): `sqrt` (SVD, :313-323), `pinv`, `logabsdet` / `logdet`, `solve` (`\\`) and `rdiv`
+(`/`) of two operators, and `+`, `-`, scalar `*`, `/` (torch, elementwise).  `sqrt` / `pinv` / `logabsdet` are cached on the object like the
+reference's `Ref`s.  NOT here: `Cℓ_to_Cov` (defined through CirculantCov.jl only, :430-503) -- blocks come from the caller; the AD rules;
+lensing on this projection."""
+import ctypes
+
+import numpy as np
+import torch
+
+from .lib import load_library, check
+from .engine import ProjLambert, MAP, _ptr
+
+AZFOURIER = 3
+_PD = ctypes.POINTER(ctypes.c_double)
+
+
+def equirect_geometry(Ny, Nx, theta_span, phi_span):
+    """ProjEquiRect(; Ny, Nx, θspan, φspan) (src/proj_equirect.jl:71-81, 112-120) on the host in double (`cmbl_equirect_geometry_host`; needs no
+    device): dict of theta (Ny), phi (Nx), theta_edges (Ny+1), phi_edges (Nx+1), omega (Ny) and lx (Ny, Nx)."""
+    lib = load_library()
+    Ny, Nx = int(Ny), int(Nx)
+    ts, ps = np.array(theta_span, dtype=np.float64), np.array(phi_span, dtype=np.float64)
+    g = {"theta": np.empty(Ny), "phi": np.empty(Nx), "theta_edges": np.empty(Ny + 1), "phi_edges": np.empty(Nx + 1), "omega": np.empty(Ny),
+         "lx": np.empty((Nx, Ny))}
+    p = lambda a: a.ctypes.data_as(_PD)
+    check(lib.cmbl_equirect_geometry_host(Ny, Nx, p(ts), p(ps), p(g["theta"]), p(g["phi"]), p(g["theta_edges"]), p(g["phi_edges"]), p(g["omega"]), p(g["lx"])))
+    g["lx"] = np.ascontiguousarray(g["lx"].T)                                # the library writes the Julia array (Ny contiguous)
+    return g
+
+
+class ProjEquiRect:
+    """`ProjEquiRect(; Ny, Nx, θspan, φspan, T)` (src/proj_equirect.jl:83-127).  The spans are in radians, in either order.  The geometry fields
+    (`theta`, `phi`, `theta_edges`, `phi_edges`, `omega`, `lx`) are NumPy arrays of the precision `T`, like the reference's `T.(…)`."""
+
+    def __init__(self, Ny, Nx, theta_span, phi_span, T=torch.float32, device=0):
+        self.Ny, self.Nx, self.Mh = int(Ny), int(Nx), int(Nx) // 2 + 1
+        self.theta_span, self.phi_span = tuple(sorted(float(v) for v in theta_span)), tuple(sorted(float(v) for v in phi_span))
+        self.T = T
+        self.CT = torch.complex64 if T == torch.float32 else torch.complex128
+        npT = np.float32 if T == torch.float32 else np.float64
+        for k, v in equirect_geometry(Ny, Nx, theta_span, phi_span).items():
+            setattr(self, k, v.astype(npT))
+        self._ctx = ProjLambert(Ny, Nx, 1.0, T, device)                      # the context: sizes, precision, stream, scratch (its pixel size is not used)
+        self.lib, self._h, self.device = self._ctx.lib, self._ctx._h, self._ctx.device
+
+    def __eq__(self, o):
+        return isinstance(o, ProjEquiRect) and (self.Ny, self.Nx, self.theta_span, self.phi_span, self.T, self.device) == \
+            (o.Ny, o.Nx, o.theta_span, o.phi_span, o.T, o.device)
+
+    __hash__ = None
+
+    def synchronize(self):
+        self._ctx.synchronize()
+
+    def tensor(self, a):
+        return self._ctx.tensor(a)
+
+
+def _same_proj(a, b):
+    if a is not b and a != b:
+        raise ValueError("fields / operators of different ProjEquiRect projections")      # promote_metadata_strict
+
+
+class EquiRectField:
+    """A spin-0 (P = 1) or spin-2 (P = 2) field on a ProjEquiRect in the MAP or AZFOURIER basis.  `arr`: MAP (B, P, Nx, Ny) real; AZFOURIER
+    (B, Nx//2+1, P Ny) complex."""
+
+    def __init__(self, proj, arr, basis):
+        self.proj, self.basis = proj, int(basis)
+        t = proj.tensor(arr)
+        if self.basis == MAP:
+            if t.dim() == 3:
+                t = t[None]
+            ok = t.dim() == 4 and t.shape[1] in (1, 2) and tuple(t.shape[2:]) == (proj.Nx, proj.Ny) and t.dtype == proj.T
+            self.P = int(t.shape[1]) if ok else 0
+        elif self.basis == AZFOURIER:
+            if t.dim() == 2:
+                t = t[None]
+            ok = t.dim() == 3 and t.shape[1] == proj.Mh and t.shape[2] in (proj.Ny, 2 * proj.Ny) and t.dtype == proj.CT
+            self.P = int(t.shape[2]) // proj.Ny if ok else 0
+        else:
+            raise ValueError("EquiRectField: the basis is MAP or AZFOURIER")
+        if not ok:
+            raise ValueError(f"EquiRectField: array of shape {tuple(t.shape)} / {t.dtype} does not fit a {proj.Ny} x {proj.Nx} projection in basis {basis}")
+        if self.P == 2 and proj.Nx % 2:
+            raise ValueError("EquiRectField: QU fields need an even Nx (src/proj_equirect.jl:166)")
+        self.arr = t.contiguous()
+        self.B = int(t.shape[0])
+
+    def to(self, basis):
+        """Map <-> AzFourier, QUMap <-> QUAzFourier (src/proj_equirect.jl:149-178)"""
+        if basis == self.basis:
+            return self
+        p = self.proj
+        if basis == MAP:
+            out = torch.empty((self.B, self.P, p.Nx, p.Ny), dtype=p.T, device=p.device)
+        elif basis == AZFOURIER:
+            out = torch.empty((self.B, p.Mh, self.P * p.Ny), dtype=p.CT, device=p.device)
+        else:
+            raise ValueError("EquiRectField.to: the basis is MAP or AZFOURIER")
+        check(p.lib.cmbl_equirect_convert(p._h, self.basis, _ptr(self.arr), basis, _ptr(out), self.P, self.B))
+        return EquiRectField(p, out, basis)
+
+    def dot(self, other):
+        """dot(a, b) = dot(Ł(a).arr, Ł(b).arr) (src/proj_equirect.jl:355): the plain dot product of the map arrays, batch included"""
+        _same_proj(self.proj, other.proj)
+        return float(torch.dot(self.to(MAP).arr.reshape(-1), other.to(MAP).arr.reshape(-1)))
+
+    # f[:Ix], f[:Il] (spin 0); f[:Qx], f[:Ux], f[:Px], f[:Pl] (spin 2) (src/proj_equirect.jl:181-196)
+    def __getitem__(self, k):
+        if self.P == 1 and k == "Ix":
+            return self.to(MAP).arr[:, 0]
+        if self.P == 1 and k == "Il":
+            return self.to(AZFOURIER).arr
+        if self.P == 2 and k in ("Qx", "Ux"):
+            return self.to(MAP).arr[:, 0 if k == "Qx" else 1]
+        if self.P == 2 and k == "Px":
+            m = self.to(MAP).arr
+            return torch.complex(m[:, 0], m[:, 1])
+        if self.P == 2 and k == "Pl":
+            return self.to(AZFOURIER).arr
+        raise KeyError(f"invalid index {k!r} for a spin-{0 if self.P == 1 else 2} EquiRectField")
+
+    def __mul__(self, a):
+        return EquiRectField(self.proj, self.arr * a, self.basis)
+
+    __rmul__ = __mul__
+
+    def __add__(self, o):
+        _same_proj(self.proj, o.proj)
+        return EquiRectField(self.proj, self.arr + o.to(self.basis).arr, self.basis)
+
+    def __sub__(self, o):
+        _same_proj(self.proj, o.proj)
+        return EquiRectField(self.proj, self.arr - o.to(self.basis).arr, self.basis)
+
+
+def blocks_from_ref(a):
+    """NumPy blocks indexed [p, q, m] like the reference's -> the row-major array [m, q, p] the device holds"""
+    return np.ascontiguousarray(np.transpose(np.asarray(a), (2, 1, 0)))
+
+
+def blocks_to_ref(t):
+    """device blocks [m, q, p] -> NumPy array indexed [p, q, m]"""
+    return np.transpose((t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)), (2, 1, 0))
+
+
+class _Adjoint:
+    def __init__(self, parent):
+        self.parent = parent
+
+    @property
+    def H(self):
+        return self.parent
+
+    def __mul__(self, x):
+        if isinstance(x, EquiRectField):
+            return self.parent._apply(x, True)
+        if isinstance(x, BlockDiagEquiRect):
+            return self.parent._matmul(x, True, False)
+        if isinstance(x, _Adjoint):
+            raise TypeError("the product of two adjoints is not defined (src/proj_equirect.jl:254-269)")
+        return (self.parent * np.conj(x)).H                                  # (conj(a) * M.parent)' (:305-306)
+
+    __matmul__ = __mul__
+
+    def dot(self, M2):
+        """dot(M1', M2) = Σ conj(M1[q, p, m]) M2[p, q, m] (src/proj_equirect.jl:358-360)"""
+        return self.parent._dot(M2)
+
+
+class BlockDiagEquiRect:
+    """`BlockDiagEquiRect{B}(blocks, proj)` (src/proj_equirect.jl:209-222): one n x n block per azimuthal mode m, n = Ny (AzFourier) or 2 Ny
+    (QUAzFourier), real or complex.  `blocks`: device tensor or array (Nx//2+1, n, n) indexed [m, q, p] (`blocks_from_ref` converts the
+    reference's [p, q, m])."""
+
+    def __init__(self, blocks, proj, basis=AZFOURIER):
+        if basis != AZFOURIER:
+            raise ValueError("BlockDiagEquiRect: the basis is AZFOURIER")
+        t = proj.tensor(blocks)
+        if t.dim() != 3 or t.shape[0] != proj.Mh or t.shape[1] != t.shape[2] or t.shape[1] not in (proj.Ny, 2 * proj.Ny):
+            raise ValueError(f"BlockDiagEquiRect: blocks of shape {tuple(t.shape)}, expected ({proj.Mh}, n, n) with n = Ny or 2 Ny")
+        self.proj, self.basis, self.blocks = proj, basis, t.contiguous()
+        self.n, self.complex = int(t.shape[1]), bool(t.is_complex())
+        self._sqrt = self._pinv = self._logabsdet = None
+
+    # ---- device products
+    def _apply(self, f, adjoint):
+        _same_proj(self.proj, f.proj)
+        f = f.to(AZFOURIER)                                                  # M * B(f) (:228)
+        if f.arr.shape[2] != self.n:
+            raise ValueError(f"operator blocks of size {self.n} on a field with {f.arr.shape[2]} rows")
+        out = torch.empty_like(f.arr)
+        p = self.proj
+        check(p.lib.cmbl_equirect_block_apply(p._h, _ptr(self.blocks), int(self.complex), self.n, int(adjoint), _ptr(f.arr), _ptr(out), f.B))
+        return EquiRectField(p, out, AZFOURIER)
+
+    def _pair(self, o):
+        _same_proj(self.proj, o.proj)
+        if o.n != self.n:
+            raise ValueError("operators of different block sizes")
+        a, b = self.blocks, o.blocks
+        if self.complex != o.complex:
+            a, b = a.to(self.proj.CT), b.to(self.proj.CT)
+        return a, b
+
+    def _matmul(self, o, adjA, adjB):
+        a, b = self._pair(o)
+        out = torch.empty_like(a)
+        p = self.proj
+        check(p.lib.cmbl_equirect_block_matmul(p._h, _ptr(a), int(adjA), _ptr(b), int(adjB), int(a.is_complex()), self.n, _ptr(out)))
+        return BlockDiagEquiRect(out, p)
+
+    def _dot(self, o):
+        a, b = self._pair(o)
+        out = (ctypes.c_double * 2)()
+        p = self.proj
+        check(p.lib.cmbl_equirect_block_dot(p._h, _ptr(a), _ptr(b), int(a.is_complex()), self.n, out))
+        return complex(out[0], out[1])
+
+    @property
+    def H(self):
+        return _Adjoint(self)
+
+    def __mul__(self, x):
+        if isinstance(x, EquiRectField):
+            return self._apply(x, False)
+        if isinstance(x, BlockDiagEquiRect):
+            return self._matmul(x, False, False)
+        if isinstance(x, _Adjoint):
+            return self._matmul(x.parent, False, True)
+        return BlockDiagEquiRect(self.blocks * x, self.proj)
+
+    __matmul__ = __mul__
+
+    def __rmul__(self, a):
+        return BlockDiagEquiRect(self.blocks * a, self.proj)
+
+    def __truediv__(self, x):
+        if isinstance(x, BlockDiagEquiRect):
+            return self.rdiv(x)
+        return BlockDiagEquiRect(self.blocks / x, self.proj)
+
+    def __add__(self, o):
+        a, b = self._pair(o)
+        return BlockDiagEquiRect(a + b, self.proj)
+
+    def __sub__(self, o):
+        a, b = self._pair(o)
+        return BlockDiagEquiRect(a - b, self.proj)
+
+    def scale_columns(self, w):
+        """blocks[j, k, m] *= w[k] in place (the step of Cℓ_to_Beam(:I), src/proj_equirect.jl:512)"""
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        p = self.proj
+        check(p.lib.cmbl_equirect_block_scale_columns(p._h, _ptr(self.blocks), int(self.complex), self.n, w.ctypes.data_as(_PD), w.size))
+        self._sqrt = self._pinv = self._logabsdet = None
+        return self
+
+    # ---- host linear algebra, once per operator, float64, batched over m
+    def _host(self):
+        a = self.blocks.detach().cpu().numpy().transpose(0, 2, 1)            # [m, p, q]
+        return a.astype(np.complex128 if self.complex else np.float64)
+
+    def _from_host(self, a):
+        a = np.ascontiguousarray(np.transpose(a, (0, 2, 1)))
+        if not self.complex:
+            a = a.real
+        return BlockDiagEquiRect(self.proj.tensor(a), self.proj)
+
+    def sqrt(self):
+        """U * Diagonal(sqrt.(S)) * V' of the SVD of every block (src/proj_equirect.jl:313-323)"""
+        if self._sqrt is None:
+            u, s, vh = np.linalg.svd(self._host())
+            self._sqrt = self._from_host((u * np.sqrt(s)[:, None, :]) @ vh)
+        return self._sqrt
+
+    def pinv(self):
+        if self._pinv is None:
+            self._pinv = self._from_host(np.linalg.pinv(self._host()))
+        return self._pinv
+
+    def logabsdet(self):
+        """(Σ log|det|, Π sign) over the blocks (src/proj_equirect.jl:342-347)"""
+        if self._logabsdet is None:
+            sign, lad = np.linalg.slogdet(self._host())
+            self._logabsdet = (float(lad.sum()), complex(np.prod(sign)))
+        return self._logabsdet
+
+    def logdet(self):
+        l, s = self.logabsdet()
+        v = l + np.log(s)
+        return float(v.real) if abs(v.imag) < 1e-12 else v
+
+    def solve(self, o):
+        """M₁ \\ M₂, blockwise (src/proj_equirect.jl:274-282)"""
+        _same_proj(self.proj, o.proj)
+        r = np.linalg.solve(self._host(), o._host())
+        return (self if self.complex or not o.complex else o)._from_host(r)
+
+    def rdiv(self, o):
+        """M₁ / M₂ = M₁ M₂⁻¹, blockwise"""
+        _same_proj(self.proj, o.proj)
+        a, b = self._host(), o._host()
+        r = np.conj(np.transpose(np.linalg.solve(np.conj(np.transpose(b, (0, 2, 1))), np.conj(np.transpose(a, (0, 2, 1)))), (0, 2, 1)))
+        return (self if self.complex or not o.complex else o)._from_host(r)
+
+
+def Cl_to_Beam(pol, cov_I_blocks, proj):
+    """Cℓ_to_Beam(:I / :P) (src/proj_equirect.jl:505-533) from the real blocks of Cℓ_to_Cov(:I) (which the caller supplies; the reference makes
+    them through CirculantCov.jl): `"I"`: blocks[j, k, m] * Ω[k]; `"P"`: [B 0; 0 B] * diag(Ω, Ω), complex 2Ny blocks."""
+    M = cov_I_blocks if isinstance(cov_I_blocks, BlockDiagEquiRect) else BlockDiagEquiRect(cov_I_blocks, proj)
+    _same_proj(M.proj, proj)
+    if M.complex or M.n != proj.Ny:
+        raise ValueError("Cl_to_Beam: the :I covariance has real Ny x Ny blocks")
+    om = np.ascontiguousarray(proj.omega, dtype=np.float64)
+    if pol == "I":
+        return BlockDiagEquiRect(M.blocks.clone(), proj).scale_columns(om)
+    if pol == "P":
+        out = torch.empty((proj.Mh, 2 * proj.Ny, 2 * proj.Ny), dtype=proj.CT, device=proj.device)
+        check(proj.lib.cmbl_equirect_beam_pol(proj._h, _ptr(M.blocks), om.ctypes.data_as(_PD), _ptr(out)))
+        return BlockDiagEquiRect(out, proj)
+    raise ValueError("Cl_to_Beam: pol is 'I' or 'P'")
+
+
+def simulate(M, seed=0, nbatch=1):
+    """simulate(rng, M) = sqrt(M) * white map (src/proj_equirect.jl:399-405), the white map from the device generator (Philox keyed by
+    seed + slot).  Returns an AZFOURIER field, like the reference's `M * f`."""
+    p = M.proj
+    P = M.n // p.Ny
+    white = p._ctx.randn([int(seed) + b for b in range(int(nbatch))], 0, P)
+    return M.sqrt() * EquiRectField(p, white, MAP)

@@ -87,6 +87,13 @@ SIGNATURES = {
     "cmbl_powerlens_apply": [_vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci],
     "cmbl_edt_sq": [_vp, _vp, _vp],
     "cmbl_make_mask": [_vp, _pci, _ci, _ci, _ci, _ci, _ci, _vp],
+    "cmbl_equirect_geometry_host": [_ci, _ci, _pd, _pd, _pd, _pd, _pd, _pd, _pd, _pd],
+    "cmbl_equirect_convert": [_vp, _ci, _vp, _ci, _vp, _ci, _ci],
+    "cmbl_equirect_block_apply": [_vp, _vp, _ci, _ci, _ci, _vp, _vp, _ci],
+    "cmbl_equirect_block_matmul": [_vp, _vp, _ci, _vp, _ci, _ci, _ci, _vp],
+    "cmbl_equirect_block_dot": [_vp, _vp, _vp, _ci, _ci, _pd],
+    "cmbl_equirect_block_scale_columns": [_vp, _vp, _ci, _ci, _pd, _ci],
+    "cmbl_equirect_beam_pol": [_vp, _vp, _pd, _vp],
 }
 SYMBOLS = list(OTHER_RETURNS) + list(SIGNATURES)
 

@@ -46,8 +46,9 @@ enum { CMBL_OK = 0, CMBL_ERR_ARG = 1, CMBL_ERR_SHAPE = 2, CMBL_ERR_HIP = 3, CMBL
 enum { CMBL_F32 = 0, CMBL_F64 = 1 };
 
 /* bases (src/generic.jl:42-98): MAP = Map/QUMap/IQUMap (LenseBasis), FOURIER = Fourier/QUFourier/
- * IQUFourier (DerivBasis), HARMONIC = Fourier/EBFourier/IEBFourier (basis covariances are diagonal in) */
-enum { CMBL_MAP = 0, CMBL_FOURIER = 1, CMBL_HARMONIC = 2 };
+ * IQUFourier (DerivBasis), HARMONIC = Fourier/EBFourier/IEBFourier (basis covariances are diagonal in).
+ * AZFOURIER = AzFourier/QUAzFourier of ProjEquiRect (src/proj_equirect.jl:149-178): accepted by cmbl_equirect_convert only */
+enum { CMBL_MAP = 0, CMBL_FOURIER = 1, CMBL_HARMONIC = 2, CMBL_AZFOURIER = 3 };
 
 /* LenseFlow operator modes (src/flowops.jl:11-14) */
 enum { CMBL_FLOW_FWD = 0,     /* L * f   : velocity,  t 0->1 */
@@ -335,6 +336,43 @@ int cmbl_powerlens_apply(cmbl_powerlens* L, int mode, int basis_in, const void* 
  *      wider than any map) is CMBL_ERR_ARG as well.  Synchronises the context's stream; the scratch planes live for the call only. */
 int cmbl_edt_sq(cmbl_ctx* ctx, const uint8_t* feat_dev, int32_t* d2_dev);
 int cmbl_make_mask(cmbl_ctx* ctx, const int32_t* src_yx_host, int nsrc, int pad, int apod_w, int round_w, int src_w, void* out_map_dev);
+
+/* ---- ProjEquiRect (src/proj_equirect.jl): the equirectangular projection, its azimuthal Fourier bases and block-diagonal operators.
+ *      Arrays are the reference's, column-major: maps (Ny, Nx, npol, nbatch) with θ contiguous; AzFourier fields (n, Nx/2+1, nbatch) complex with
+ *      n = Ny (I) or 2 Ny (QU); operators `blocks` (n, n, Nx/2+1), row index contiguous, real (blocks_complex = 0) or complex elements of the
+ *      context's precision.  The context supplies Ny, Nx, precision, stream and scratch; its pixel size is not used.  Nothing is accumulated with
+ *      atomics, results are bit-identical between runs.  NOT included: Cℓ_to_Cov (:430-503, defined through CirculantCov.jl only: blocks come from
+ *      the caller), the AD rules (:242-248, 349-351), IQUAzFourier (an alias without a transform), lensing on this projection.
+ *   cmbl_equirect_geometry_host: ProjEquiRect(; Ny, Nx, θspan, φspan) (:71-81, 112-120) on the host in double, no context and no device needed.  The
+ *      spans are sorted.  theta_edges = range(θspan, Ny+1) (Ny+1 values), theta = its midpoints (Ny); phi_edges (Nx+1) and phi (Nx) = rem2pi(·, RoundDown)
+ *      of the equispaced edges and midpoints, in [0, 2π); omega[j] = rem2pi(phi_edges[1] − phi_edges[0]) (cos θedges[j] − cos θedges[j+1]) (Ny);
+ *      lx[j + Ny i] = ifftshift(−Nx÷2 … (Nx−1)÷2)[i] · 2π / (Nx Δx[j]), Δx[j] = sin θ[j] |φspan₂ − φspan₁| / Nx (Ny × Nx).  Any output may be NULL.
+ *      Ny, Nx outside [2, 4096]: CMBL_ERR_SHAPE.
+ *   cmbl_equirect_convert: basis_in / basis_out: CMBL_MAP or CMBL_AZFOURIER (others: CMBL_ERR_ARG); equal bases copy.  npol = 1: AzFourier(f) =
+ *      rfft along φ / √Nx and Map(f) = irfft along φ · √Nx (:149-157; FFTW's c2r rule: the imaginary parts of m = 0, and of m = Nx/2 for even Nx, are
+ *      never read); any Nx.  npol = 2: QUAzFourier (:160-168): F = fft_φ(Q + iU) / √Nx, rows 0 … Ny−1 of column m hold F[:, m], rows Ny … 2Ny−1
+ *      conj(F[:, (Nx − m) mod Nx]); QUMap (:170-178): F[:, 0 … Nx/2] = the top rows, THEN F[:, (Nx − m) mod Nx] = conj(bottom rows of column m) -- columns
+ *      0 and Nx/2 are assigned twice and the second assignment wins, as in the reference -- then Q + iU = ifft_φ(F) · √Nx.  Odd Nx with npol = 2 is
+ *      CMBL_ERR_SHAPE (the reference throws a dimension mismatch, :166); npol = 3 is CMBL_ERR_ARG; `in == out` is CMBL_ERR_ARG.
+ *   cmbl_equirect_block_apply: M * f (:230-233), out[p, m, b] = Σ_q M[p, q, m] f[q, m, b]; adjoint != 0: M' * f (:237-240), with conj(M[q, p, m]).
+ *      n must be Ny or 2 Ny (CMBL_ERR_SHAPE).  Real blocks are read as real.  Every block element is fetched once per 8 batch slots.  `in == out` is
+ *      CMBL_ERR_ARG.
+ *   cmbl_equirect_block_matmul: M₁ * M₂, M₁' * M₂ (adjA), M₁ * M₂' (adjB) (:254-269), on the matrix cores (exact f32 / f64 MFMA).  Both adjoints, or
+ *      `out` aliasing an input: CMBL_ERR_ARG.  A, B and out share n and element type.
+ *   cmbl_equirect_block_dot: dot(M₁', M₂) = Σ conj(A[q, p, m]) B[p, q, m] (:358-360), accumulated in double in a fixed order; out_host = (re, im).
+ *      Synchronises the context's stream.
+ *   cmbl_equirect_block_scale_columns: blocks[j, k, m] *= w[k] in place, w rounded to the context's precision (Cℓ_to_Beam(:I), :505-515); nw != n
+ *      is CMBL_ERR_SHAPE.
+ *   cmbl_equirect_beam_pol: out (2Ny, 2Ny, Nx/2+1) complex = [B 0; 0 B] · diag(Ω, Ω) from the real blocks B (Ny, Ny, Nx/2+1) (Cℓ_to_Beam(:P), :517-533);
+ *      omega_host: Ny doubles.  The two beam calls copy their weights to the device before they return (one blocking copy). */
+int cmbl_equirect_geometry_host(int Ny, int Nx, const double* theta_span, const double* phi_span, double* theta, double* phi,
+                                double* theta_edges, double* phi_edges, double* omega, double* lx);
+int cmbl_equirect_convert(cmbl_ctx* ctx, int basis_in, const void* in, int basis_out, void* out, int npol, int nbatch);
+int cmbl_equirect_block_apply(cmbl_ctx* ctx, const void* blocks, int blocks_complex, int n, int adjoint, const void* in, void* out, int nbatch);
+int cmbl_equirect_block_matmul(cmbl_ctx* ctx, const void* A, int adjA, const void* B, int adjB, int blocks_complex, int n, void* out);
+int cmbl_equirect_block_dot(cmbl_ctx* ctx, const void* A, const void* B, int blocks_complex, int n, double* out_host);
+int cmbl_equirect_block_scale_columns(cmbl_ctx* ctx, void* blocks, int blocks_complex, int n, const double* w_host, int nw);
+int cmbl_equirect_beam_pol(cmbl_ctx* ctx, const void* blocksI_real, const double* omega_host, void* out_complex);
 
 /* ---- small helpers used by the drivers above the hot kernels
  * axpby: out = a[b]*x + b[b]*y per batch slot (y may be NULL) -- the FieldTuple / Field broadcasts of the CG, line-search

@@ -101,9 +101,18 @@ mutable struct HIPContext
         reference_exact() && chk(ccall((:cmbl_set_sum_accuracy_mode, lib), Cint, (Ptr{Cvoid}, Cint), h[], 0))
         finalizer(c -> ccall((:cmbl_ctx_destroy, lib), Cint, (Ptr{Cvoid},), c.h), new(h[], Any[]))
     end
+    # a ProjEquiRect (src/proj_equirect.jl:25-58) takes the same context: sizes, precision, stream and scratch; its pixel size is not used
+    function HIPContext(proj::CMBLensing.ProjEquiRect{T}) where {T}
+        h = Ref{Ptr{Cvoid}}()
+        chk(ccall((:cmbl_ctx_create, lib), Cint, (Cint, Cint, Cdouble, Cint, Cint, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}),
+                  proj.Ny, proj.Nx, 1.0, dtype(real(T)), AMDGPU.device_id(AMDGPU.device()) - 1,
+                  Ptr{Cvoid}(UInt(Base.unsafe_convert(Ptr{Cvoid}, AMDGPU.stream().stream))), h))
+        finalizer(c -> ccall((:cmbl_ctx_destroy, lib), Cint, (Ptr{Cvoid},), c.h), new(h[], Any[]))
+    end
 end
 const contexts = IdDict{Any,HIPContext}()                                 # one per (memoized, hence ===) ProjLambert
 hip_ctx(proj::ProjLambert) = get!(() -> HIPContext(proj), contexts, proj)
+hip_ctx(proj::CMBLensing.ProjEquiRect) = get!(() -> HIPContext(proj), contexts, proj)
 hip_ctx(f::BaseField) = hip_ctx(f.metadata)
 synchronize(ctx::HIPContext) = (chk(ccall((:cmbl_ctx_synchronize, lib), Cint, (Ptr{Cvoid},), ctx.h)); empty!(ctx.keep); nothing)
 # a temporary that is only read by an asynchronous call must outlive the call, not just the `ccall`: park it on the context; the
@@ -621,6 +630,85 @@ function CMBLensing.make_mask(rng::Random.AbstractRNG, f::BaseField{B,<:ProjLamb
     BaseField{Map}(out, f.metadata)
 end
 CMBLensing.make_mask(f::BaseField{B,<:ProjLambert,<:Any,<:ROCArray}; kwargs...) where {B} = CMBLensing.make_mask(Random.default_rng(), f; kwargs...)
+
+# ---- ProjEquiRect (src/proj_equirect.jl) for device-backed fields and operators: the azimuthal transforms (:149-178), `M*f`, `M'*f` (:230-240), the three
+# operator products (:254-269, on the matrix cores), `dot(M₁', M₂)` (:358-360) and the beams (:505-533) are one `cmbl_equirect_*` call each
+# (include/cmblens.h has the semantics, the two quirks included: QU needs an even Nx, and QUMap's second assignment wins at columns 0 and Nx÷2).
+# `sqrt`, `pinv`, `logabsdet`, `\`, `/`, `+`, `-` keep the reference's own methods (one-off setup through AMDGPU.jl's LinearAlgebra and broadcasts), and
+# so does `Cℓ_to_Cov` (CirculantCov.jl on the host, then `gpu`).
+const AZFOURIER = Cint(3)                                                    # CMBL_AZFOURIER
+eq_nbatch(a, nd) = ndims(a) > nd ? size(a, nd + 1) : 1
+function CMBLensing.AzFourier(f::BaseField{Map,<:CMBLensing.ProjEquiRect,<:Any,<:ROCArray})                     # :149-152
+    a = f.arr; B = eq_nbatch(a, 2); out = similar(a, complex(eltype(a)), (f.Ny, f.Nx ÷ 2 + 1, B))
+    GC.@preserve a out chk(ccall((:cmbl_equirect_convert, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint),
+                                 hip_ctx(f.metadata).h, MAP, devptr(a), AZFOURIER, devptr(out), 1, B))
+    CMBLensing.EquiRectAzFourier(B == 1 ? dropdims(out, dims=3) : out, f.metadata)
+end
+function CMBLensing.Map(f::BaseField{CMBLensing.AzFourier,<:CMBLensing.ProjEquiRect,<:Any,<:ROCArray})          # :154-157
+    a = f.arr; B = eq_nbatch(a, 2); out = similar(a, real(eltype(a)), (f.Ny, f.Nx, B))
+    GC.@preserve a out chk(ccall((:cmbl_equirect_convert, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint),
+                                 hip_ctx(f.metadata).h, AZFOURIER, devptr(a), MAP, devptr(out), 1, B))
+    CMBLensing.EquiRectMap(B == 1 ? dropdims(out, dims=3) : out, f.metadata)
+end
+function CMBLensing.QUAzFourier(f::BaseField{CMBLensing.QUMap,<:CMBLensing.ProjEquiRect,<:Any,<:ROCArray})      # :160-168
+    a = f.arr; B = eq_nbatch(a, 3); out = similar(a, complex(eltype(a)), (2f.Ny, f.Nx ÷ 2 + 1, B))
+    GC.@preserve a out chk(ccall((:cmbl_equirect_convert, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint),
+                                 hip_ctx(f.metadata).h, MAP, devptr(a), AZFOURIER, devptr(out), 2, B))
+    CMBLensing.EquiRectQUAzFourier(B == 1 ? dropdims(out, dims=3) : out, f.metadata)
+end
+function CMBLensing.QUMap(f::BaseField{CMBLensing.QUAzFourier,<:CMBLensing.ProjEquiRect,<:Any,<:ROCArray})      # :170-178
+    a = f.arr; B = eq_nbatch(a, 2); out = similar(a, real(eltype(a)), (f.Ny, f.Nx, 2, B))
+    GC.@preserve a out chk(ccall((:cmbl_equirect_convert, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint),
+                                 hip_ctx(f.metadata).h, AZFOURIER, devptr(a), MAP, devptr(out), 2, B))
+    CMBLensing.EquiRectQUMap(B == 1 ? dropdims(out, dims=4) : out, f.metadata)
+end
+
+const ROCBlockDiag{B,T,P,A<:ROCArray} = CMBLensing.BlockDiagEquiRect{B,T,P,A}
+function equirect_apply(M::ROCBlockDiag, f::BaseField, adjoint::Bool)
+    blocks, a = M.blocks, f.arr
+    n = size(blocks, 1); B = eq_nbatch(a, 2)
+    out = similar(a)
+    GC.@preserve blocks a out chk(ccall((:cmbl_equirect_block_apply, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Cint),
+                                        hip_ctx(M.proj).h, devptr(blocks), eltype(blocks) <: Complex, n, adjoint, devptr(a), devptr(out), B))
+    typeof(f)(out, f.metadata)
+end
+(*)(M::ROCBlockDiag{B}, f::BaseField{B,<:CMBLensing.ProjEquiRect,<:Any,<:ROCArray}) where {B<:CMBLensing.AzBasis} = equirect_apply(M, f, false)                 # :230-233
+(*)(M::Adjoint{<:Any,<:ROCBlockDiag{B}}, f::BaseField{B,<:CMBLensing.ProjEquiRect,<:Any,<:ROCArray}) where {B<:CMBLensing.AzBasis} = equirect_apply(M.parent, f, true)   # :237-240
+function equirect_matmul(M₁::ROCBlockDiag{B}, adj₁::Bool, M₂::ROCBlockDiag{B}, adj₂::Bool) where {B}
+    E = promote_type(eltype(M₁.blocks), eltype(M₂.blocks))
+    a, b = E.(M₁.blocks), E.(M₂.blocks)
+    out = similar(a)
+    GC.@preserve a b out chk(ccall((:cmbl_equirect_block_matmul, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cvoid}),
+                                   hip_ctx(M₁.proj).h, devptr(a), adj₁, devptr(b), adj₂, E <: Complex, size(a, 1), devptr(out)))
+    CMBLensing.BlockDiagEquiRect{B}(out, M₁.proj)
+end
+(*)(M₁::ROCBlockDiag{B}, M₂::ROCBlockDiag{B}) where {B<:CMBLensing.AzBasis} = equirect_matmul(M₁, false, M₂, false)                                             # :254-257
+(*)(M₁::Adjoint{<:Any,<:ROCBlockDiag{B}}, M₂::ROCBlockDiag{B}) where {B<:CMBLensing.AzBasis} = equirect_matmul(M₁.parent, true, M₂, false)                      # :260-263
+(*)(M₁::ROCBlockDiag{B}, M₂::Adjoint{<:Any,<:ROCBlockDiag{B}}) where {B<:CMBLensing.AzBasis} = equirect_matmul(M₁, false, M₂.parent, true)                      # :266-269
+function LinearAlgebra.dot(M₁::Adjoint{<:Any,<:ROCBlockDiag{B}}, M₂::ROCBlockDiag{B}) where {B<:CMBLensing.AzBasis}                                             # :358-360
+    E = promote_type(eltype(M₁.parent.blocks), eltype(M₂.blocks))
+    a, b = E.(M₁.parent.blocks), E.(M₂.blocks)
+    out = zeros(Cdouble, 2)
+    GC.@preserve a b out chk(ccall((:cmbl_equirect_block_dot, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}),
+                                   hip_ctx(M₂.proj).h, devptr(a), devptr(b), E <: Complex, size(a, 1), out))
+    E <: Complex ? E(complex(out[1], out[2])) : E(out[1])
+end
+# the Ω steps of Cℓ_to_Beam (:512, 524-530) on device-backed :I covariance blocks
+function equirect_beam(pol::Symbol, Cov::ROCBlockDiag{CMBLensing.AzFourier})
+    proj = Cov.proj
+    Ω = Cdouble.(Array(proj.Ω))
+    if pol == :I
+        blocks = copy(Cov.blocks)
+        GC.@preserve blocks Ω chk(ccall((:cmbl_equirect_block_scale_columns, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cint),
+                                        hip_ctx(proj).h, devptr(blocks), eltype(blocks) <: Complex, size(blocks, 1), Ω, length(Ω)))
+        return CMBLensing.BlockDiagEquiRect{CMBLensing.AzFourier}(blocks, proj)
+    end
+    blocks = Cov.blocks
+    out = similar(blocks, complex(eltype(blocks)), (2proj.Ny, 2proj.Ny, size(blocks, 3)))
+    GC.@preserve blocks Ω out chk(ccall((:cmbl_equirect_beam_pol, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cvoid}),
+                                        hip_ctx(proj).h, devptr(blocks), Ω, devptr(out)))
+    CMBLensing.BlockDiagEquiRect{CMBLensing.QUAzFourier}(out, proj)
+end
 
 # device RNG for `simulate` / `randn!` (src/specialops.jl:6, src/base_fields.jl:169-170): counter-based Philox4x32-10
 mutable struct HIPPhilox <: Random.AbstractRNG
