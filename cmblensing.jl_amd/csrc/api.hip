@@ -593,6 +593,46 @@ int cmbl_equirect_beam_pol(cmbl_ctx* ctx, const void* blocksI_real, const double
   });
 }
 
+// ---- HEALPix <-> Cartesian projection (src/proj_healpix.jl) ------------------------------------------------------------------
+int cmbl_healpix_pix2ang_host(int nside, long first, long n, double* theta, double* phi) {
+  return guard([&] {
+    NOTNULL(theta); NOTNULL(phi);
+    CMBL_REQUIRE(hpx_nside_ok(nside), ERR_SHAPE, "Nside must be a power of two in 1 ... 8192");
+    CMBL_REQUIRE(first >= 0 && n >= 0 && first + n <= 12L * nside * nside, ERR_ARG, "pix2ang: pixel range outside [0, 12 Nside^2)");
+    for (long k = 0; k < n; ++k) hpx_pix2ang(nside, first + k, theta + k, phi + k);
+  });
+}
+int cmbl_projector_create(cmbl_ctx* ctx, int nside, int cart_kind, const double* params, cmbl_projector** out) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(params); NOTNULL(out);
+    CMBL_REQUIRE(hpx_nside_ok(nside), ERR_SHAPE, "Nside must be a power of two in 1 ... 8192");
+    CMBL_REQUIRE(cart_kind == CMBL_PROJ_LAMBERT || cart_kind == CMBL_PROJ_EQUIRECT, ERR_ARG, "cart_kind must be CMBL_PROJ_LAMBERT or CMBL_PROJ_EQUIRECT");
+    for (int k = 0; k < (cart_kind == CMBL_PROJ_LAMBERT ? 3 : 4); ++k) CMBL_REQUIRE(std::isfinite(params[k]), ERR_ARG, "projector: params must be finite");
+    auto h = std::make_unique<cmbl_projector>();
+    h->ctx = ctx;
+    BY_DTYPE(ctx, do_projector_create, h.get(), nside, cart_kind, params);
+    *out = h.release();
+  });
+}
+int cmbl_projector_destroy(cmbl_projector* P) { return guard([&] { delete P; }); }
+int cmbl_projector_info_host(cmbl_projector* P, int which, double* out_host, size_t n) {
+  return guard([&] { NOTNULL(P); NOTNULL(out_host); P->p->info(which, out_host, n); });
+}
+int cmbl_project_to_cart(cmbl_projector* P, const void* hpx, void* map_out, int npol, int nbatch) {
+  return guard([&] {
+    NOTNULL(P); NOTNULL(hpx); NOTNULL(map_out); POLB_OK(npol, nbatch);
+    CMBL_REQUIRE(hpx != map_out, ERR_ARG, "project_to_cart: out must not alias the input");
+    P->p->to_cart(hpx, map_out, npol, nbatch);
+  });
+}
+int cmbl_project_to_healpix(cmbl_projector* P, int basis_in, const void* in, void* hpx_out, int npol, int nbatch) {
+  return guard([&] {
+    NOTNULL(P); NOTNULL(in); NOTNULL(hpx_out); BASIS_OK(basis_in); POLB_OK(npol, nbatch);
+    CMBL_REQUIRE(in != hpx_out, ERR_ARG, "project_to_healpix: out must not alias the input");
+    P->p->to_healpix(basis_in, in, hpx_out, npol, nbatch);
+  });
+}
+
 #ifdef CMBL_STAMPS
 // phase timestamps of the last stamped launch (tools/gpu_stamps*.py) of the translation unit CMBL_STAMPS_TU (kernels_fft.hpp CMBL_STAMPS_READER)
 int cmbl_debug_stamps(unsigned long long* out_host, int n) {

@@ -1,7 +1,7 @@
 // What api.hip (the entry points) and the per-precision translation units share: the handle structs, the list of the typed bodies behind the
 // entry points and the dispatch on a context's precision.  The build is split by explicit instantiation (lib.py builds the objects in parallel):
 //   api.hip                 extern "C" entry points, argument checks, error plumbing -- instantiates NO kernel and nothing of Flow<T>, Bilinear<T>,
-//                           PowerLens<T>, Dataset<T> or Drivers<T> (tests/test_boundary.py reads the object's symbols)
+//                           PowerLens<T>, Projector<T>, Dataset<T> or Drivers<T> (tests/test_boundary.py reads the object's symbols)
 //   tu_main_{f32,f64}.hip   every body of CMBL_API_BODIES (api_body.hpp) and with them Ctx<T>, Flow<T>, Bilinear<T>, PowerLens<T>, Dataset<T>, Drivers<T>, their
 //                           vtables and their kernels
 //   tu_gen_{f32,f64}.hip    the host side of the any-size transform launches (engine_gen.hpp) and the run-time-plan kernels k_gen_dft*
@@ -11,7 +11,7 @@
 //   tu_small_{f32,f64}.hip  the one-launch flows of small maps (engine_small.hpp: k_small_flow, k_small_adj)
 // An entry point reaches typed code in two ways only, and neither makes api.hip instantiate a member of a typed class (members defined in class
 // are inline, and an explicit instantiation DECLARATION does not stop inline functions from being instantiated -- [temp.explicit]/10):
-//   * a virtual member of the precision-free base its handle owns (CtxBase, FlowApi, DatasetApi, BilinearApi, PowerLensApi): set_phi, apply, grad, ... and the
+//   * a virtual member of the precision-free base its handle owns (CtxBase, FlowApi, DatasetApi, BilinearApi, PowerLensApi, ProjectorApi): set_phi, apply, grad, ... and the
 //     destructors.  The typed objects are made by the creators below, so their vtables are emitted in tu_main_* alone.
 //   * BY_DTYPE(ctx, do_x, args...): a body of the list below, for what takes typed pointers or needs the typed object (which it gets back from
 //     the handle with typed<Flow<T>>(L) etc., a static_cast).
@@ -24,6 +24,7 @@
 #include "engine_powerlens.hpp"
 #include "engine_mask.hpp"
 #include "engine_equirect.hpp"
+#include "engine_healpix.hpp"
 #include "../../include/cmblens.h"
 
 struct cmbl_ctx { std::unique_ptr<cmbl::CtxBase> p; };
@@ -31,6 +32,7 @@ struct cmbl_clbins { std::unique_ptr<cmbl::ClBins> p; };
 struct cmbl_flow { cmbl_ctx* ctx; std::unique_ptr<cmbl::FlowApi> p; };
 struct cmbl_bilinear { cmbl_ctx* ctx; std::unique_ptr<cmbl::BilinearApi> p; };
 struct cmbl_powerlens { cmbl_ctx* ctx; std::unique_ptr<cmbl::PowerLensApi> p; };
+struct cmbl_projector { cmbl_ctx* ctx; std::unique_ptr<cmbl::ProjectorApi> p; };
 struct cmbl_dataset {
   cmbl_ctx* ctx; std::unique_ptr<cmbl::DatasetApi> p;
   std::map<const cmbl::FlowApi*, std::shared_ptr<void>> drv;                 // driver scratch (a Drivers<T>, deleter and all) per (dataset, flow) pair
@@ -70,7 +72,8 @@ namespace cmbl {
   X(T, do_eq_matmul, (cmbl_ctx* ctx, const void* A, bool adjA, const void* Bm, bool adjB, bool cplx, int n, void* out)) \
   X(T, do_eq_dot, (cmbl_ctx* ctx, const void* A, const void* Bm, bool cplx, int n, double* out)) \
   X(T, do_eq_scale_columns, (cmbl_ctx* ctx, void* blocks, bool cplx, int n, const double* w)) \
-  X(T, do_eq_beam_pol, (cmbl_ctx* ctx, const void* blocksI, const double* omega, void* out))
+  X(T, do_eq_beam_pol, (cmbl_ctx* ctx, const void* blocksI, const double* omega, void* out)) \
+  X(T, do_projector_create, (cmbl_projector* h, int nside, int kind, const double* params))
 
 #define CMBL_API_DECLARE(T, name, params) template <typename T> void name params;
 #define CMBL_API_INSTANTIATE(T, name, params) template void name<T> params;

@@ -35,9 +35,13 @@ def reference_exact():
 
 
 class ProjLambert:
-    """Context: geometry + FFT tables + stream.  `T` is torch.float32 or torch.float64."""
+    """Context: geometry + FFT tables + stream.  `T` is torch.float32 or torch.float64.  `rotator`: the (z, y, x) Euler angles in degrees
+    that place the patch on the sphere (src/proj_lambert.jl:29, 45); only the HEALPix projection (healpix.py) reads it."""
 
-    def __init__(self, Ny, Nx, theta_pix=1.0, T=torch.float32, device=0):
+    def __init__(self, Ny, Nx, theta_pix=1.0, T=torch.float32, device=0, rotator=(0, 90, 0)):
+        self.rotator = tuple(float(v) for v in rotator)
+        if len(self.rotator) != 3:
+            raise ValueError("rotator: three angles in degrees (z, y, x)")
         if not torch.cuda.is_available():
             raise RuntimeError("cmblensing_jl_amd needs a HIP device (no CPU fallback)")
         self.lib = load_library()

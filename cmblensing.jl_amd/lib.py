@@ -94,6 +94,12 @@ SIGNATURES = {
     "cmbl_equirect_block_dot": [_vp, _vp, _vp, _ci, _ci, _pd],
     "cmbl_equirect_block_scale_columns": [_vp, _vp, _ci, _ci, _pd, _ci],
     "cmbl_equirect_beam_pol": [_vp, _vp, _pd, _vp],
+    "cmbl_healpix_pix2ang_host": [_ci, _l, _l, _pd, _pd],
+    "cmbl_projector_create": [_vp, _ci, _ci, _pd, _pvp],
+    "cmbl_projector_destroy": [_vp],
+    "cmbl_projector_info_host": [_vp, _ci, _pd, _sz],
+    "cmbl_project_to_cart": [_vp, _vp, _vp, _ci, _ci],
+    "cmbl_project_to_healpix": [_vp, _ci, _vp, _vp, _ci, _ci],
 }
 SYMBOLS = list(OTHER_RETURNS) + list(SIGNATURES)
 

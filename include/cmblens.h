@@ -465,6 +465,36 @@ int cmbl_quadratic_estimate(cmbl_dataset* ds, int which, const double* Cf_host, 
                             const double* TF_host, const double* Cphi_host, int wiener_filtered, const double* AL_in_host,
                             void* phiqe_out, double* AL_out_host, int nbatch);
 
+/* ---- HEALPix <-> Cartesian projection (src/proj_healpix.jl): project(healpix_field => cart_proj) and project(cart_field => ProjHealpix(Nside)),
+ *      method = :bilinear.  RING ordering; pixel indices are 0-based here (the reference's k - 1).  HEALPix fields are (npix, npol, nbatch)
+ *      arrays of the context's dtype, npix = 12 Nside^2 fastest: the reference's (npix, npol) plus the batch axis.  npol = 1 (I), 2 (QU),
+ *      3 (IQU); QU are rotated by the angle psi between the two coordinate bases ("polarization flattening", :238-252, 327-341).
+ *      ALL geometry is double on the device whatever the context's dtype (the reference computes it in T); values, weights and
+ *      cos 2 psi / sin 2 psi are of the context's dtype.  NOT here: method = :fft (a non-uniform FFT), NEST ordering, the AD rules.
+ *
+ * healpix_pix2ang_host: pix2angRing of the pixels first ... first + n - 1 (host, double, no device).
+ * projector_create: Projector(ProjHealpix(nside) => cart_proj) (:254-294) for the Cartesian projection of `ctx` (its Ny, Nx).  cart_kind
+ *   CMBL_PROJ_LAMBERT: params = rotator[3] in degrees (RotZYX, the reference's default is (0, 90, 0)), pixel size the context's;
+ *   CMBL_PROJ_EQUIRECT: params = theta_span[2], phi_span[2] in radians.  Nside: a power of two in 1 ... 8192, else CMBL_ERR_SHAPE.  A
+ *   Cartesian pixel whose colatitude is outside [0, pi] is CMBL_ERR_ARG (healpy.get_interp_val refuses it).  Synchronises.
+ * projector_info_host: doubles.  CMBL_PROJ_COUNTS: n = 2, {pixels in the patch, touched pixels}.  _THETA, _PHI, _PSI_CART: n = Ny Nx, at
+ *   the Cartesian pixel centres, Ny fastest.  _IDX_IN_PATCH: hpx_idxs_in_patch (1 <= i <= Ny, 1 <= j <= Nx, :270), ascending.  _IDX_TOUCHED,
+ *   _I, _J, _PSI_HPX: the pixels with 0 < i < Ny+1, 0 < j < Nx+1 (every other pixel of a projection to the sphere is exactly 0), ascending,
+ *   their fractional (i, j) (1-based like the reference's) and psi.
+ * project_to_cart: hpx (npix, npol, nbatch) -> map_out MAP (Ny, Nx, npol, nbatch): healpy.get_interp_val at the pixel centres.
+ * project_to_healpix: `in` in basis_in (converted to MAP first; a ProjEquiRect context takes MAP only) -> hpx_out (npix, npol, nbatch):
+ *   Images.bilinear_interpolation, a corner outside the map counts as zero.  Neither call synchronises. */
+typedef struct cmbl_projector cmbl_projector;
+enum { CMBL_PROJ_LAMBERT = 0, CMBL_PROJ_EQUIRECT = 1 };
+enum { CMBL_PROJ_COUNTS = 0, CMBL_PROJ_THETA = 1, CMBL_PROJ_PHI = 2, CMBL_PROJ_PSI_CART = 3, CMBL_PROJ_IDX_IN_PATCH = 4, CMBL_PROJ_IDX_TOUCHED = 5,
+       CMBL_PROJ_I = 6, CMBL_PROJ_J = 7, CMBL_PROJ_PSI_HPX = 8 };
+int cmbl_healpix_pix2ang_host(int nside, long first, long n, double* theta, double* phi);
+int cmbl_projector_create(cmbl_ctx* ctx, int nside, int cart_kind, const double* params, cmbl_projector** out);
+int cmbl_projector_destroy(cmbl_projector* P);
+int cmbl_projector_info_host(cmbl_projector* P, int which, double* out_host, size_t n);
+int cmbl_project_to_cart(cmbl_projector* P, const void* hpx, void* map_out, int npol, int nbatch);
+int cmbl_project_to_healpix(cmbl_projector* P, int basis_in, const void* in, void* hpx_out, int npol, int nbatch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -710,6 +710,67 @@ function equirect_beam(pol::Symbol, Cov::ROCBlockDiag{CMBLensing.AzFourier})
     CMBLensing.BlockDiagEquiRect{CMBLensing.QUAzFourier}(out, proj)
 end
 
+# ---- HEALPix <-> Cartesian projection (src/proj_healpix.jl), method = :bilinear, for a device-backed Cartesian side: the Projector (:254-294) is
+# `cmbl_projector_create` -- pix2angRing, θϕ_to_ij / ij_to_θϕ, get_ψpol and the ring lookup of healpy.get_interp_val on the device, in double whatever
+# T -- and each direction of `project` one gather kernel with the QU rotation fused in (`cmbl_project_to_cart`, `cmbl_project_to_healpix`): no
+# healpy, no Images.jl, nothing through the host.  The library counts pixels from 0 and stores a HEALPix field as (npix, npol, nbatch).
+# `method = :fft` keeps the reference's NFFT methods.  (Unexecuted, like the rest of this file: there is no Julia on the build machines.)
+mutable struct HIPProjector
+    h         :: Ptr{Cvoid}
+    cart_proj
+    hpx_proj  :: CMBLensing.ProjHealpix
+    function HIPProjector(h, cart_proj, hpx_proj)
+        P = new(h, cart_proj, hpx_proj)
+        finalizer(P -> ccall((:cmbl_projector_destroy, lib), Cint, (Ptr{Cvoid},), P.h), P)
+    end
+end
+projector_params(proj::ProjLambert) = (Cint(0), Cdouble[proj.rotator...])                                       # CMBL_PROJ_LAMBERT
+projector_params(proj::CMBLensing.ProjEquiRect) = (Cint(1), Cdouble[proj.θspan..., proj.φspan...])              # CMBL_PROJ_EQUIRECT
+function HIPProjector((hpx_proj, cart_proj)::Pair{<:CMBLensing.ProjHealpix,<:CMBLensing.CartesianProj})         # :254-294
+    kind, params = projector_params(cart_proj)
+    h = Ref{Ptr{Cvoid}}()
+    GC.@preserve params chk(ccall((:cmbl_projector_create, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Ptr{Cvoid}}),
+                                  hip_ctx(cart_proj).h, hpx_proj.Nside, kind, params, h))
+    HIPProjector(h[], cart_proj, hpx_proj)
+end
+HIPProjector((cart_proj, hpx_proj)::Pair{<:CMBLensing.CartesianProj,<:CMBLensing.ProjHealpix}) = HIPProjector(hpx_proj => cart_proj)   # :304-306
+function projector_info(P::HIPProjector, which::Integer, n::Integer)
+    out = Vector{Cdouble}(undef, n)
+    chk(ccall((:cmbl_projector_info_host, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Csize_t), P.h, which, out, n))
+    out
+end
+hpx_idxs_in_patch(P::HIPProjector) = Int.(projector_info(P, 4, Int(projector_info(P, 0, 2)[1]))) .+ 1           # the reference's 1-based k (:270)
+hpx_npol(::CMBLensing.HealpixField{B}) where {B} = B <: CMBLensing.Basis3Prod ? 3 : B <: CMBLensing.Basis2Prod ? 2 : 1
+# project(projector, hpx_map => cart_proj) (:221-252): `hpx_map.arr` (npix, npol) is moved to the device of the projection
+function CMBLensing.project(P::HIPProjector, (hpx_map, cart_proj)::Pair{<:CMBLensing.HealpixField,<:CMBLensing.CartesianProj})
+    @assert P.hpx_proj == hpx_map.proj && P.cart_proj == cart_proj
+    npol = hpx_npol(hpx_map)
+    a = ROCArray(cart_proj.T.(hpx_map.arr))
+    out = similar(a, (cart_proj.Ny, cart_proj.Nx, npol))
+    GC.@preserve a out chk(ccall((:cmbl_project_to_cart, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint), P.h, devptr(a), devptr(out), npol, 1))
+    npol == 1 ? BaseMap(dropdims(out, dims=3), cart_proj) : npol == 2 ? BaseField{QUMap}(out, cart_proj) : BaseField{IQUMap}(out, cart_proj)
+end
+# project(projector, cart_field => hpx_proj) (:308-341): Map(cart_field) is taken by the library (any basis of a ProjLambert field)
+function CMBLensing.project(P::HIPProjector, (cart_field, hpx_proj)::Pair{<:BaseField{B,<:CMBLensing.CartesianProj,<:Any,<:ROCArray},<:CMBLensing.ProjHealpix}) where {B}
+    @assert P.cart_proj == cart_field.proj && P.hpx_proj == hpx_proj
+    f = cart_field.proj isa ProjLambert ? cart_field : Ł(cart_field)
+    a = f.arr
+    npol = size(a, 3)
+    out = similar(a, real(eltype(a)), (12 * hpx_proj.Nside^2, npol))
+    GC.@preserve a out chk(ccall((:cmbl_project_to_healpix, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint),
+                                 P.h, f.proj isa ProjLambert ? basis_tag(f) : MAP, devptr(a), devptr(out), npol, 1))
+    npol == 1 ? CMBLensing.HealpixMap(vec(out), hpx_proj) : npol == 2 ? CMBLensing.HealpixQUMap(out, hpx_proj) : CMBLensing.HealpixIQUMap(out, hpx_proj)
+end
+function CMBLensing.project((cart_field, hpx_proj)::Pair{<:BaseField{B,<:CMBLensing.CartesianProj,<:Any,<:ROCArray},<:CMBLensing.ProjHealpix}; method::Symbol=:bilinear) where {B}
+    method == :bilinear || return CMBLensing.project(CMBLensing.Projector(cart_field.proj => hpx_proj; method), cart_field => hpx_proj)
+    CMBLensing.project(HIPProjector(hpx_proj => cart_field.proj), cart_field => hpx_proj)
+end
+# sphere -> patch: the target decides; a projection whose `storage` is a ROCArray gets the device path
+function CMBLensing.project((hpx_map, cart_proj)::Pair{<:CMBLensing.HealpixField,<:CMBLensing.CartesianProj}, ::Type{<:ROCArray}; method::Symbol=:bilinear)
+    method == :bilinear || error("method = :$method is not implemented on the device; use the reference's project")
+    CMBLensing.project(HIPProjector(hpx_map.proj => cart_proj), hpx_map => cart_proj)
+end
+
 # device RNG for `simulate` / `randn!` (src/specialops.jl:6, src/base_fields.jl:169-170): counter-based Philox4x32-10
 mutable struct HIPPhilox <: Random.AbstractRNG
     seed   :: UInt64
