@@ -10,14 +10,8 @@ template <typename T> Ctx<T>* C(cmbl_ctx* c) { return &typed<Ctx<T>>(c); }
 
 template <typename T> void do_convert(cmbl_ctx* ctx, int bi, const void* in, int bo, void* out, int P, int B) {
   Ctx<T>* c = C<T>(ctx);
-  const long sl = (long)P * B;
-  c->tmpA.ensure(sizeof(cx<T>) * sl * c->plane());
-  cx<T>* F = c->tmpA.template as<cx<T>>();
-  // carry the data in the basis of whichever side is a Fourier basis; map<->map is a copy
-  if (bi == B_MAP && bo == B_MAP) { CMBL_HIP(hipMemcpyAsync(out, in, sizeof(T) * sl * c->npix(), hipMemcpyDeviceToDevice, c->stream)); return; }
-  const int carry = (bi == B_MAP) ? (bo == B_HARMONIC ? B_HARMONIC : B_FOURIER) : bi;
-  c->to_F(bi, in, F, carry, P, B);
-  c->from_F(F, carry, bo, out, P, B);
+  c->tmpA.ensure(sizeof(cx<T>) * (long)P * B * c->plane());              // (whatever the bases: the context's scratch exists after its first conversion)
+  c->convert(bi, in, bo, out, P, B, c->tmpA);
 }
 template <typename T>
 void do_diag(cmbl_ctx* ctx, int kind, int bd, const void* diag, int nplanes, bool transpose, int bi, const void* in, int bo, void* out, int P, int B) {

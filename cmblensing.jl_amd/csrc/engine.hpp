@@ -55,6 +55,9 @@ static const char* const kKernelNames[K_COUNT] = {"layout", "y_r2c", "y_c2r", "x
     } else { hipLaunchKernelGGL(kernel, grid, dim3(nthreads), (lds), (stream), __VA_ARGS__); CMBL_HIP(hipGetLastError()); }   \
   } while (0)
 #define CMBL_LAUNCH(ctxp, kid, kernel, grid, lds, stream, ...) CMBL_LAUNCH_NT(ctxp, kid, NTP, kernel, grid, lds, stream, __VA_ARGS__)
+inline unsigned nblocks(long n) { return (unsigned)((n + NTP - 1) / NTP); }         // workgroups of NTP threads, one thread per element
+// (∂xϕ, ∂yϕ) planes of Fourier planes (kernels_bilinear.hpp): launched by Ctx::deflection_maps for every operator that lenses by ∇ϕ
+template <typename T> __global__ void k_bl_gradmult(const cx<T>* F, cx<T>* out, const T* lx_r, const T* ly, int Nx, long plane, int S);
 
 // compiled column-tile shapes (lgM, R, NT):  C = R*NT >> lgM columns per workgroup.  Per lgM the list holds what tileY() can select in
 // either precision (narrowest C >= 4 that fits LDS, 512 threads preferred; C = 2 or 1 where four double-precision columns do not fit)
@@ -233,9 +236,10 @@ struct Ctx : CtxBase {
     build_geometry();
   }
 
+  T dx() const { return (T)(theta / 60.0 * M_PI / 180.0); }                   // Δx in T (src/proj_lambert.jl:58)
   // src/proj_lambert.jl:58-71 (computed in T like the reference, tables uploaded in the internal layouts)
   void build_geometry() {
-    const T dx = (T)(theta / 60.0 * M_PI / 180.0);
+    const T dx = this->dx();
     const T dlx = (T)(2.0 * M_PI / (double)((T)Nx * dx));
     const T dly = (T)(2.0 * M_PI / (double)((T)Ny * dx));
     dlx_over_Nx = dlx / (T)Nx;
@@ -861,6 +865,63 @@ struct Ctx : CtxBase {
     if (P >= 2 && have_h != want_h) harm(in_F, in_F, P, B, 0, nullptr, false, !have_h, !want_h);
     if (basis_out == B_MAP) F_to_map(in_F, (T*)out, slices);
     else F2ref(in_F, (cx<T>*)out, slices);
+  }
+
+  // ---- the boundary shell of an operator: what lies between an ABI call in any basis and kernels that want maps ------------------
+  // Scratch is the caller's (an operator's own DevBuf: handles share none); each helper ensures what it is handed before its first launch,
+  // so a caller that must have every buffer before ITS first launch ensures them itself and these become no-ops.
+  void copy_maps(const T* in, T* out, long slices) { CMBL_HIP(hipMemcpyAsync(out, in, sizeof(T) * slices * npix(), hipMemcpyDeviceToDevice, stream)); }
+  // B(f): the data is carried in the basis of whichever side is a Fourier basis (MAP -> HARMONIC: HARMONIC); MAP -> MAP is a copy, of nothing in place
+  void convert(int bi, const void* in, int bo, void* out, int P, int B, DevBuf& scratch) {
+    const long sl = (long)P * B;
+    if (bi == B_MAP && bo == B_MAP) { if (in != out) copy_maps((const T*)in, (T*)out, sl); return; }
+    scratch.ensure(sizeof(cx<T>) * sl * plane());
+    const int carry = bi == B_MAP ? (bo == B_HARMONIC ? B_HARMONIC : B_FOURIER) : bi;
+    to_F(bi, in, scratch.as<cx<T>>(), carry, P, B);
+    from_F(scratch.as<cx<T>>(), carry, bo, out, P, B);
+  }
+  // Ł(f): `in` itself for a MAP argument, else ref2F, harm if needed, F_to_map into `maps`; `F` is left holding the QU Fourier planes
+  const T* as_maps(int basis, const void* in, DevBuf& F, T* maps, int P, int B) {
+    if (basis == B_MAP) return (const T*)in;
+    F.ensure(sizeof(cx<T>) * (long)P * B * plane());
+    to_F(basis, in, F.as<cx<T>>(), B_FOURIER, P, B);
+    F_to_map(F.as<cx<T>>(), maps, (long)P * B);
+    return maps;
+  }
+  const T* as_maps(int basis, const void* in, DevBuf& F, DevBuf& maps, int P, int B) {
+    if (basis != B_MAP) maps.ensure(sizeof(T) * (long)P * B * npix());
+    return as_maps(basis, in, F, maps.as<T>(), P, B);
+  }
+  // the inverse: rfft2_F, harm if needed, F2ref into `out` (bo a Fourier basis)
+  void from_maps(const T* maps, int bo, void* out, DevBuf& F, int P, int B) {
+    F.ensure(sizeof(cx<T>) * (long)P * B * plane());
+    rfft2_F(maps, F.as<cx<T>>(), (long)P * B);
+    from_F(F.as<cx<T>>(), B_FOURIER, bo, out, P, B);
+  }
+  // Where an operator that cannot run in place writes its maps, and what is left to do then: a MAP result goes straight to `out` unless
+  // that is the argument itself, else to `scratch`, from where map_finish converts or copies it
+  T* map_dst(int bo, void* out, const void* arg, DevBuf& scratch, long slices) {
+    if (bo == B_MAP && arg != out) return (T*)out;
+    scratch.ensure(sizeof(T) * slices * npix());
+    return scratch.as<T>();
+  }
+  void map_finish(const T* dst, int bo, void* out, DevBuf& F, int P, int B) {
+    if (bo != B_MAP) from_maps(dst, bo, out, F, P, B);
+    else if (dst != (const T*)out) copy_maps(dst, (T*)out, (long)P * B);
+  }
+  // d = ∇ϕ: ϕ in any basis -> defl [2][npix], x then y, by one transform pair; `kid`: the profiling class of the operator that asks
+  void deflection_maps(int basis, const void* phi, DevBuf& phiF, DevBuf& gF, DevBuf& defl, int kid) {
+    const long pl = plane();
+    phiF.ensure(sizeof(cx<T>) * pl); gF.ensure(sizeof(cx<T>) * 2 * pl); defl.ensure(sizeof(T) * 2 * npix());
+    to_F(basis, phi, phiF.as<cx<T>>(), B_FOURIER, 1, 1);
+    CMBL_LAUNCH(this, kid, (k_bl_gradmult<T>), dim3(nblocks(pl)), 0, stream, (const cx<T>*)phiF.as<cx<T>>(), gF.as<cx<T>>(), lx_r.as<T>(), ly.as<T>(), Nx, pl, 1);
+    F_to_map(gF.as<cx<T>>(), defl.as<T>(), 2);
+  }
+  // ... or the two given maps
+  void deflection_maps(const void* dy, const void* dx, DevBuf& defl) {
+    defl.ensure(sizeof(T) * 2 * npix());
+    copy_maps((const T*)dx, defl.as<T>(), 1);
+    copy_maps((const T*)dy, defl.as<T>() + npix(), 1);
   }
 };
 
@@ -1491,18 +1552,8 @@ struct Flow : FlowApi {
     if (mode == F_FWD || mode == F_INV) {
       y0.ensure(sizeof(T) * slices * np);
       T* y = (basis_out == B_MAP) ? (T*)out : y0.as<T>();
-      if (basis_in == B_MAP) flow_map((const T*)in, y, P, B, mode == F_INV);
-      else {
-        cvt.ensure(sizeof(cx<T>) * slices * pl);
-        c->ref2F((const cx<T>*)in, cvt.as<cx<T>>(), slices);
-        c->from_F(cvt.as<cx<T>>(), basis_in, B_MAP, y, P, B);
-        flow_map(y, y, P, B, mode == F_INV);
-      }
-      if (basis_out != B_MAP) {
-        cvt.ensure(sizeof(cx<T>) * slices * pl);
-        c->to_F(B_MAP, y, cvt.as<cx<T>>(), basis_out, P, B);
-        c->F2ref(cvt.as<cx<T>>(), (cx<T>*)out, slices);
-      }
+      flow_map(c->as_maps(basis_in, in, cvt, y, P, B), y, P, B, mode == F_INV);   // in place on the converted argument
+      if (basis_out != B_MAP) c->from_maps(y, basis_out, out, cvt, P, B);
     } else {
       Y0.ensure(sizeof(cx<T>) * slices * pl);
       c->to_F(basis_in, in, Y0.as<cx<T>>(), B_FOURIER, P, B);

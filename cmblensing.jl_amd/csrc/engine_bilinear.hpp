@@ -33,7 +33,7 @@ struct Bilinear : BilinearApi {
   DevBuf defl;                               // [2][npix]: x then y component
   BlTab fwd, anti;
   DevBuf cnt, blk, flag, phiF, gF;           // set-up scratch
-  DevBuf inm, outm, cvt;                     // boundary conversion scratch
+  DevBuf inm, outm, cvt;                     // boundary scratch (Ctx::as_maps / map_dst / map_finish): argument maps, result maps, F planes
   DevBuf Q, tmp, H, y, part;                 // GMRES: the orthonormal basis [m+1][S][npix], A q, Hessenberg entries, coefficients, partial sums
   DevBuf gmaps, vmaps, vF, dF;               // pullback scratch
   static constexpr int RED = 256;
@@ -42,7 +42,7 @@ struct Bilinear : BilinearApi {
   Bilinear(const Bilinear&) = delete;
   Bilinear& operator=(const Bilinear&) = delete;
 
-  unsigned pgrid() const { return (unsigned)((c->npix() + NTP - 1) / NTP); }
+  unsigned pgrid() const { return nblocks(c->npix()); }
   void reset() { fwd.rows = fwd.csr = anti.rows = anti.csr = false; }
 
   void rows(BlTab& t, T sign) {
@@ -84,10 +84,10 @@ struct Bilinear : BilinearApi {
 
   void set_phi(int basis, const void* phi, int nb) override {
     CMBL_REQUIRE(nb == 1, ERR_SHAPE, "BilinearLens with batched phi is not implemented (src/bilinearlens.jl:40)");
-    const long np = c->npix(), pl = c->plane(), n = basis == B_MAP ? np : 2 * pl;
+    const long n = basis == B_MAP ? c->npix() : 2 * c->plane();
     flag.ensure(sizeof(int));
     CMBL_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), c->stream));
-    CMBL_LAUNCH(c, K_BL, (k_bl_anynz<T>), dim3((unsigned)std::min<long>((n + NTP - 1) / NTP, 1024)), 0, c->stream, (const T*)phi, n, flag.as<int>());
+    CMBL_LAUNCH(c, K_BL, (k_bl_anynz<T>), dim3(std::min(nblocks(n), 1024u)), 0, c->stream, (const T*)phi, n, flag.as<int>());
     int nz = 0;
     CMBL_HIP(hipMemcpyAsync(&nz, flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     CMBL_HIP(hipStreamSynchronize(c->stream));
@@ -95,19 +95,12 @@ struct Bilinear : BilinearApi {
     identity = nz == 0;                                                     // norm(ϕ) == 0 (:34)
     ready = true;
     if (identity) return;
-    phiF.ensure(sizeof(cx<T>) * pl); gF.ensure(sizeof(cx<T>) * 2 * pl); defl.ensure(sizeof(T) * 2 * np);
-    c->to_F(basis, phi, phiF.as<cx<T>>(), B_FOURIER, 1, 1);
-    CMBL_LAUNCH(c, K_BL, (k_bl_gradmult<T>), dim3((unsigned)((pl + NTP - 1) / NTP)), 0, c->stream, phiF.as<cx<T>>(), gF.as<cx<T>>(), c->lx_r.template as<T>(),
-                c->ly.template as<T>(), c->Nx, pl, 1);
-    c->F_to_map(gF.as<cx<T>>(), defl.as<T>(), 2);                           // one transform pair: (∂xϕ, ∂yϕ)
-    div = (T)(c->theta / 60.0 * M_PI / 180.0);                              // Δx in T (src/proj_lambert.jl:58)
+    c->deflection_maps(basis, phi, phiF, gF, defl, K_BL);
+    div = c->dx();
     rows(fwd, (T)1);
   }
   void set_deflection(const void* dy_px, const void* dx_px) override {
-    const long np = c->npix();
-    defl.ensure(sizeof(T) * 2 * np);
-    CMBL_HIP(hipMemcpyAsync(defl.as<T>(), dx_px, sizeof(T) * np, hipMemcpyDeviceToDevice, c->stream));
-    CMBL_HIP(hipMemcpyAsync(defl.as<T>() + np, dy_px, sizeof(T) * np, hipMemcpyDeviceToDevice, c->stream));
+    c->deflection_maps(dy_px, dx_px, defl);
     div = 1;
     reset();
     identity = false; ready = true;
@@ -117,7 +110,7 @@ struct Bilinear : BilinearApi {
   // <w, qdot> (qdot null: <w, w>) of every slice -> out[S] (device doubles), after w -= hprev qprev when qprev is given
   void mgs(T* w, const T* qprev, const double* hprev, const T* qdot, double* out, int S) {
     const long np = c->npix();
-    const unsigned nblk = (unsigned)std::min<long>((np + NTP - 1) / NTP, RED);
+    const unsigned nblk = std::min(nblocks(np), (unsigned)RED);
     CMBL_LAUNCH(c, K_BL, (k_bl_mgs<T>), dim3(nblk, (unsigned)S), 0, c->stream, w, qprev, hprev, qdot, part.as<double>(), np);
     CMBL_LAUNCH(c, K_REDUCE, (k_reduce_final<T, SUM_FLOAT64>), dim3((unsigned)S), 0, c->stream, part.as<double>(), out, (int)nblk, 1.0);
   }
@@ -130,7 +123,7 @@ struct Bilinear : BilinearApi {
     auto slot = [&](int j, int k) { return h + ((long)j * m + k) * S; };
     // a direction whose norm is below 16 eps of its column's is rounding noise of the orthogonalisation
     const double thr = 16.0 * (double)std::numeric_limits<T>::epsilon(), thr2 = thr * thr;
-    const dim3 sg((unsigned)std::min<long>((np + NTP - 1) / NTP, 1024), (unsigned)S);
+    const dim3 sg(std::min(pgrid(), 1024u), (unsigned)S);
     mul(true, transposed, b, q, S);                                         // K1 = Pl b
     mgs(q, nullptr, nullptr, nullptr, slot(m + 1, 0), S);                   // beta^2
     CMBL_LAUNCH(c, K_BL, (k_bl_scale<T>), sg, 0, c->stream, q, (const double*)slot(m + 1, 0), (const double*)h, 0L, 0, thr2, np);
@@ -148,44 +141,17 @@ struct Bilinear : BilinearApi {
   }
 
   void check_ready() const { CMBL_REQUIRE(ready, ERR_STATE, "cmbl_bilinear_set_phi / cmbl_bilinear_set_deflection has not been called"); }
-  // Ł(field) -> maps; returns `in` itself for a MAP argument
-  const T* as_map(int basis, const void* in, DevBuf& buf, int P, int B) {
-    if (basis == B_MAP) return (const T*)in;
-    const long sl = (long)P * B;
-    cvt.ensure(sizeof(cx<T>) * sl * c->plane()); buf.ensure(sizeof(T) * sl * c->npix());
-    c->to_F(basis, in, cvt.as<cx<T>>(), B_FOURIER, P, B);
-    c->F_to_map(cvt.as<cx<T>>(), buf.as<T>(), sl);
-    return buf.as<T>();
-  }
-  void from_map(const T* m, int basis, void* out, int P, int B) {
-    const long sl = (long)P * B;
-    cvt.ensure(sizeof(cx<T>) * sl * c->plane());
-    c->rfft2_F(m, cvt.as<cx<T>>(), sl);
-    c->from_F(cvt.as<cx<T>>(), B_FOURIER, basis, out, P, B);
-  }
-  void convert(int bi, const void* in, int bo, void* out, int P, int B) {
-    const long sl = (long)P * B;
-    if (bi == B_MAP && bo == B_MAP) { if (in != out) CMBL_HIP(hipMemcpyAsync(out, in, sizeof(T) * sl * c->npix(), hipMemcpyDeviceToDevice, c->stream)); return; }
-    cvt.ensure(sizeof(cx<T>) * sl * c->plane());
-    const int carry = bi == B_MAP ? (bo == B_HARMONIC ? B_HARMONIC : B_FOURIER) : bi;
-    c->to_F(bi, in, cvt.as<cx<T>>(), carry, P, B);
-    c->from_F(cvt.as<cx<T>>(), carry, bo, out, P, B);
-  }
 
   void apply(int mode, int bi, const void* in, int bo, void* out, int P, int B, int maxiter) override {
     check_ready();
-    if (identity) return convert(bi, in, bo, out, P, B);                    // sparse_repr === I && return f (:108, 118, 128, 141)
+    if (identity) return c->convert(bi, in, bo, out, P, B, cvt);            // sparse_repr === I && return f (:108, 118, 128, 141)
     const int S = P * B;
-    const long sn = (long)S * c->npix();
-    const T* src = as_map(bi, in, inm, P, B);
-    // the gathers cannot run in place: a MAP result goes straight to `out` unless that is the input itself
-    T* dst = (T*)out;
-    if (bo != B_MAP || (const void*)src == out) { outm.ensure(sizeof(T) * sn); dst = outm.as<T>(); }
+    const T* src = c->as_maps(bi, in, cvt, inm, P, B);
+    T* dst = c->map_dst(bo, out, src, outm, S);                             // the gathers cannot run in place
     if (mode == F_FWD) mul(false, false, src, dst, S);
     else if (mode == F_ADJ) mul(false, true, src, dst, S);
     else solve(mode == F_INVADJ, src, dst, maxiter, S);
-    if (bo != B_MAP) from_map(dst, bo, out, P, B);
-    else if (dst != (T*)out) CMBL_HIP(hipMemcpyAsync(out, dst, sizeof(T) * sn, hipMemcpyDeviceToDevice, c->stream));
+    c->map_finish(dst, bo, out, cvt, P, B);
   }
 
   // pullback of L*f (:165-171): δf = L'Δ in `bdf`; δϕ = ∇'·(Σ_pol Ł(Δ) Ł(∇f̃)), a Fourier plane per batch slot (ABI layout)
@@ -193,26 +159,24 @@ struct Bilinear : BilinearApi {
     check_ready();
     const int S = P * B;
     const long np = c->npix(), pl = c->plane();
-    const T* dm = as_map(bdel, delta, inm, P, B);
+    const T* dm = c->as_maps(bdel, delta, cvt, inm, P, B);
     // ∇f̃ in Fourier space (the reference's choice), back to maps
     vF.ensure(sizeof(cx<T>) * 3 * S * pl); gmaps.ensure(sizeof(T) * 2 * S * np); vmaps.ensure(sizeof(T) * 2 * B * np); dF.ensure(sizeof(cx<T>) * B * pl);
     cx<T>* F = vF.as<cx<T>>(); cx<T>* G = F + (long)S * pl;
-    const dim3 fg((unsigned)((pl + NTP - 1) / NTP));
+    const dim3 fg(nblocks(pl));
     c->rfft2_F((const T*)f_lensed, F, S);
     CMBL_LAUNCH(c, K_BL, (k_bl_gradmult<T>), fg, 0, c->stream, (const cx<T>*)F, G, c->lx_r.template as<T>(), c->ly.template as<T>(), c->Nx, pl, S);
     c->F_to_map(G, gmaps.as<T>(), 2L * S);
-    CMBL_LAUNCH(c, K_BL, (k_bl_polsum<T>), dim3((unsigned)std::min<long>((np + NTP - 1) / NTP, 1024), (unsigned)B), 0, c->stream, dm, (const T*)gmaps.as<T>(),
+    CMBL_LAUNCH(c, K_BL, (k_bl_polsum<T>), dim3(std::min(pgrid(), 1024u), (unsigned)B), 0, c->stream, dm, (const T*)gmaps.as<T>(),
                 vmaps.as<T>(), np, P, B);
     c->rfft2_F(vmaps.as<T>(), F, 2L * B);
     CMBL_LAUNCH(c, K_BL, (k_bl_div<T>), fg, 0, c->stream, (const cx<T>*)F, dF.as<cx<T>>(), c->lx_r.template as<T>(), c->ly.template as<T>(), c->Nx, pl, B);
     c->F2ref(dF.as<cx<T>>(), (cx<T>*)dphi, B);
     // δf = B(Lϕ' * Δ)
-    if (identity) return convert(B_MAP, dm, bdf, df, P, B);
-    T* dst = (T*)df;
-    if (bdf != B_MAP || (const void*)dm == df) { outm.ensure(sizeof(T) * S * np); dst = outm.as<T>(); }
+    if (identity) return c->convert(B_MAP, dm, bdf, df, P, B, cvt);
+    T* dst = c->map_dst(bdf, df, dm, outm, S);
     mul(false, true, dm, dst, S);
-    if (bdf != B_MAP) from_map(dst, bdf, df, P, B);
-    else if (dst != (T*)df) CMBL_HIP(hipMemcpyAsync(df, dst, sizeof(T) * S * np, hipMemcpyDeviceToDevice, c->stream));
+    c->map_finish(dst, bdf, df, cvt, P, B);
   }
 };
 

@@ -55,7 +55,7 @@ struct Projector : ProjectorApi {
       g.ph0 = std::min(params[2], params[3]); g.dph = std::fabs(params[3] - params[2]);
       CMBL_REQUIRE(g.dth > 0 && g.dph > 0, ERR_ARG, "projector: an empty span");
     }
-    const unsigned gc = (unsigned)((ncart + NTP - 1) / NTP);
+    const unsigned gc = nblocks(ncart);
     const int nblk = (int)((npix + HPX_CHUNK - 1) / HPX_CHUNK);
     theta.ensure(sizeof(double) * ncart); phi.ensure(sizeof(double) * ncart); psi.ensure(sizeof(double) * ncart);
     c2.ensure(sizeof(T) * ncart); s2.ensure(sizeof(T) * ncart); pix.ensure(sizeof(int4) * ncart); w.ensure(sizeof(T) * 4 * ncart);
@@ -88,24 +88,15 @@ struct Projector : ProjectorApi {
   Projector& operator=(const Projector&) = delete;
 
   void to_cart(const void* hpx, void* map_out, int P, int B) override {
-    CMBL_LAUNCH(c, K_HPX_PROJECT, (k_hpx_to_cart<T>), dim3((unsigned)((ncart + NTP - 1) / NTP)), 0, c->stream, (const T*)hpx, (T*)map_out, pix.as<int4>(),
+    CMBL_LAUNCH(c, K_HPX_PROJECT, (k_hpx_to_cart<T>), dim3(nblocks(ncart)), 0, c->stream, (const T*)hpx, (T*)map_out, pix.as<int4>(),
                 w.as<T>(), c2.as<T>(), s2.as<T>(), ncart, npix, P, B);
   }
   void to_healpix(int bi, const void* in, void* hpx_out, int P, int B) override {
-    const T* m = (const T*)in;
-    if (bi != B_MAP) {
-      CMBL_REQUIRE(g.kind == HPX_LAMBERT, ERR_ARG, "project_to_healpix: a ProjEquiRect input must be in the MAP basis");
-      const long sl = (long)P * B;
-      inm.ensure(sizeof(T) * sl * ncart);
-      c->tmpA.ensure(sizeof(cx<T>) * sl * c->plane());
-      cx<T>* F = c->tmpA.template as<cx<T>>();
-      c->to_F(bi, in, F, bi, P, B);
-      c->from_F(F, bi, B_MAP, inm.p, P, B);
-      m = inm.as<T>();
-    }
+    CMBL_REQUIRE(bi == B_MAP || g.kind == HPX_LAMBERT, ERR_ARG, "project_to_healpix: a ProjEquiRect input must be in the MAP basis");
+    const T* m = c->as_maps(bi, in, c->tmpA, inm, P, B);                      // Map(cart_field) (:311)
     CMBL_HIP(hipMemsetAsync(hpx_out, 0, sizeof(T) * (size_t)npix * P * B, c->stream));
     if (L.n_touched > 0)
-      CMBL_LAUNCH(c, K_HPX_PROJECT, (k_hpx_to_healpix<T>), dim3((unsigned)((L.n_touched + NTP - 1) / NTP)), 0, c->stream, m, (T*)hpx_out, L, c->Ny, c->Nx, npix, P, B);
+      CMBL_LAUNCH(c, K_HPX_PROJECT, (k_hpx_to_healpix<T>), dim3(nblocks(L.n_touched)), 0, c->stream, m, (T*)hpx_out, L, c->Ny, c->Nx, npix, P, B);
   }
   void info(int which, double* out, size_t n) override {
     if (which == PROJ_INFO_COUNTS) {

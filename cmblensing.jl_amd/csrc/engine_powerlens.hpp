@@ -21,6 +21,16 @@ struct PowerLensApi {                        // what the C ABI (api.hip) holds o
 };
 
 #define CMBL_PL_ORDERS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12)
+// fn(integral_constant<int, n>) for a run-time order n in FIRST..12 (FIRST = 0: Taylens' bare permutation as well)
+template <int FIRST, typename Fn> void by_order(int n, const char* who, Fn&& fn) {
+  if constexpr (FIRST == 0) { if (n == 0) return fn(std::integral_constant<int, 0>{}); }
+  switch (n) {
+#define CMBL_X(N) case N: return fn(std::integral_constant<int, N>{});
+    CMBL_PL_ORDERS(CMBL_X)
+#undef CMBL_X
+    default: fail(ERR_ARG, std::string(who) + ": order outside " + (FIRST ? "1" : "0") + "..12");
+  }
+}
 
 template <typename T>
 struct PowerLens : PowerLensApi {
@@ -28,13 +38,13 @@ struct PowerLens : PowerLensApi {
   const int order;
   const bool taylens;
   bool ready = false;
-  T dx;                                      // Δx in T (src/proj_lambert.jl:58)
+  const T dx;                                // Δx in T
   DevBuf defl, u, src;                       // deflection maps [2][npix] (x then y, radians); the table
   DevBuf phiF, gF;                           // set_phi scratch
-  DevBuf fF, dF, dmaps, inm, outm;           // F of the argument (the adjoint's result), the planes and maps of one order, boundary maps
+  DevBuf fF, dF, dmaps, inm, outm;           // F of the argument (the adjoint's result), the planes and maps of one order, boundary maps (Ctx::as_maps / map_dst)
   static constexpr int V = 16 / sizeof(T);   // reals per vector access
 
-  PowerLens(Ctx<T>* ctx, int order_, int kind) : c(ctx), order(order_), taylens(kind == PL_TAYLENS), dx((T)(ctx->theta / 60.0 * M_PI / 180.0)) {}
+  PowerLens(Ctx<T>* ctx, int order_, int kind) : c(ctx), order(order_), taylens(kind == PL_TAYLENS), dx(ctx->dx()) {}
   PowerLens(const PowerLens&) = delete;
   PowerLens& operator=(const PowerLens&) = delete;
 
@@ -45,8 +55,8 @@ struct PowerLens : PowerLensApi {
     for (int a = 0; a <= n; ++a) cf.c[a] = (T)(1.0 / (fact[a] * fact[n - a]));
     return cf;
   }
-  dim3 fgrid() const { return dim3((unsigned)((c->plane() + NTP - 1) / NTP)); }
-  dim3 pgrid(int v) const { return dim3((unsigned)((c->npix() / v + NTP - 1) / NTP)); }
+  dim3 fgrid() const { return dim3(nblocks(c->plane())); }
+  dim3 pgrid(int v) const { return dim3(nblocks(c->npix() / v)); }
   // V pixels per thread where every plane of every array starts on a 16-byte boundary
   bool vec(std::initializer_list<const void*> ps) const {
     if (c->npix() % V) return false;
@@ -64,74 +74,46 @@ struct PowerLens : PowerLensApi {
   }
   void set_phi(int basis, const void* phi, int nb) override {
     CMBL_REQUIRE(nb == 1, ERR_SHAPE, "PowerLens / Taylens with a batched phi is not implemented (require_unbatched, src/powerlens.jl:25, src/taylens.jl:27)");
-    const long np = c->npix(), pl = c->plane();
-    phiF.ensure(sizeof(cx<T>) * pl); gF.ensure(sizeof(cx<T>) * 2 * pl); defl.ensure(sizeof(T) * 2 * np);
-    c->to_F(basis, phi, phiF.as<cx<T>>(), B_FOURIER, 1, 1);
-    CMBL_LAUNCH(c, K_PL, (k_bl_gradmult<T>), fgrid(), 0, c->stream, (const cx<T>*)phiF.as<cx<T>>(), gF.as<cx<T>>(), c->lx_r.template as<T>(), c->ly.template as<T>(),
-                c->Nx, pl, 1);
-    c->F_to_map(gF.as<cx<T>>(), defl.as<T>(), 2);                           // d = ∇ϕ (src/powerlens.jl:23)
+    c->deflection_maps(basis, phi, phiF, gF, defl, K_PL);                   // d = ∇ϕ (src/powerlens.jl:23)
     table();
   }
   void set_deflection(const void* dy_rad, const void* dx_rad) override {
-    const long np = c->npix();
-    defl.ensure(sizeof(T) * 2 * np);
-    CMBL_HIP(hipMemcpyAsync(defl.as<T>(), dx_rad, sizeof(T) * np, hipMemcpyDeviceToDevice, c->stream));
-    CMBL_HIP(hipMemcpyAsync(defl.as<T>() + np, dy_rad, sizeof(T) * np, hipMemcpyDeviceToDevice, c->stream));
+    c->deflection_maps(dy_rad, dx_rad, defl);
     table();
   }
 
   void mult(int n, const cx<T>* F, cx<T>* out, int S) {
-    switch (n) {
-#define CMBL_X(N) case N: CMBL_LAUNCH(c, K_PL, (k_pl_mult<T, N>), fgrid(), 0, c->stream, F, out, c->lx_r.template as<T>(), c->ly.template as<T>(), dx, c->Nx, c->plane(), S); break;
-      CMBL_PL_ORDERS(CMBL_X)
-#undef CMBL_X
-      default: fail(ERR_ARG, "PowerLens: order outside 1..12");
-    }
+    by_order<1>(n, "PowerLens", [&](auto o) {
+      CMBL_LAUNCH(c, K_PL, (k_pl_mult<T, decltype(o)::value>), fgrid(), 0, c->stream, F, out, c->lx_r.template as<T>(), c->ly.template as<T>(), dx, c->Nx, c->plane(), S);
+    });
   }
   void combine(int n, const cx<T>* G, cx<T>* r, int S) {
-    switch (n) {
-#define CMBL_X(N) case N: CMBL_LAUNCH(c, K_PL, (k_pl_combine<T, N>), fgrid(), 0, c->stream, G, r, c->lx_r.template as<T>(), c->ly.template as<T>(), dx, c->Nx, c->plane(), S); break;
-      CMBL_PL_ORDERS(CMBL_X)
-#undef CMBL_X
-      default: fail(ERR_ARG, "PowerLens: order outside 1..12");
-    }
+    by_order<1>(n, "PowerLens", [&](auto o) {
+      CMBL_LAUNCH(c, K_PL, (k_pl_combine<T, decltype(o)::value>), fgrid(), 0, c->stream, G, r, c->lx_r.template as<T>(), c->ly.template as<T>(), dx, c->Nx, c->plane(), S);
+    });
   }
   void premul(int n, const T* g, T* W, int S) {
     const bool v = vec({g, W});
-    switch (n) {
-#define CMBL_X(N) case N: \
-      if (v) CMBL_LAUNCH(c, K_PL, (k_pl_premul<T, N, V>), pgrid(V), 0, c->stream, (const cx<T>*)u.as<cx<T>>(), g, W, coef(N), c->npix(), S); \
-      else CMBL_LAUNCH(c, K_PL, (k_pl_premul<T, N, 1>), pgrid(1), 0, c->stream, (const cx<T>*)u.as<cx<T>>(), g, W, coef(N), c->npix(), S); \
-      break;
-      CMBL_PL_ORDERS(CMBL_X)
-#undef CMBL_X
-      default: fail(ERR_ARG, "PowerLens: order outside 1..12");
-    }
+    by_order<1>(n, "PowerLens", [&](auto o) {
+      constexpr int N = decltype(o)::value;
+      if (v) CMBL_LAUNCH(c, K_PL, (k_pl_premul<T, N, V>), pgrid(V), 0, c->stream, (const cx<T>*)u.as<cx<T>>(), g, W, coef(N), c->npix(), S);
+      else CMBL_LAUNCH(c, K_PL, (k_pl_premul<T, N, 1>), pgrid(1), 0, c->stream, (const cx<T>*)u.as<cx<T>>(), g, W, coef(N), c->npix(), S);
+    });
   }
   // out = base + the terms of total order n (n = 0: Taylens' permutation of base alone)
   void accum(int n, const T* D, const T* base, T* out, bool gather_base, int S) {
     const cx<T>* uu = u.as<cx<T>>(); const unsigned* sp = src.as<unsigned>();
     const long np = c->npix();
-    if (taylens) {
-      switch (n) {
-        case 0: CMBL_LAUNCH(c, K_PL, (k_pl_accum<T, 0, true, 1>), pgrid(1), 0, c->stream, uu, sp, D, base, out, coef(0), gather_base ? 1 : 0, np, S); break;
-#define CMBL_X(N) case N: CMBL_LAUNCH(c, K_PL, (k_pl_accum<T, N, true, 1>), pgrid(1), 0, c->stream, uu, sp, D, base, out, coef(N), gather_base ? 1 : 0, np, S); break;
-        CMBL_PL_ORDERS(CMBL_X)
-#undef CMBL_X
-        default: fail(ERR_ARG, "Taylens: order outside 0..12");
-      }
-      return;
-    }
+    if (taylens)
+      return by_order<0>(n, "Taylens", [&](auto o) {
+        CMBL_LAUNCH(c, K_PL, (k_pl_accum<T, decltype(o)::value, true, 1>), pgrid(1), 0, c->stream, uu, sp, D, base, out, coef(decltype(o)::value), gather_base ? 1 : 0, np, S);
+      });
     const bool v = vec({D, base, out});
-    switch (n) {
-#define CMBL_X(N) case N: \
-      if (v) CMBL_LAUNCH(c, K_PL, (k_pl_accum<T, N, false, V>), pgrid(V), 0, c->stream, uu, sp, D, base, out, coef(N), 0, np, S); \
-      else CMBL_LAUNCH(c, K_PL, (k_pl_accum<T, N, false, 1>), pgrid(1), 0, c->stream, uu, sp, D, base, out, coef(N), 0, np, S); \
-      break;
-      CMBL_PL_ORDERS(CMBL_X)
-#undef CMBL_X
-      default: fail(ERR_ARG, "PowerLens: order outside 1..12");
-    }
+    by_order<1>(n, "PowerLens", [&](auto o) {
+      constexpr int N = decltype(o)::value;
+      if (v) CMBL_LAUNCH(c, K_PL, (k_pl_accum<T, N, false, V>), pgrid(V), 0, c->stream, uu, sp, D, base, out, coef(N), 0, np, S);
+      else CMBL_LAUNCH(c, K_PL, (k_pl_accum<T, N, false, 1>), pgrid(1), 0, c->stream, uu, sp, D, base, out, coef(N), 0, np, S);
+    });
   }
 
   void apply(int mode, int bi, const void* in, int bo, void* out, int P, int B) override {
@@ -140,24 +122,17 @@ struct PowerLens : PowerLensApi {
     CMBL_REQUIRE(ready, ERR_STATE, "cmbl_powerlens_set_phi / cmbl_powerlens_set_deflection has not been called");
     const int S = P * B;
     const long np = c->npix(), pl = c->plane(), sn = (long)S * np;
-    if (order == 0 && !taylens && mode == F_FWD) {                          // the loop of :44 is empty: a copy, with no transform where both sides are Fourier
-      if (bi == B_MAP && bo == B_MAP) { if (in != out) CMBL_HIP(hipMemcpyAsync(out, in, sizeof(T) * sn, hipMemcpyDeviceToDevice, c->stream)); return; }
-      fF.ensure(sizeof(cx<T>) * S * pl);
-      const int carry = bi == B_MAP ? (bo == B_HARMONIC ? B_HARMONIC : B_FOURIER) : bi;
-      c->to_F(bi, in, fF.as<cx<T>>(), carry, P, B);
-      c->from_F(fF.as<cx<T>>(), carry, bo, out, P, B);
-      return;
-    }
+    // the loop of :44 is empty: a copy, with no transform where both sides are Fourier
+    if (order == 0 && !taylens && mode == F_FWD) return c->convert(bi, in, bo, out, P, B, fF);
     // every buffer before the first launch: growing one frees it
     fF.ensure(sizeof(cx<T>) * S * pl);
     if (order > 0) { dF.ensure(sizeof(cx<T>) * (order + 1) * S * pl); dmaps.ensure(sizeof(T) * (order + 1) * sn); if (!c->generic) c->mixed_scratch((long)(order + 1) * S); }
     if (bi != B_MAP) inm.ensure(sizeof(T) * sn);
     outm.ensure(sizeof(T) * sn);
     cx<T>* F = fF.as<cx<T>>();
-    // the argument as maps AND as QU Fourier planes: both sums need both
-    const T* fm = (const T*)in;
-    if (order > 0 || bi != B_MAP || mode == F_ADJ) c->to_F(bi, in, F, B_FOURIER, P, B);
-    if (bi != B_MAP) { c->F_to_map(F, inm.as<T>(), S); fm = inm.as<T>(); }
+    // the argument as maps AND as QU Fourier planes: both sums need both (as_maps leaves the planes in fF)
+    if (bi == B_MAP && (order > 0 || mode == F_ADJ)) c->to_F(bi, in, F, B_FOURIER, P, B);
+    const T* fm = c->as_maps(bi, in, fF, inm, P, B);
     if (mode == F_ADJ) {                                                    // r = Ð(g) + ...  (src/powerlens.jl:54-57)
       for (int n = 1; n <= order; ++n) {
         premul(n, fm, dmaps.as<T>(), S);
@@ -167,18 +142,14 @@ struct PowerLens : PowerLensApi {
       c->from_F(F, B_FOURIER, bo, out, P, B);
       return;
     }
-    // a MAP result goes straight to `out` unless that is the argument itself (Taylens gathers from it)
-    T* dst = (bo == B_MAP && (const void*)fm != out) ? (T*)out : outm.as<T>();
+    T* dst = c->map_dst(bo, out, fm, outm, S);                              // Taylens gathers from the argument
     if (order == 0) accum(0, nullptr, fm, dst, true, S);                    // Taylens(0): the loop of src/taylens.jl:62 is empty, the permutation stays
     for (int n = 1; n <= order; ++n) {
       mult(n, F, dF.as<cx<T>>(), S);
       c->F_to_map(dF.as<cx<T>>(), dmaps.as<T>(), (long)(n + 1) * S);
       accum(n, dmaps.as<T>(), n == 1 ? fm : dst, dst, n == 1, S);
     }
-    if (bo != B_MAP) {
-      c->rfft2_F(dst, F, S);
-      c->from_F(F, B_FOURIER, bo, out, P, B);
-    } else if (dst != (T*)out) CMBL_HIP(hipMemcpyAsync(out, dst, sizeof(T) * sn, hipMemcpyDeviceToDevice, c->stream));
+    c->map_finish(dst, bo, out, fF, P, B);
   }
 };
 

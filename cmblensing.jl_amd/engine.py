@@ -34,9 +34,27 @@ def reference_exact():
     return os.environ.get("CMBL_REFERENCE_EXACT", "0") not in ("", "0")
 
 
-class ProjLambert:
+class _Handle:
+    """Owner of one handle of the C ABI: `_h`, made by `lib.<create>(..., &_h)`, destroyed with the object by `lib.<_destroy>(_h)`."""
+    _destroy = None                      # name of the cmbl_*_destroy function
+
+    def _open(self, lib, create, *args):
+        self.lib, self._h = lib, ctypes.c_void_p()
+        check(getattr(lib, create)(*args, ctypes.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if self._h:
+                getattr(self.lib, self._destroy)(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+class ProjLambert(_Handle):
     """Context: geometry + FFT tables + stream.  `T` is torch.float32 or torch.float64.  `rotator`: the (z, y, x) Euler angles in degrees
     that place the patch on the sphere (src/proj_lambert.jl:29, 45); only the HEALPix projection (healpix.py) reads it."""
+    _destroy = "cmbl_ctx_destroy"
 
     def __init__(self, Ny, Nx, theta_pix=1.0, T=torch.float32, device=0, rotator=(0, 90, 0)):
         self.rotator = tuple(float(v) for v in rotator)
@@ -44,25 +62,14 @@ class ProjLambert:
             raise ValueError("rotator: three angles in degrees (z, y, x)")
         if not torch.cuda.is_available():
             raise RuntimeError("cmblensing_jl_amd needs a HIP device (no CPU fallback)")
-        self.lib = load_library()
         self.Ny, self.Nx, self.Nyh, self.theta_pix = int(Ny), int(Nx), int(Ny) // 2 + 1, float(theta_pix)
         self.T = T
         self.CT = torch.complex64 if T == torch.float32 else torch.complex128
         self.device = torch.device("cuda", device)
-        self._h = ctypes.c_void_p()
         torch.cuda.set_device(self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        check(self.lib.cmbl_ctx_create(self.Ny, self.Nx, self.theta_pix, 0 if T == torch.float32 else 1,
-                                       device, ctypes.c_void_p(stream), ctypes.byref(self._h)))
+        self._open(load_library(), "cmbl_ctx_create", self.Ny, self.Nx, self.theta_pix, 0 if T == torch.float32 else 1, device, ctypes.c_void_p(stream))
         self._geom = {}
-
-    def __del__(self):
-        try:
-            if self._h:
-                self.lib.cmbl_ctx_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
     # geometry (host numpy, float64 copies of the T-precision values the kernels use)
     def _g(self, which, shape):
@@ -447,26 +454,18 @@ _CL_PLANE = {1: {"I": 0}, 2: {"Q": 0, "U": 1, "E": 0, "B": 1}, 3: {"I": 0, "Q": 
 _CL_WHICH = {1: "II", 2: ("EE", "BB"), 3: ("II", "EE", "BB", "IE", "IB", "EB")}       # the reference's defaults (:505, 510)
 
 
-class _ClPlan:
+class _ClPlan(_Handle):
     """binning plan of one (context, edges, weight plane): cmbl_clbins_*; A, Sℓ and the full-plane mode counts per bin are host arrays"""
+    _destroy = "cmbl_clbins_destroy"
 
     def __init__(self, proj, ledges, w):
-        self.lib, self.ledges, self.nbins = proj.lib, ledges, len(ledges) - 1
-        self._h = ctypes.c_void_p()
+        self.ledges, self.nbins = ledges, len(ledges) - 1
         pd = ctypes.POINTER(ctypes.c_double)
-        check(self.lib.cmbl_clbins_create(proj._h, ledges.ctypes.data_as(pd), len(ledges), None if w is None else w.ctypes.data_as(pd),
-                                          0 if w is None else w.size, ctypes.byref(self._h)))
+        self._open(proj.lib, "cmbl_clbins_create", proj._h, ledges.ctypes.data_as(pd), len(ledges), None if w is None else w.ctypes.data_as(pd),
+                   0 if w is None else w.size)
         self.A, self.Sl, self.count = (np.empty(self.nbins) for _ in range(3))
         for which, a in enumerate((self.A, self.Sl, self.count)):
             check(self.lib.cmbl_clbins_info_host(self._h, which, a.ctypes.data_as(pd), a.size))
-
-    def __del__(self):
-        try:
-            if self._h:
-                self.lib.cmbl_clbins_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
 
 def _cl_plan(proj, dl, ledges, Clfid):
@@ -612,65 +611,76 @@ class _Adjoint:
     def __init__(self, L):
         self.L = L
 
-    def __mul__(self, g):            # L' * g
+    def __mul__(self, g):                    # L' * g
         return self.L._apply(FLOW_ADJ, g)
 
-    def ldiv(self, g):               # L' \ g
-        return self.L._apply(FLOW_INVADJ, g)
+    def ldiv(self, g, *extra, **kw):         # L' \ g
+        return self.L._apply(FLOW_INVADJ, g, None, *extra, **kw)
 
 
-class LenseFlow:
-    """`LenseFlow(ϕ, n)` / `CachedLenseFlow` (src/lenseflow.jl:19-60): `L(ϕ)` re-caches only when ϕ is a
-    different object (src/lenseflow.jl:123-129)."""
+class _LensOp(_Handle):
+    """What the lensing operators share on top of cmbl_<_abi>_{create, destroy, set_phi, apply}: `L(ϕ)` / `L.set_phi(ϕ)` re-set ϕ only for a
+    different object, `L * f`, `L.ldiv(f)`, `L.adjoint * g`, `L.adjoint.ldiv(g)`.  `extra`: what the class' `_extra` takes (BilinearLens: maxiter).
+    An action that the reference does not define for a class is refused by the library (PowerLens has no inverse)."""
+    _abi = None
+    _basis_out = {FLOW_FWD: MAP, FLOW_INV: MAP, FLOW_ADJ: MAP, FLOW_INVADJ: MAP}      # Ł / Ð of each mode's result when none is asked for
+    _destroy = property(lambda s: f"cmbl_{s._abi}_destroy")
 
-    def __init__(self, proj, nsteps=7):
-        self.proj, self.nsteps = proj, int(nsteps)
-        self.lib = proj.lib
-        self._h = ctypes.c_void_p()
-        check(self.lib.cmbl_lenseflow_create(proj._h, self.nsteps, ctypes.byref(self._h)))
-        self._phi = None
-
-    def __del__(self):
-        try:
-            if self._h:
-                self.lib.cmbl_lenseflow_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+    def _create(self, proj, *args):
+        self.proj, self._phi = proj, None
+        self._open(proj.lib, f"cmbl_{self._abi}_create", proj._h, *args)
+        self._c_set_phi, self._c_apply = (getattr(self.lib, f"cmbl_{self._abi}_{fn}") for fn in ("set_phi", "apply"))
 
     def __call__(self, phi):
-        """phi: Field (MAP or FOURIER, P=1)."""
+        """phi: Field (P=1; B=1 unless the class takes a batched ϕ)."""
         if self._phi is not phi:
             P, B = self.proj._check(phi.arr, phi.basis)
             assert P == 1
-            check(self.lib.cmbl_lenseflow_set_phi(self._h, phi.basis, _ptr(phi.arr), B))
+            check(self._c_set_phi(self._h, phi.basis, _ptr(phi.arr), B))
             self._phi = phi
         return self
+
+    def set_phi(self, phi):
+        return self(phi)
 
     def invalidate(self):
         self._phi = None
 
     @property
-    def phi(self):                                   # getϕ (src/lenseflow.jl:69-70)
+    def phi(self):                           # getϕ (src/lenseflow.jl:69-70)
         return self._phi
 
-    def _apply(self, mode, f, basis_out=None):
+    def _extra(self):                        # what cmbl_<_abi>_apply takes after nbatch
+        return ()
+
+    def _apply(self, mode, f, basis_out=None, *extra, **kw):
         P, B = self.proj._check(f.arr, f.basis)
         if basis_out is None:
-            basis_out = MAP if mode in (FLOW_FWD, FLOW_INV) else FOURIER      # Ł / Ð of the result (src/flowops.jl:11-14)
+            basis_out = self._basis_out[mode]
         out = self.proj.empty(basis_out, P, B)
-        check(self.lib.cmbl_lenseflow_apply(self._h, mode, f.basis, _ptr(f.arr), basis_out, _ptr(out), P, B))
+        check(self._c_apply(self._h, mode, f.basis, _ptr(f.arr), basis_out, _ptr(out), P, B, *self._extra(*extra, **kw)))
         return Field(self.proj, out, basis_out)
 
-    def __mul__(self, f):            # L * f
+    def __mul__(self, f):                    # L * f
         return self._apply(FLOW_FWD, f)
 
-    def ldiv(self, f):               # L \ f
-        return self._apply(FLOW_INV, f)
+    def ldiv(self, f, *extra, **kw):         # L \ f
+        return self._apply(FLOW_INV, f, None, *extra, **kw)
 
     @property
     def adjoint(self):
         return _Adjoint(self)
+
+
+class LenseFlow(_LensOp):
+    """`LenseFlow(ϕ, n)` / `CachedLenseFlow` (src/lenseflow.jl:19-60): `L(ϕ)` re-caches only when ϕ is a
+    different object (src/lenseflow.jl:123-129).  phi: Field (MAP or FOURIER, P=1)."""
+    _abi = "lenseflow"
+    _basis_out = {FLOW_FWD: MAP, FLOW_INV: MAP, FLOW_ADJ: FOURIER, FLOW_INVADJ: FOURIER}      # src/flowops.jl:11-14
+
+    def __init__(self, proj, nsteps=7):
+        self.nsteps = int(nsteps)
+        self._create(proj, self.nsteps)
 
     def max_lensing_step(self, phi, eta):
         """get_max_lensing_step (src/lenseflow.jl:242-256), one value per batch slot"""
@@ -695,44 +705,17 @@ class LenseFlow:
         return Field(self.proj, dphi, FOURIER), Field(self.proj, df, basis_df), Field(self.proj, fstart, MAP)
 
 
-class _BilinearAdjoint:
-    def __init__(self, L):
-        self.L = L
-
-    def __mul__(self, g):            # L' * g
-        return self.L._apply(FLOW_ADJ, g)
-
-    def ldiv(self, g, maxiter=5):    # L' \\ g
-        return self.L._apply(FLOW_INVADJ, g, maxiter=maxiter)
-
-
-class BilinearLens:
+class BilinearLens(_LensOp):
     """`BilinearLens(ϕ)` (src/bilinearlens.jl): lensing by bilinear interpolation, with the surface of `LenseFlow`.  `L(ϕ)` rebuilds the
-    interpolation table only when ϕ is a different object; one ϕ serves any number of batch slots of f (a batched ϕ raises, :40)."""
+    interpolation table only when ϕ is a different object (any basis, P=1, B=1); one ϕ serves any number of batch slots of f (a batched ϕ
+    raises, :40).  The reference returns Ł fields from all four actions (:109-114); `ldiv(f, maxiter=5)`: the GMRES iterations."""
+    _abi = "bilinear"
 
     def __init__(self, proj):
-        self.proj = proj
-        self.lib = proj.lib
-        self._h = ctypes.c_void_p()
-        check(self.lib.cmbl_bilinear_create(proj._h, ctypes.byref(self._h)))
-        self._phi = None
+        self._create(proj)
 
-    def __del__(self):
-        try:
-            if self._h:
-                self.lib.cmbl_bilinear_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def __call__(self, phi):
-        """phi: Field (any basis, P=1, B=1)."""
-        if self._phi is not phi:
-            P, B = self.proj._check(phi.arr, phi.basis)
-            assert P == 1
-            check(self.lib.cmbl_bilinear_set_phi(self._h, phi.basis, _ptr(phi.arr), B))
-            self._phi = phi
-        return self
+    def _extra(self, maxiter=5):
+        return (int(maxiter),)
 
     def set_deflection(self, dy, dx):
         """Lensing by a given displacement: pixel (i, j) reads (i + dy, j + dx), `dy` along Ny and `dx` along Nx in pixels, maps of shape (Nx, Ny)."""
@@ -741,29 +724,6 @@ class BilinearLens:
         check(self.lib.cmbl_bilinear_set_deflection(self._h, _ptr(dy), _ptr(dx)))
         self._phi = None
         return self
-
-    def invalidate(self):
-        self._phi = None
-
-    @property
-    def phi(self):
-        return self._phi
-
-    def _apply(self, mode, f, basis_out=MAP, maxiter=5):
-        P, B = self.proj._check(f.arr, f.basis)
-        out = self.proj.empty(basis_out, P, B)                          # the reference returns Ł fields from all four (:109-114)
-        check(self.lib.cmbl_bilinear_apply(self._h, mode, f.basis, _ptr(f.arr), basis_out, _ptr(out), P, B, int(maxiter)))
-        return Field(self.proj, out, basis_out)
-
-    def __mul__(self, f):            # L * f
-        return self._apply(FLOW_FWD, f)
-
-    def ldiv(self, f, maxiter=5):    # L \\ f
-        return self._apply(FLOW_INV, f, maxiter=maxiter)
-
-    @property
-    def adjoint(self):
-        return _BilinearAdjoint(self)
 
     def gradient(self, f_lensed, delta, basis_df=None):
         """Pullback of `L*f` (src/bilinearlens.jl:165-171).  f_lensed: the primal output (map Field); delta: cotangent.  Returns (δϕ [FOURIER], δf)."""
@@ -776,45 +736,22 @@ class BilinearLens:
         return Field(self.proj, dphi, FOURIER), Field(self.proj, df, basis_df)
 
 
-class _PowerLensAdjoint:
-    def __init__(self, L):
-        self.L = L
-
-    def __mul__(self, g):            # L' * g, in the Fourier basis as the reference returns it (src/powerlens.jl:54)
-        return self.L._apply(FLOW_ADJ, g, basis_out=FOURIER)
-
-
-class PowerLens:
+class PowerLens(_LensOp):
     """`PowerLens(ϕ, order)` (src/powerlens.jl): lensing by the Taylor series in ∇ϕ up to `order` (0 ... 12), with the part of `BilinearLens`'
-    surface that the reference defines: `L(ϕ)` / `set_phi`, `set_deflection`, `L * f` and `L.adjoint * g`.  One ϕ serves any number of
-    batch slots of f (a batched ϕ raises, :25)."""
+    surface that the reference defines: `L(ϕ)` / `set_phi` (any basis, P=1, B=1), `set_deflection`, `L * f` and `L.adjoint * g`.  One ϕ serves any
+    number of batch slots of f (a batched ϕ raises, :25)."""
+    _abi = "powerlens"
     _kind = 0                        # CMBL_POWERLENS
+    _basis_out = {**_LensOp._basis_out, FLOW_ADJ: FOURIER}       # the adjoint in the Fourier basis, as the reference returns it (src/powerlens.jl:54)
+    _defl = None                     # the (dy, dx) of set_deflection, for antilensing
 
     def __init__(self, proj, order):
-        self.proj, self.order = proj, int(order)
-        self.lib = proj.lib
-        self._h = ctypes.c_void_p()
-        check(self.lib.cmbl_powerlens_create(proj._h, self.order, self._kind, ctypes.byref(self._h)))
-        self._phi = self._defl = None
-
-    def __del__(self):
-        try:
-            if self._h:
-                self.lib.cmbl_powerlens_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        self.order = int(order)
+        self._create(proj, self.order, self._kind)
 
     def __call__(self, phi):
-        """phi: Field (any basis, P=1, B=1)."""
-        if self._phi is not phi:
-            P, B = self.proj._check(phi.arr, phi.basis)
-            assert P == 1
-            check(self.lib.cmbl_powerlens_set_phi(self._h, phi.basis, _ptr(phi.arr), B))
-            self._phi, self._defl = phi, None
-        return self
-
-    set_phi = __call__
+        self._defl = None
+        return super().__call__(phi)
 
     def set_deflection(self, dy, dx):
         """`PowerLens(d::FieldVector, order)` (:24): the deflection along Ny (`dy`) and along Nx (`dx`) in RADIANS, maps of shape (Nx, Ny)."""
@@ -823,23 +760,6 @@ class PowerLens:
         check(self.lib.cmbl_powerlens_set_deflection(self._h, _ptr(dy), _ptr(dx)))
         self._phi, self._defl = None, (dy, dx)
         return self
-
-    @property
-    def phi(self):
-        return self._phi
-
-    def _apply(self, mode, f, basis_out=MAP):
-        P, B = self.proj._check(f.arr, f.basis)
-        out = self.proj.empty(basis_out, P, B)
-        check(self.lib.cmbl_powerlens_apply(self._h, mode, f.basis, _ptr(f.arr), basis_out, _ptr(out), P, B))
-        return Field(self.proj, out, basis_out)
-
-    def __mul__(self, f):            # L * f
-        return self._apply(FLOW_FWD, f)
-
-    @property
-    def adjoint(self):
-        return _PowerLensAdjoint(self)
 
 
 class Taylens(PowerLens):
@@ -862,7 +782,7 @@ def antilensing(L):
     return A.set_deflection(-L._defl[0], -L._defl[1])
 
 
-class BaseDataSet:
+class BaseDataSet(_Handle):
     """`BaseDataSet` at fiducial θ (src/dataset.jl:37-57) with the operators resident on the device.
 
     ops: dict name -> real planes (numpy/torch, reference layout):
@@ -870,13 +790,13 @@ class BaseDataSet:
         'Cphi_inv','G_inv' : (1, Nx, Nyh) ;  'Mpix' : (Nx, Ny) optional
     d: harmonic-basis data (B,P,Nx,Nyh); logdet_sum: logdet Cf + logdet Cϕ + logdet Cn.
     """
+    _destroy = "cmbl_dataset_destroy"
     _ids = dict(Cf_inv=OP_CF_INV, Cn_inv=OP_CN_INV, B=OP_B, Mf=OP_MF, D=OP_D, D_inv=OP_D_INV,
                 precond_inv=OP_PRECOND_INV, Cphi_inv=OP_CPHI_INV, G_inv=OP_G_INV, Mpix=OP_MPIX)
 
     def __init__(self, proj, P, ops, d=None, logdet_sum=0.0, nsteps=7):
-        self.proj, self.P, self.lib = proj, int(P), proj.lib
-        self._h = ctypes.c_void_p()
-        check(self.lib.cmbl_dataset_create(proj._h, self.P, ctypes.byref(self._h)))
+        self.proj, self.P = proj, int(P)
+        self._open(proj.lib, "cmbl_dataset_create", proj._h, self.P)
         self.L = LenseFlow(proj, nsteps)
         self.ops = {}
         for k, v in ops.items():
@@ -897,14 +817,6 @@ class BaseDataSet:
         # (and starts every context with plain working-precision sums, the reference's `sum_accuracy_mode`).
         self.alias_quirk = reference_exact()
         check(self.lib.cmbl_dataset_set_logdet(self._h, self.logdet_sum))
-
-    def __del__(self):
-        try:
-            if self._h:
-                self.lib.cmbl_dataset_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
     def set_logdet(self, logdet_sum):
         self.logdet_sum = float(logdet_sum)

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from .lib import load_library, check
-from .engine import ProjLambert, Field, MAP, _ptr
+from .engine import ProjLambert, Field, MAP, _ptr, _Handle
 from .equirect import ProjEquiRect, EquiRectField
 
 _PD = ctypes.POINTER(ctypes.c_double)
@@ -143,10 +143,11 @@ def _method(method):
         raise ValueError(f'method must be "bilinear" (or "fft", not implemented), got {method!r}')
 
 
-class Projector:
+class Projector(_Handle):
     """`Projector(hpx_proj => cart_proj; method)` (:254-306): what both directions of `project` precompute, on the device.  Either order of
     the two projections.  Host readbacks (float64 / int64 NumPy, cached): `thetas`, `phis`, `psi_cart` (Ny Nx, Ny fastest: the reference's
     θs, ϕs, ψpol_θϕs), `hpx_idxs_in_patch`, and for the touched pixels (0 < i < Ny+1, 0 < j < Nx+1) `touched`, `is_`, `js`, `psi_hpx`."""
+    _destroy = "cmbl_projector_destroy"
 
     def __init__(self, hpx_proj, cart_proj, method="bilinear"):
         if isinstance(cart_proj, ProjHealpix):
@@ -155,22 +156,12 @@ class Projector:
         if not isinstance(hpx_proj, ProjHealpix) or not isinstance(cart_proj, (ProjLambert, ProjEquiRect)):
             raise TypeError("Projector: a ProjHealpix and a ProjLambert or ProjEquiRect are needed")
         self.hpx_proj, self.cart_proj, self.method = hpx_proj, cart_proj, method
-        self.lib = cart_proj.lib
         if isinstance(cart_proj, ProjEquiRect):
             kind, params = 1, list(cart_proj.theta_span) + list(cart_proj.phi_span)
         else:
             kind, params = 0, list(cart_proj.rotator)
-        self._h = ctypes.c_void_p()
-        check(self.lib.cmbl_projector_create(cart_proj._h, hpx_proj.Nside, kind, (ctypes.c_double * len(params))(*params), ctypes.byref(self._h)))
+        self._open(cart_proj.lib, "cmbl_projector_create", cart_proj._h, hpx_proj.Nside, kind, (ctypes.c_double * len(params))(*params))
         self._info = {}
-
-    def __del__(self):
-        try:
-            if self._h:
-                self.lib.cmbl_projector_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
     def _get(self, which, n):
         if which not in self._info:
