@@ -603,18 +603,25 @@ int cmbl_healpix_pix2ang_host(int nside, long first, long n, double* theta, doub
   });
 }
 int cmbl_projector_create(cmbl_ctx* ctx, int nside, int cart_kind, const double* params, cmbl_projector** out) {
+  return cmbl_projector_create_method(ctx, nside, cart_kind, params, CMBL_PROJECT_BILINEAR, out);
+}
+int cmbl_projector_create_method(cmbl_ctx* ctx, int nside, int cart_kind, const double* params, int method, cmbl_projector** out) {
   return guard([&] {
     NOTNULL(ctx); NOTNULL(params); NOTNULL(out);
+    CMBL_REQUIRE(method == CMBL_PROJECT_BILINEAR || method == CMBL_PROJECT_NFFT, ERR_ARG, "method must be CMBL_PROJECT_BILINEAR or CMBL_PROJECT_NFFT");
     CMBL_REQUIRE(hpx_nside_ok(nside), ERR_SHAPE, "Nside must be a power of two in 1 ... 8192");
     CMBL_REQUIRE(cart_kind == CMBL_PROJ_LAMBERT || cart_kind == CMBL_PROJ_EQUIRECT, ERR_ARG, "cart_kind must be CMBL_PROJ_LAMBERT or CMBL_PROJ_EQUIRECT");
     for (int k = 0; k < (cart_kind == CMBL_PROJ_LAMBERT ? 3 : 4); ++k) CMBL_REQUIRE(std::isfinite(params[k]), ERR_ARG, "projector: params must be finite");
     auto h = std::make_unique<cmbl_projector>();
     h->ctx = ctx;
-    BY_DTYPE(ctx, do_projector_create, h.get(), nside, cart_kind, params);
+    BY_DTYPE(ctx, do_projector_create, h.get(), nside, cart_kind, params, method);
     *out = h.release();
   });
 }
 int cmbl_projector_destroy(cmbl_projector* P) { return guard([&] { delete P; }); }
+int cmbl_projector_method(cmbl_projector* P, int* method, int* window_width) {
+  return guard([&] { NOTNULL(P); NOTNULL(method); NOTNULL(window_width); *method = P->p->method(); *window_width = P->p->width(); });
+}
 int cmbl_projector_info_host(cmbl_projector* P, int which, double* out_host, size_t n) {
   return guard([&] { NOTNULL(P); NOTNULL(out_host); P->p->info(which, out_host, n); });
 }

@@ -200,7 +200,10 @@ template <typename T> void do_flow_create(cmbl_flow* h, int nsteps) { h->p = std
 template <typename T> void do_dataset_create(cmbl_dataset* h, int npol) { h->p = std::make_unique<Dataset<T>>(C<T>(h->ctx), npol); }
 template <typename T> void do_bl_create(cmbl_bilinear* h) { h->p = std::make_unique<Bilinear<T>>(C<T>(h->ctx)); }
 template <typename T> void do_pl_create(cmbl_powerlens* h, int order, int kind) { h->p = std::make_unique<PowerLens<T>>(C<T>(h->ctx), order, kind); }
-template <typename T> void do_projector_create(cmbl_projector* h, int nside, int kind, const double* params) { h->p = std::make_unique<Projector<T>>(C<T>(h->ctx), nside, kind, params); }
+template <typename T> void do_projector_create(cmbl_projector* h, int nside, int kind, const double* params, int method) {
+  if (method == PROJECT_NFFT) h->p = std::make_unique<NfftProjector<T>>(C<T>(h->ctx), nside, kind, params);
+  else h->p = std::make_unique<Projector<T>>(C<T>(h->ctx), nside, kind, params);
+}
 template <typename T> void do_axpby(cmbl_ctx* ctx, const double* a, const void* x, const double* b, const void* y, void* out, long n, int B) {
   C<T>(ctx)->lincomb((T*)out, (const T*)x, (const T*)y, a, b, n, B);
 }

@@ -29,6 +29,8 @@ struct ProjectorApi {                        // what the C ABI (api.hip) holds o
   virtual void to_cart(const void* hpx, void* map_out, int P, int B) = 0;
   virtual void to_healpix(int bi, const void* in, void* hpx_out, int P, int B) = 0;
   virtual void info(int which, double* out, size_t n) = 0;
+  virtual int method() const { return 0; }          // CMBL_PROJECT_BILINEAR; engine_nfft.hpp has the other one
+  virtual int width() const { return 0; }           // cells per axis a node touches (0: no window)
 };
 
 template <typename T>

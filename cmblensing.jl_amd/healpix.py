@@ -2,11 +2,16 @@
 `HealpixField` / `HealpixMap`, `Projector` and `project`.
 
 A HEALPix field is a tensor (B, P, npix) == Julia (npix, npol) plus the batch axis, RING ordering, P = 1 (I), 2 (QU) or 3 (IQU).  Pixel
-indices are 0-based here (the reference's k - 1).  `project` covers both directions of `method="bilinear"` for `ProjLambert` (with its
-`rotator`) and `ProjEquiRect`; the geometry is computed on the device in double whatever the precision of the projection.
+indices are 0-based here (the reference's k - 1).  `project` covers both directions of `method="bilinear"` and of `method="nfft"` for
+`ProjLambert` (with its `rotator`) and `ProjEquiRect`; the geometry is computed on the device in double whatever the precision of the
+projection (DESIGN.md).
 
-NOT here (README "HEALPix projection", out of scope): `method="fft"` (a non-uniform FFT, src/proj_healpix.jl:229-236, 314-325), NEST
-ordering, the AD rules, lensing of HEALPix fields."""
+`method="nfft"` is the reference's `method = :fft` (a non-uniform FFT, src/proj_healpix.jl:229-236, 314-325): trigonometric interpolation
+of the band-limited patch at the HEALPix centres one way and its transpose the other way (DESIGN.md 4.8 has the definition).  The spelling
+`"fft"` itself still raises NotImplementedError, with its message unchanged: existing tests pin that, and making it an alias of "nfft" is
+left to a change that may touch them.
+
+NOT here (README "HEALPix projection", out of scope): NEST ordering, the AD rules, lensing of HEALPix fields."""
 import ctypes
 
 import numpy as np
@@ -135,24 +140,30 @@ def HealpixMap(arr):
     return HealpixField(ProjHealpix(npix2nside(n)), arr, "I")
 
 
+_METHODS = {"bilinear": 0, "nfft": 1}          # CMBL_PROJECT_BILINEAR, CMBL_PROJECT_NFFT
+
+
 def _method(method):
+    """the method's number in the C ABI; "fft" (the reference's name of "nfft") is refused as before, see the module docstring"""
     if method == "fft":
         raise NotImplementedError('project(method="fft") needs a non-uniform FFT (src/proj_healpix.jl:229-236, 314-325) and is out of scope, like NEST '
                                   'ordering, the AD rules and lensing of HEALPix fields (README, "HEALPix projection": out)')
-    if method != "bilinear":
-        raise ValueError(f'method must be "bilinear" (or "fft", not implemented), got {method!r}')
+    if method not in _METHODS:
+        raise ValueError(f'method must be "bilinear" or "nfft" (or "fft", not implemented under that name), got {method!r}')
+    return _METHODS[method]
 
 
 class Projector(_Handle):
     """`Projector(hpx_proj => cart_proj; method)` (:254-306): what both directions of `project` precompute, on the device.  Either order of
-    the two projections.  Host readbacks (float64 / int64 NumPy, cached): `thetas`, `phis`, `psi_cart` (Ny Nx, Ny fastest: the reference's
-    θs, ϕs, ψpol_θϕs), `hpx_idxs_in_patch`, and for the touched pixels (0 < i < Ny+1, 0 < j < Nx+1) `touched`, `is_`, `js`, `psi_hpx`."""
+    the two projections.  `method`: "bilinear" or "nfft" (the reference's :fft; even Ny, Nx up to 2048 and a patch that holds at least one
+    HEALPix centre); `window_width` is the number of fine-grid cells per axis a node touches (0 for "bilinear").  Host readbacks (float64 /
+    int64 NumPy, cached): `thetas`, `phis`, `psi_cart` (Ny Nx, Ny fastest: the reference's θs, ϕs, ψpol_θϕs), `hpx_idxs_in_patch`, and for the touched pixels (0 < i < Ny+1, 0 < j < Nx+1) `touched`, `is_`, `js`, `psi_hpx`."""
     _destroy = "cmbl_projector_destroy"
 
     def __init__(self, hpx_proj, cart_proj, method="bilinear"):
         if isinstance(cart_proj, ProjHealpix):
             hpx_proj, cart_proj = cart_proj, hpx_proj
-        _method(method)
+        code = _method(method)
         if not isinstance(hpx_proj, ProjHealpix) or not isinstance(cart_proj, (ProjLambert, ProjEquiRect)):
             raise TypeError("Projector: a ProjHealpix and a ProjLambert or ProjEquiRect are needed")
         self.hpx_proj, self.cart_proj, self.method = hpx_proj, cart_proj, method
@@ -160,8 +171,14 @@ class Projector(_Handle):
             kind, params = 1, list(cart_proj.theta_span) + list(cart_proj.phi_span)
         else:
             kind, params = 0, list(cart_proj.rotator)
-        self._open(cart_proj.lib, "cmbl_projector_create", cart_proj._h, hpx_proj.Nside, kind, (ctypes.c_double * len(params))(*params))
+        self._open(cart_proj.lib, "cmbl_projector_create_method", cart_proj._h, hpx_proj.Nside, kind, (ctypes.c_double * len(params))(*params), code)
         self._info = {}
+
+    @property
+    def window_width(self):
+        m, w = ctypes.c_int(), ctypes.c_int()
+        check(self.lib.cmbl_projector_method(self._h, ctypes.byref(m), ctypes.byref(w)))
+        return w.value
 
     def _get(self, which, n):
         if which not in self._info:
@@ -211,7 +228,7 @@ def project(field, target_proj, method="bilinear", projector=None):
     """`project(healpix_field => cart_proj)` and `project(cart_field => ProjHealpix(Nside))` (src/proj_healpix.jl:164-219, 300-302): a
     HealpixField lands on `target_proj` (ProjLambert or ProjEquiRect) as a MAP Field / EquiRectField; a Field or EquiRectField lands on the
     sphere as a HealpixField, exactly 0 outside the patch.  QU and IQU fields have their polarisation rotated into the local basis.
-    `projector`: a cached `Projector` of the same pair."""
+    `method`: "bilinear" or "nfft" (module docstring).  `projector`: a cached `Projector` of the same pair and the same method."""
     _method(method)
     to_cart = isinstance(field, HealpixField)
     if to_cart == isinstance(target_proj, ProjHealpix):
@@ -221,4 +238,6 @@ def project(field, target_proj, method="bilinear", projector=None):
         projector = Projector(hpx, cart, method)
     elif projector.hpx_proj != hpx or (projector.cart_proj is not cart and projector.cart_proj != cart):
         raise ValueError("project: the projector was built for another pair of projections")           # the @assert of :222, 309
+    elif projector.method != method:
+        raise ValueError(f"project: the projector was built for method {projector.method!r}, not {method!r}")   # Projector{method} (:221, 229)
     return projector.to_cart(field) if to_cart else projector.to_healpix(field)

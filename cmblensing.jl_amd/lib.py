@@ -96,7 +96,9 @@ SIGNATURES = {
     "cmbl_equirect_beam_pol": [_vp, _vp, _pd, _vp],
     "cmbl_healpix_pix2ang_host": [_ci, _l, _l, _pd, _pd],
     "cmbl_projector_create": [_vp, _ci, _ci, _pd, _pvp],
+    "cmbl_projector_create_method": [_vp, _ci, _ci, _pd, _ci, _pvp],
     "cmbl_projector_destroy": [_vp],
+    "cmbl_projector_method": [_vp, _pci, _pci],
     "cmbl_projector_info_host": [_vp, _ci, _pd, _sz],
     "cmbl_project_to_cart": [_vp, _vp, _vp, _ci, _ci],
     "cmbl_project_to_healpix": [_vp, _ci, _vp, _vp, _ci, _ci],

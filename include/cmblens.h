@@ -470,13 +470,26 @@ int cmbl_quadratic_estimate(cmbl_dataset* ds, int which, const double* Cf_host, 
  *      arrays of the context's dtype, npix = 12 Nside^2 fastest: the reference's (npix, npol) plus the batch axis.  npol = 1 (I), 2 (QU),
  *      3 (IQU); QU are rotated by the angle psi between the two coordinate bases ("polarization flattening", :238-252, 327-341).
  *      ALL geometry is double on the device whatever the context's dtype (the reference computes it in T); values, weights and
- *      cos 2 psi / sin 2 psi are of the context's dtype.  NOT here: method = :fft (a non-uniform FFT), NEST ordering, the AD rules.
+ *      cos 2 psi / sin 2 psi are of the context's dtype.  NOT here: NEST ordering, the AD rules.
+ *
+ *      The METHOD belongs to the projector (the reference's Projector{method}); cmbl_project_to_cart / _to_healpix dispatch on it.
+ *      CMBL_PROJECT_BILINEAR is described below.  CMBL_PROJECT_NFFT is method = :fft (:229-236, 314-325), a non-uniform FFT: with
+ *      I_N = {-N/2 ... N/2-1}, K(x) = sum_{l in I_Ny x I_Nx} cos 2 pi l.x, grid nodes x_g = ((i - Ny/2 - 1)/Ny, (j - Nx/2 - 1)/Nx) and the same
+ *      formula at the fractional (i_p, j_p) of the Npatch pixels of hpx_idxs_in_patch,
+ *        project_to_healpix  h_p = 1/(Ny Nx) sum_g m_g K(x_g - x_p) on the patch, exactly 0 elsewhere,
+ *        project_to_cart     m_g = 1/Npatch sum_p h_p K(x_p - x_g),
+ *      transposes of each other up to Ny Nx / Npatch, with the same QU rotations as the bilinear method.  Computed through an oversampled
+ *      grid (sigma = 2) and a window of cmbl_projector_method's `window_width` cells per axis (8 in float32, 14 in float64), to the rounding
+ *      floor of the dtype; bit-identical between runs.  Ny, Nx must be even, hold one window on the fine grid (2N >= width)
+ *      and be at most 2048, else CMBL_ERR_SHAPE; a patch without a HEALPix pixel centre is CMBL_ERR_ARG.
  *
  * healpix_pix2ang_host: pix2angRing of the pixels first ... first + n - 1 (host, double, no device).
  * projector_create: Projector(ProjHealpix(nside) => cart_proj) (:254-294) for the Cartesian projection of `ctx` (its Ny, Nx).  cart_kind
  *   CMBL_PROJ_LAMBERT: params = rotator[3] in degrees (RotZYX, the reference's default is (0, 90, 0)), pixel size the context's;
  *   CMBL_PROJ_EQUIRECT: params = theta_span[2], phi_span[2] in radians.  Nside: a power of two in 1 ... 8192, else CMBL_ERR_SHAPE.  A
  *   Cartesian pixel whose colatitude is outside [0, pi] is CMBL_ERR_ARG (healpy.get_interp_val refuses it).  Synchronises.
+ * projector_create_method: the same with the method named; projector_create means CMBL_PROJECT_BILINEAR.  Another method number is CMBL_ERR_ARG.
+ * projector_method: the projector's method and the window width in use (0 for CMBL_PROJECT_BILINEAR).
  * projector_info_host: doubles.  CMBL_PROJ_COUNTS: n = 2, {pixels in the patch, touched pixels}.  _THETA, _PHI, _PSI_CART: n = Ny Nx, at
  *   the Cartesian pixel centres, Ny fastest.  _IDX_IN_PATCH: hpx_idxs_in_patch (1 <= i <= Ny, 1 <= j <= Nx, :270), ascending.  _IDX_TOUCHED,
  *   _I, _J, _PSI_HPX: the pixels with 0 < i < Ny+1, 0 < j < Nx+1 (every other pixel of a projection to the sphere is exactly 0), ascending,
@@ -486,11 +499,14 @@ int cmbl_quadratic_estimate(cmbl_dataset* ds, int which, const double* Cf_host, 
  *   Images.bilinear_interpolation, a corner outside the map counts as zero.  Neither call synchronises. */
 typedef struct cmbl_projector cmbl_projector;
 enum { CMBL_PROJ_LAMBERT = 0, CMBL_PROJ_EQUIRECT = 1 };
+enum { CMBL_PROJECT_BILINEAR = 0, CMBL_PROJECT_NFFT = 1 };
 enum { CMBL_PROJ_COUNTS = 0, CMBL_PROJ_THETA = 1, CMBL_PROJ_PHI = 2, CMBL_PROJ_PSI_CART = 3, CMBL_PROJ_IDX_IN_PATCH = 4, CMBL_PROJ_IDX_TOUCHED = 5,
        CMBL_PROJ_I = 6, CMBL_PROJ_J = 7, CMBL_PROJ_PSI_HPX = 8 };
 int cmbl_healpix_pix2ang_host(int nside, long first, long n, double* theta, double* phi);
 int cmbl_projector_create(cmbl_ctx* ctx, int nside, int cart_kind, const double* params, cmbl_projector** out);
+int cmbl_projector_create_method(cmbl_ctx* ctx, int nside, int cart_kind, const double* params, int method, cmbl_projector** out);
 int cmbl_projector_destroy(cmbl_projector* P);
+int cmbl_projector_method(cmbl_projector* P, int* method, int* window_width);
 int cmbl_projector_info_host(cmbl_projector* P, int which, double* out_host, size_t n);
 int cmbl_project_to_cart(cmbl_projector* P, const void* hpx, void* map_out, int npol, int nbatch);
 int cmbl_project_to_healpix(cmbl_projector* P, int basis_in, const void* in, void* hpx_out, int npol, int nbatch);

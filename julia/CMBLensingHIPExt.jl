@@ -710,30 +710,39 @@ function equirect_beam(pol::Symbol, Cov::ROCBlockDiag{CMBLensing.AzFourier})
     CMBLensing.BlockDiagEquiRect{CMBLensing.QUAzFourier}(out, proj)
 end
 
-# ---- HEALPix <-> Cartesian projection (src/proj_healpix.jl), method = :bilinear, for a device-backed Cartesian side: the Projector (:254-294) is
+# ---- HEALPix <-> Cartesian projection (src/proj_healpix.jl), method = :bilinear and :fft, for a device-backed Cartesian side: the Projector (:254-294) is
 # `cmbl_projector_create` -- pix2angRing, θϕ_to_ij / ij_to_θϕ, get_ψpol and the ring lookup of healpy.get_interp_val on the device, in double whatever
 # T -- and each direction of `project` one gather kernel with the QU rotation fused in (`cmbl_project_to_cart`, `cmbl_project_to_healpix`): no
 # healpy, no Images.jl, nothing through the host.  The library counts pixels from 0 and stores a HEALPix field as (npix, npol, nbatch).
-# `method = :fft` keeps the reference's NFFT methods.  (Unexecuted, like the rest of this file: there is no Julia on the build machines.)
+# `method = :fft` is the library's CMBL_PROJECT_NFFT (`cmbl_projector_create_method`): the sums NFFT.jl's plans approximate, through an oversampled
+# grid and a window to the rounding floor of T (DESIGN 4.8), so neither NFFT.jl nor CuNFFT.jl is needed; even Ny, Nx up to 2048.  The method
+# belongs to the projector, as in the reference.  (Unexecuted, like the rest of this file: there is no Julia on the build machines.)
+projector_method(method::Symbol) = method == :bilinear ? Cint(0) : method == :fft ? Cint(1) : error("method = :$method: :bilinear or :fft")   # CMBL_PROJECT_*
 mutable struct HIPProjector
     h         :: Ptr{Cvoid}
     cart_proj
     hpx_proj  :: CMBLensing.ProjHealpix
-    function HIPProjector(h, cart_proj, hpx_proj)
-        P = new(h, cart_proj, hpx_proj)
+    method    :: Symbol
+    function HIPProjector(h, cart_proj, hpx_proj, method)
+        P = new(h, cart_proj, hpx_proj, method)
         finalizer(P -> ccall((:cmbl_projector_destroy, lib), Cint, (Ptr{Cvoid},), P.h), P)
     end
 end
 projector_params(proj::ProjLambert) = (Cint(0), Cdouble[proj.rotator...])                                       # CMBL_PROJ_LAMBERT
 projector_params(proj::CMBLensing.ProjEquiRect) = (Cint(1), Cdouble[proj.θspan..., proj.φspan...])              # CMBL_PROJ_EQUIRECT
-function HIPProjector((hpx_proj, cart_proj)::Pair{<:CMBLensing.ProjHealpix,<:CMBLensing.CartesianProj})         # :254-294
+function HIPProjector((hpx_proj, cart_proj)::Pair{<:CMBLensing.ProjHealpix,<:CMBLensing.CartesianProj}; method::Symbol=:bilinear)   # :254-294
     kind, params = projector_params(cart_proj)
     h = Ref{Ptr{Cvoid}}()
-    GC.@preserve params chk(ccall((:cmbl_projector_create, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Ptr{Cvoid}}),
-                                  hip_ctx(cart_proj).h, hpx_proj.Nside, kind, params, h))
-    HIPProjector(h[], cart_proj, hpx_proj)
+    GC.@preserve params chk(ccall((:cmbl_projector_create_method, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Ptr{Cvoid}}),
+                                  hip_ctx(cart_proj).h, hpx_proj.Nside, kind, params, projector_method(method), h))
+    HIPProjector(h[], cart_proj, hpx_proj, method)
 end
-HIPProjector((cart_proj, hpx_proj)::Pair{<:CMBLensing.CartesianProj,<:CMBLensing.ProjHealpix}) = HIPProjector(hpx_proj => cart_proj)   # :304-306
+HIPProjector((cart_proj, hpx_proj)::Pair{<:CMBLensing.CartesianProj,<:CMBLensing.ProjHealpix}; method::Symbol=:bilinear) = HIPProjector(hpx_proj => cart_proj; method)   # :304-306
+function projector_window_width(P::HIPProjector)                                                                  # cells per axis a node touches; 0 for :bilinear
+    m, w = Ref{Cint}(), Ref{Cint}()
+    chk(ccall((:cmbl_projector_method, lib), Cint, (Ptr{Cvoid}, Ptr{Cint}, Ptr{Cint}), P.h, m, w))
+    Int(w[])
+end
 function projector_info(P::HIPProjector, which::Integer, n::Integer)
     out = Vector{Cdouble}(undef, n)
     chk(ccall((:cmbl_projector_info_host, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Csize_t), P.h, which, out, n))
@@ -762,13 +771,11 @@ function CMBLensing.project(P::HIPProjector, (cart_field, hpx_proj)::Pair{<:Base
     npol == 1 ? CMBLensing.HealpixMap(vec(out), hpx_proj) : npol == 2 ? CMBLensing.HealpixQUMap(out, hpx_proj) : CMBLensing.HealpixIQUMap(out, hpx_proj)
 end
 function CMBLensing.project((cart_field, hpx_proj)::Pair{<:BaseField{B,<:CMBLensing.CartesianProj,<:Any,<:ROCArray},<:CMBLensing.ProjHealpix}; method::Symbol=:bilinear) where {B}
-    method == :bilinear || return CMBLensing.project(CMBLensing.Projector(cart_field.proj => hpx_proj; method), cart_field => hpx_proj)
-    CMBLensing.project(HIPProjector(hpx_proj => cart_field.proj), cart_field => hpx_proj)
+    CMBLensing.project(HIPProjector(hpx_proj => cart_field.proj; method), cart_field => hpx_proj)
 end
 # sphere -> patch: the target decides; a projection whose `storage` is a ROCArray gets the device path
 function CMBLensing.project((hpx_map, cart_proj)::Pair{<:CMBLensing.HealpixField,<:CMBLensing.CartesianProj}, ::Type{<:ROCArray}; method::Symbol=:bilinear)
-    method == :bilinear || error("method = :$method is not implemented on the device; use the reference's project")
-    CMBLensing.project(HIPProjector(hpx_map.proj => cart_proj), hpx_map => cart_proj)
+    CMBLensing.project(HIPProjector(hpx_map.proj => cart_proj; method), hpx_map => cart_proj)
 end
 
 # device RNG for `simulate` / `randn!` (src/specialops.jl:6, src/base_fields.jl:169-170): counter-based Philox4x32-10
