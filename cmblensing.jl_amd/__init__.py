@@ -9,7 +9,7 @@ from .lib import load_library, library_path, CmblError, build            # noqa:
 from .engine import (ProjLambert, LenseFlow, BilinearLens, PowerLens, Taylens, antilensing, BaseDataSet, Field, MAP, FOURIER, HARMONIC,   # noqa: F401
                      FLOW_FWD, FLOW_INV, FLOW_ADJ, FLOW_INVADJ, reference_exact, ud_grade, pixwin, UD_MAP, UD_FOURIER,
                      get_Cl, get_Dl, get_l4Cl, get_rhol, cov_to_Cl, make_mask)
-from .equirect import (ProjEquiRect, EquiRectField, BlockDiagEquiRect, AZFOURIER, Cl_to_Beam, simulate, equirect_geometry,   # noqa: F401
+from .equirect import (ProjEquiRect, EquiRectField, BlockDiagEquiRect, AZFOURIER, Cl_to_Beam, Cl_to_Cov, simulate, equirect_geometry,   # noqa: F401
                        blocks_from_ref, blocks_to_ref)
 from .healpix import (ProjHealpix, HealpixField, HealpixMap, Projector, project, pix2ang_ring, npix2nside)   # noqa: F401
 from .sim import (Cls, load_sim, noise_cls, beam_cls, lowpass, cl_to_2d, HarmOp, border_mask)   # noqa: F401

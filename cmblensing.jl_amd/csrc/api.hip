@@ -592,6 +592,23 @@ int cmbl_equirect_beam_pol(cmbl_ctx* ctx, const void* blocksI_real, const double
     BY_DTYPE(ctx, do_eq_beam_pol, ctx, blocksI_real, omega_host, out_complex);
   });
 }
+// Cℓ_to_Cov(:I / :P) (:430-503): the covariance of the AzFourier / QUAzFourier coefficients of an isotropic field, in double, rounded at the store
+int cmbl_equirect_cov(cmbl_ctx* ctx, const double* theta_span, const double* phi_span, int pol, int lmax, const double* cl_a, const double* cl_b,
+                      int ngrid, void* blocks_out) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(theta_span); NOTNULL(phi_span); NOTNULL(cl_a); NOTNULL(blocks_out);
+    CMBL_REQUIRE(pol == 0 || pol == 2, ERR_ARG, "equirect_cov: pol is 0 (I) or 2 (P)");
+    CMBL_REQUIRE(pol == 0 || cl_b != nullptr, ERR_ARG, "equirect_cov: P needs the EE and the BB spectrum");
+    CMBL_REQUIRE(theta_span[0] != theta_span[1] && phi_span[0] != phi_span[1], ERR_ARG, "equirect_cov: an empty span");
+    CMBL_REQUIRE(equirect_span_K(phi_span) >= 1, ERR_SHAPE, "equirect_cov: the azimuthal span must be 2 pi / K for an integer K (no block-diagonal covariance otherwise)");
+    CMBL_REQUIRE(pol == 0 || ctx->p->Nx % 2 == 0, ERR_SHAPE, "equirect_cov: QUAzFourier needs an even Nx");
+    CMBL_REQUIRE(lmax >= (pol == 0 ? 0 : 2) && lmax <= 100000, ERR_SHAPE, "equirect_cov: lmax must be at least 0 (I) or 2 (P) and at most 100000 (the integer recurrence coefficients stay exact in double)");
+    CMBL_REQUIRE(ngrid == 0 || (ngrid >= 4 && ngrid <= (1 << 24)), ERR_SHAPE, "equirect_cov: ngrid is 0 (exact mode) or at least 4 (the interpolation stencil)");
+    for (int l = 0; l <= lmax; ++l)
+      CMBL_REQUIRE(std::isfinite(cl_a[l]) && (pol == 0 || std::isfinite(cl_b[l])), ERR_NAN, "equirect_cov: a spectrum value is not finite");
+    BY_DTYPE(ctx, do_eq_cov, ctx, theta_span, phi_span, pol, lmax, cl_a, cl_b, ngrid, blocks_out);
+  });
+}
 
 // ---- HEALPix <-> Cartesian projection (src/proj_healpix.jl) ------------------------------------------------------------------
 int cmbl_healpix_pix2ang_host(int nside, long first, long n, double* theta, double* phi) {

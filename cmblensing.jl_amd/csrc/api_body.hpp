@@ -233,5 +233,6 @@ template <typename T> void do_eq_matmul(cmbl_ctx* ctx, const void* A, bool adjA,
 template <typename T> void do_eq_dot(cmbl_ctx* ctx, const void* A, const void* Bm, bool cplx, int n, double* out) { equirect_block_dot<T>(C<T>(ctx), A, Bm, cplx, n, out); }
 template <typename T> void do_eq_scale_columns(cmbl_ctx* ctx, void* blocks, bool cplx, int n, const double* w) { equirect_scale_columns<T>(C<T>(ctx), blocks, cplx, n, w); }
 template <typename T> void do_eq_beam_pol(cmbl_ctx* ctx, const void* blocksI, const double* omega, void* out) { equirect_beam_pol<T>(C<T>(ctx), blocksI, omega, out); }
+template <typename T> void do_eq_cov(cmbl_ctx* ctx, const double* tspan, const double* pspan, int pol, int lmax, const double* cl_a, const double* cl_b, int ngrid, void* blocks) { equirect_cov<T>(C<T>(ctx), tspan, pspan, pol, lmax, cl_a, cl_b, ngrid, blocks); }
 
 }  // namespace cmbl

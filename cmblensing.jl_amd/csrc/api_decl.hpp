@@ -24,6 +24,7 @@
 #include "engine_powerlens.hpp"
 #include "engine_mask.hpp"
 #include "engine_equirect.hpp"
+#include "engine_equirect_cov.hpp"
 #include "engine_healpix.hpp"
 #include "engine_nfft.hpp"
 #include "../../include/cmblens.h"
@@ -74,6 +75,7 @@ namespace cmbl {
   X(T, do_eq_dot, (cmbl_ctx* ctx, const void* A, const void* Bm, bool cplx, int n, double* out)) \
   X(T, do_eq_scale_columns, (cmbl_ctx* ctx, void* blocks, bool cplx, int n, const double* w)) \
   X(T, do_eq_beam_pol, (cmbl_ctx* ctx, const void* blocksI, const double* omega, void* out)) \
+  X(T, do_eq_cov, (cmbl_ctx* ctx, const double* tspan, const double* pspan, int pol, int lmax, const double* cl_a, const double* cl_b, int ngrid, void* blocks)) \
   X(T, do_projector_create, (cmbl_projector* h, int nside, int kind, const double* params, int method))
 
 #define CMBL_API_DECLARE(T, name, params) template <typename T> void name params;

@@ -8,8 +8,8 @@ complex == Julia (n, Nx÷2+1, B) with n = Ny (I) or 2 Ny (QU); operator blocks (
 On the device: the four transforms, `M * f`, `M' * f`, the three operator products, `dot(M1', M2)` and the beams.  On the host, once per
 operator, in float64 and batched over m (numpy.linalg): `sqrt` (SVD, :313-323), `pinv`, `logabsdet` / `logdet`, `solve` (`\\`) and `rdiv`
 (`/`) of two operators, and `+`, `-`, scalar `*`, `/` (torch, elementwise).  `sqrt` / `pinv` / `logabsdet` are cached on the object like the
-reference's `Ref`s.  NOT here: `Cℓ_to_Cov` (defined through CirculantCov.jl only, :430-503) -- blocks come from the caller; the AD rules;
-lensing on this projection."""
+reference's `Ref`s.  `Cl_to_Cov` (:430-503) builds the isotropic covariance blocks on the device, in double, from their definition (the reference
+delegates to CirculantCov.jl, whose own numbers are not compared here).  NOT here: the AD rules; lensing on this projection."""
 import ctypes
 
 import numpy as np
@@ -314,9 +314,45 @@ class BlockDiagEquiRect:
         return (self if self.complex or not o.complex else o)._from_host(r)
 
 
-def Cl_to_Beam(pol, cov_I_blocks, proj):
-    """Cℓ_to_Beam(:I / :P) (src/proj_equirect.jl:505-533) from the real blocks of Cℓ_to_Cov(:I) (which the caller supplies; the reference makes
-    them through CirculantCov.jl): `"I"`: blocks[j, k, m] * Ω[k]; `"P"`: [B 0; 0 B] * diag(Ω, Ω), complex 2Ny blocks."""
+def _cl_array(Cl, lmax):
+    """nan2zero.(C(0:ℓmax)) of a `Cls`-like callable (anything with `ell` and `__call__`), or an array over ℓ = 0, 1, ...; ℓmax clamped to what it holds"""
+    if callable(Cl) and hasattr(Cl, "ell"):
+        lmax = min(int(lmax), int(np.floor(np.max(Cl.ell))))
+        a = np.asarray(Cl(np.arange(lmax + 1)), dtype=np.float64)
+    else:
+        a = np.asarray(Cl, dtype=np.float64).ravel()
+        lmax = min(int(lmax), a.size - 1)
+        a = a[:lmax + 1]
+    return np.ascontiguousarray(np.where(np.isnan(a), 0.0, a)), lmax
+
+
+def Cl_to_Cov(pol, proj, Cl, Cl_BB=None, units=1, lmax=10_000, ngrid=50_000):
+    """Cℓ_to_Cov(:I, proj, CI) / Cℓ_to_Cov(:P, proj, CEE, CBB) (src/proj_equirect.jl:436-501): the `BlockDiagEquiRect` covariance of an isotropic
+    Gaussian field with the given spectra (`Cls` objects, or arrays over ℓ = 0, 1, ...), built on the device in double and rounded to the
+    projection's precision at the store.  `ngrid`: nodes of the correlation-function table on [0, π] (the reference's CirculantCov uses 50 000);
+    0 evaluates the recurrences at every separation (exact, slow at large sizes).  The azimuthal span must be 2π/K.  `units` is accepted and
+    unused, as in the reference's body."""
+    if pol not in ("I", "P"):
+        raise ValueError("Cl_to_Cov: pol is 'I' or 'P'")
+    if (pol == "P") != (Cl_BB is not None):
+        raise ValueError("Cl_to_Cov: 'I' takes one spectrum, 'P' the EE and the BB spectrum")
+    a, la = _cl_array(Cl, lmax)
+    b, lb = _cl_array(Cl_BB, lmax) if pol == "P" else (None, la)
+    l = min(la, lb)
+    n = proj.Ny if pol == "I" else 2 * proj.Ny
+    out = torch.empty((proj.Mh, n, n), dtype=proj.T if pol == "I" else proj.CT, device=proj.device)
+    ts, ps = (np.array(s, dtype=np.float64) for s in (proj.theta_span, proj.phi_span))
+    p = lambda x: x.ctypes.data_as(_PD)
+    check(proj.lib.cmbl_equirect_cov(proj._h, p(ts), p(ps), 0 if pol == "I" else 2, l, p(a), p(b) if b is not None else None, int(ngrid), _ptr(out)))
+    return BlockDiagEquiRect(out, proj)
+
+
+def Cl_to_Beam(pol, cov_I_blocks, proj, lmax=10_000, ngrid=50_000):
+    """Cℓ_to_Beam(:I / :P) (src/proj_equirect.jl:505-533) from the real blocks of Cℓ_to_Cov(:I) -- a `BlockDiagEquiRect`, a block array, or the
+    spectrum itself (a `Cls` or an array over ℓ, as in the reference; the covariance is then built here with `lmax`, `ngrid`): `"I"`:
+    blocks[j, k, m] * Ω[k]; `"P"`: [B 0; 0 B] * diag(Ω, Ω), complex 2Ny blocks."""
+    if (callable(cov_I_blocks) and hasattr(cov_I_blocks, "ell")) or (not isinstance(cov_I_blocks, BlockDiagEquiRect) and np.ndim(cov_I_blocks) == 1):
+        cov_I_blocks = Cl_to_Cov("I", proj, cov_I_blocks, lmax=lmax, ngrid=ngrid)
     M = cov_I_blocks if isinstance(cov_I_blocks, BlockDiagEquiRect) else BlockDiagEquiRect(cov_I_blocks, proj)
     _same_proj(M.proj, proj)
     if M.complex or M.n != proj.Ny:

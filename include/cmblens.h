@@ -114,6 +114,8 @@ int cmbl_ctx_geometry_host(cmbl_ctx* ctx, int which, double* out_host, size_t n)
  *                                                                   the half plane resident in LDS (csrc/kernels_small.hpp): 0 = off, 1 = up to 64 x 64 pixels (faster at every
  *                                                                   batch size), 2 = wherever compiled (up to 128 x 128 in single, 64 x 64 in double precision).  Results agree
  *                                                                   with the staged path to rounding, not bit for bit (tests/test_gpu_small.py)
+ *        "eq_cov_scratch_mb"     CMBL_EQ_COV_SCRATCH_MB (256)      cmbl_equirect_cov: cap in MiB of the scratch of one slab of ring pairs (at least one pair per slab);
+ *                                                                   changes no result (tests/test_gpu_equirect_cov.py)
  *      (the launch-geometry and prefetch switches change no result at all: tests/test_gpu_boundary.py, tests/test_gpu_fullsize.py)
  *      Unknown names return CMBL_ERR_ARG.  The reference has no counterpart (its switches are Julia keyword arguments). */
 int cmbl_ctx_set_option(cmbl_ctx* ctx, const char* name, int value);
@@ -341,8 +343,8 @@ int cmbl_make_mask(cmbl_ctx* ctx, const int32_t* src_yx_host, int nsrc, int pad,
  *      Arrays are the reference's, column-major: maps (Ny, Nx, npol, nbatch) with θ contiguous; AzFourier fields (n, Nx/2+1, nbatch) complex with
  *      n = Ny (I) or 2 Ny (QU); operators `blocks` (n, n, Nx/2+1), row index contiguous, real (blocks_complex = 0) or complex elements of the
  *      context's precision.  The context supplies Ny, Nx, precision, stream and scratch; its pixel size is not used.  Nothing is accumulated with
- *      atomics, results are bit-identical between runs.  NOT included: Cℓ_to_Cov (:430-503, defined through CirculantCov.jl only: blocks come from
- *      the caller), the AD rules (:242-248, 349-351), IQUAzFourier (an alias without a transform), lensing on this projection.
+ *      atomics, results are bit-identical between runs.  NOT included: the AD rules (:242-248, 349-351), IQUAzFourier (an alias without a
+ *      transform), lensing on this projection.
  *   cmbl_equirect_geometry_host: ProjEquiRect(; Ny, Nx, θspan, φspan) (:71-81, 112-120) on the host in double, no context and no device needed.  The
  *      spans are sorted.  theta_edges = range(θspan, Ny+1) (Ny+1 values), theta = its midpoints (Ny); phi_edges (Nx+1) and phi (Nx) = rem2pi(·, RoundDown)
  *      of the equispaced edges and midpoints, in [0, 2π); omega[j] = rem2pi(phi_edges[1] − phi_edges[0]) (cos θedges[j] − cos θedges[j+1]) (Ny);
@@ -364,7 +366,19 @@ int cmbl_make_mask(cmbl_ctx* ctx, const int32_t* src_yx_host, int nsrc, int pad,
  *   cmbl_equirect_block_scale_columns: blocks[j, k, m] *= w[k] in place, w rounded to the context's precision (Cℓ_to_Beam(:I), :505-515); nw != n
  *      is CMBL_ERR_SHAPE.
  *   cmbl_equirect_beam_pol: out (2Ny, 2Ny, Nx/2+1) complex = [B 0; 0 B] · diag(Ω, Ω) from the real blocks B (Ny, Ny, Nx/2+1) (Cℓ_to_Beam(:P), :517-533);
- *      omega_host: Ny doubles.  The two beam calls copy their weights to the device before they return (one blocking copy). */
+ *      omega_host: Ny doubles.  The two beam calls copy their weights to the device before they return (one blocking copy).
+ *   cmbl_equirect_cov: Cℓ_to_Cov(:I) (pol = 0) and Cℓ_to_Cov(:P) (pol = 2) (:430-503).  The reference delegates the arithmetic to CirculantCov.jl; here the
+ *      blocks are DEFINED as the covariance of the AzFourier / QUAzFourier coefficients of an isotropic Gaussian field with the given spectra (DESIGN
+ *      §4.7; P = Q + iU = -Σ (E + iB)ℓm ₂Yℓm with respect to (e_θ, e_φ)) on the geometry of cmbl_equirect_geometry_host(Ny, Nx, theta_span, phi_span)
+ *      -- the context holds the sizes, not the spans, hence the two span arguments.  The azimuthal span must be 2π/K for an integer K >= 1
+ *      (|K - round K| <= 1e-9 K), else CMBL_ERR_SHAPE: no other span has a block-diagonal covariance.  cl_a (TT, or EE) and cl_b (BB; NULL for pol = 0):
+ *      HOST arrays of lmax + 1 doubles, C_ℓ at ℓ = 0 ... lmax (the caller interpolates and sets NaN to 0 like nan2zero.(C(ℓ)); a value that is not
+ *      finite is CMBL_ERR_NAN).  blocks_out: DEVICE array (Nx/2+1) n n of the context's precision indexed [m][q][p] like every operator here, real
+ *      n = Ny (pol 0) or complex n = 2 Ny (pol 2: [j, k] = γ_m, [j, k+Ny] = ξ_m, [j+Ny, k] = conj ξ_J(m), [j+Ny, k+Ny] = conj γ_J(m), :488-494).
+ *      ngrid = 0: the correlation functions by their three-term recurrences at every separation (exact mode); ngrid >= 4: from a table on ngrid
+ *      uniform nodes of [0, π] by 4-point Lagrange interpolation (the reference's CirculantCov uses a spline on 50 000 nodes); 1 ... 3:
+ *      CMBL_ERR_SHAPE.  Odd Nx or lmax < 2 with pol = 2, lmax > 100000: CMBL_ERR_SHAPE.  All arithmetic is double in either precision; only the store rounds.
+ *      Bit-identical between runs and for every "eq_cov_scratch_mb".  Synchronises the context's stream. */
 int cmbl_equirect_geometry_host(int Ny, int Nx, const double* theta_span, const double* phi_span, double* theta, double* phi,
                                 double* theta_edges, double* phi_edges, double* omega, double* lx);
 int cmbl_equirect_convert(cmbl_ctx* ctx, int basis_in, const void* in, int basis_out, void* out, int npol, int nbatch);
@@ -373,6 +387,8 @@ int cmbl_equirect_block_matmul(cmbl_ctx* ctx, const void* A, int adjA, const voi
 int cmbl_equirect_block_dot(cmbl_ctx* ctx, const void* A, const void* B, int blocks_complex, int n, double* out_host);
 int cmbl_equirect_block_scale_columns(cmbl_ctx* ctx, void* blocks, int blocks_complex, int n, const double* w_host, int nw);
 int cmbl_equirect_beam_pol(cmbl_ctx* ctx, const void* blocksI_real, const double* omega_host, void* out_complex);
+int cmbl_equirect_cov(cmbl_ctx* ctx, const double* theta_span, const double* phi_span, int pol, int lmax, const double* cl_a, const double* cl_b,
+                      int ngrid, void* blocks_out);
 
 /* ---- small helpers used by the drivers above the hot kernels
  * axpby: out = a[b]*x + b[b]*y per batch slot (y may be NULL) -- the FieldTuple / Field broadcasts of the CG, line-search
