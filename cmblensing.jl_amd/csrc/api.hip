@@ -609,6 +609,36 @@ int cmbl_equirect_cov(cmbl_ctx* ctx, const double* theta_span, const double* phi
     BY_DTYPE(ctx, do_eq_cov, ctx, theta_span, phi_span, pol, lmax, cl_a, cl_b, ngrid, blocks_out);
   });
 }
+// sqrt / pinv / singular values (:313-323), log|det| (:342-347) and the solves (:274-282) of the blocks, factorised on the device in double
+#define EQ_FACTOR_N_OK(n) CMBL_REQUIRE((n) <= 2048, ERR_SHAPE, "equirect: the device factorisations take blocks of n <= 2048")
+int cmbl_equirect_block_svd(cmbl_ctx* ctx, const void* blocks, int blocks_complex, int n, double rtol, void* out_sqrt, void* out_pinv, double* sv_host, int* sweeps_host) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(blocks);
+    EQ_N_OK(ctx, n); EQ_FACTOR_N_OK(n);
+    CMBL_REQUIRE(rtol >= 0.0 && std::isfinite(rtol), ERR_ARG, "equirect_block_svd: rtol must be finite and not negative");
+    CMBL_REQUIRE(out_sqrt != blocks && out_pinv != blocks && (out_sqrt == nullptr || out_sqrt != out_pinv), ERR_ARG, "equirect_block_svd: an output must not alias the input or the other output");
+    BY_DTYPE(ctx, do_eq_svd, ctx, blocks, blocks_complex != 0, n, rtol, out_sqrt, out_pinv, sv_host, sweeps_host);
+  });
+}
+int cmbl_equirect_block_logabsdet(cmbl_ctx* ctx, const void* blocks, int blocks_complex, int n, double* out_host) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(blocks); NOTNULL(out_host);
+    EQ_N_OK(ctx, n); EQ_FACTOR_N_OK(n);
+    BY_DTYPE(ctx, do_eq_logabsdet, ctx, blocks, blocks_complex != 0, n, out_host);
+  });
+}
+int cmbl_equirect_block_solve(cmbl_ctx* ctx, const void* A, int a_complex, int n, int side, const void* rhs, int rhs_complex, int rhs_kind, void* out, int B) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(A); NOTNULL(rhs); NOTNULL(out);
+    EQ_N_OK(ctx, n); EQ_FACTOR_N_OK(n);
+    CMBL_REQUIRE(side == CMBL_SIDE_LEFT || side == CMBL_SIDE_RIGHT, ERR_ARG, "equirect_block_solve: side is CMBL_SIDE_LEFT or CMBL_SIDE_RIGHT");
+    CMBL_REQUIRE(rhs_kind == CMBL_RHS_BLOCKS || rhs_kind == CMBL_RHS_FIELD, ERR_ARG, "equirect_block_solve: rhs_kind is CMBL_RHS_BLOCKS or CMBL_RHS_FIELD");
+    CMBL_REQUIRE(rhs_kind == CMBL_RHS_BLOCKS || (side == CMBL_SIDE_LEFT && rhs_complex != 0), ERR_ARG, "equirect_block_solve: a field is complex and is solved from the left");
+    CMBL_REQUIRE(rhs_kind == CMBL_RHS_BLOCKS || (B >= 1 && B <= 65535), ERR_SHAPE, "equirect_block_solve: nbatch must lie in [1, 65535]");
+    CMBL_REQUIRE(out != A && out != rhs, ERR_ARG, "equirect_block_solve: out must not alias an input");
+    BY_DTYPE(ctx, do_eq_solve, ctx, A, a_complex != 0, n, side, rhs, rhs_complex != 0, rhs_kind, out, B);
+  });
+}
 
 // ---- HEALPix <-> Cartesian projection (src/proj_healpix.jl) ------------------------------------------------------------------
 int cmbl_healpix_pix2ang_host(int nside, long first, long n, double* theta, double* phi) {

@@ -233,6 +233,9 @@ template <typename T> void do_eq_matmul(cmbl_ctx* ctx, const void* A, bool adjA,
 template <typename T> void do_eq_dot(cmbl_ctx* ctx, const void* A, const void* Bm, bool cplx, int n, double* out) { equirect_block_dot<T>(C<T>(ctx), A, Bm, cplx, n, out); }
 template <typename T> void do_eq_scale_columns(cmbl_ctx* ctx, void* blocks, bool cplx, int n, const double* w) { equirect_scale_columns<T>(C<T>(ctx), blocks, cplx, n, w); }
 template <typename T> void do_eq_beam_pol(cmbl_ctx* ctx, const void* blocksI, const double* omega, void* out) { equirect_beam_pol<T>(C<T>(ctx), blocksI, omega, out); }
+template <typename T> void do_eq_svd(cmbl_ctx* ctx, const void* blocks, bool cplx, int n, double rtol, void* out_sqrt, void* out_pinv, double* sv, int* sweeps) { equirect_block_svd<T>(C<T>(ctx), blocks, cplx, n, rtol, out_sqrt, out_pinv, sv, sweeps); }
+template <typename T> void do_eq_logabsdet(cmbl_ctx* ctx, const void* blocks, bool cplx, int n, double* out) { equirect_block_logabsdet<T>(C<T>(ctx), blocks, cplx, n, out); }
+template <typename T> void do_eq_solve(cmbl_ctx* ctx, const void* A, bool acplx, int n, int side, const void* rhs, bool rcplx, int kind, void* out, int B) { equirect_block_solve<T>(C<T>(ctx), A, acplx, n, side, rhs, rcplx, kind, out, B); }
 template <typename T> void do_eq_cov(cmbl_ctx* ctx, const double* tspan, const double* pspan, int pol, int lmax, const double* cl_a, const double* cl_b, int ngrid, void* blocks) { equirect_cov<T>(C<T>(ctx), tspan, pspan, pol, lmax, cl_a, cl_b, ngrid, blocks); }
 
 }  // namespace cmbl

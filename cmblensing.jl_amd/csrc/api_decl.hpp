@@ -25,6 +25,7 @@
 #include "engine_mask.hpp"
 #include "engine_equirect.hpp"
 #include "engine_equirect_cov.hpp"
+#include "engine_equirect_factor.hpp"
 #include "engine_healpix.hpp"
 #include "engine_nfft.hpp"
 #include "../../include/cmblens.h"
@@ -76,6 +77,9 @@ namespace cmbl {
   X(T, do_eq_scale_columns, (cmbl_ctx* ctx, void* blocks, bool cplx, int n, const double* w)) \
   X(T, do_eq_beam_pol, (cmbl_ctx* ctx, const void* blocksI, const double* omega, void* out)) \
   X(T, do_eq_cov, (cmbl_ctx* ctx, const double* tspan, const double* pspan, int pol, int lmax, const double* cl_a, const double* cl_b, int ngrid, void* blocks)) \
+  X(T, do_eq_svd, (cmbl_ctx* ctx, const void* blocks, bool cplx, int n, double rtol, void* out_sqrt, void* out_pinv, double* sv, int* sweeps)) \
+  X(T, do_eq_logabsdet, (cmbl_ctx* ctx, const void* blocks, bool cplx, int n, double* out)) \
+  X(T, do_eq_solve, (cmbl_ctx* ctx, const void* A, bool acplx, int n, int side, const void* rhs, bool rcplx, int kind, void* out, int B)) \
   X(T, do_projector_create, (cmbl_projector* h, int nside, int kind, const double* params, int method))
 
 #define CMBL_API_DECLARE(T, name, params) template <typename T> void name params;

@@ -36,11 +36,11 @@ inline void raise_lds_limit(const void* fn, size_t bytes) {
 }
 // kernel classes for the optional per-launch event timing (cmbl_prof_*)
 enum KernelId { K_LAYOUT = 0, K_Y_R2C, K_Y_C2R, K_X_FFT, K_X_GRAD, K_FLOW_Y, K_ADJ_Y, K_ADJ_X, K_DELTA_Y, K_DELTA_ROWS, K_DPHI_Y, K_DPHI_X,
-                K_GRADHESS, K_HARM, K_LINCOMB, K_MASK, K_REDUCE, K_GEN_DFT, K_GEN_POINT, K_CG, K_XPW, K_PWFLAT, K_UD, K_CL, K_BL, K_PL, K_EDT, K_MASK_GAUSS, K_MASK_POINT, K_EQ_APPLY, K_EQ_MATMUL, K_EQ_POINT, K_EQ_COV, K_HPX_BUILD, K_HPX_PROJECT, K_NFFT_SPREAD, K_NFFT_INTERP, K_NFFT_MODES, K_COUNT };
+                K_GRADHESS, K_HARM, K_LINCOMB, K_MASK, K_REDUCE, K_GEN_DFT, K_GEN_POINT, K_CG, K_XPW, K_PWFLAT, K_UD, K_CL, K_BL, K_PL, K_EDT, K_MASK_GAUSS, K_MASK_POINT, K_EQ_APPLY, K_EQ_MATMUL, K_EQ_POINT, K_EQ_COV, K_HPX_BUILD, K_HPX_PROJECT, K_NFFT_SPREAD, K_NFFT_INTERP, K_NFFT_MODES, K_EQ_FACTOR, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"layout", "y_r2c", "y_c2r", "x_fft", "x_grad", "flow_y_fwd", "adj_y", "adj_x", "delta_cols", "delta_rows",
                                                   "dphi_reduce", "dphi_combine", "gradhess_mult", "harm_apply", "lincomb", "mask_mul", "reduce",
                                                   "generic_dft", "generic_pointwise", "cg_update", "x_harm", "harm_dot", "ud_grade", "get_cl", "bilinear", "powerlens", "edt", "mask_gauss", "make_mask",
-                                                  "equirect_apply", "equirect_matmul", "equirect_pointwise", "equirect_cov", "healpix_build", "healpix_project", "nfft_spread", "nfft_interp", "nfft_modes"};
+                                                  "equirect_apply", "equirect_matmul", "equirect_pointwise", "equirect_cov", "healpix_build", "healpix_project", "nfft_spread", "nfft_interp", "nfft_modes", "equirect_factor"};
 
 // With profiling on, the launch goes through hipExtLaunchKernelGGL, whose start / stop events carry the kernel's OWN begin and end
 // timestamps (what rocprofv3's kernel trace reports); an event pair recorded around a plain launch also brackets its dispatch (+2 us).
@@ -113,6 +113,7 @@ struct CtxBase {
     int row_fill_target = env_int("CMBL_ROW_FILL_TARGET", 0);
     int small_flow = env_int("CMBL_SMALL_FLOW", 1);                       // small maps: a whole flow as ONE launch, one workgroup per slice (kernels_small.hpp): 0 off, 1 up to 64 x 64, 2 wherever compiled (128 x 128)
     int eq_cov_scratch_mb = env_int("CMBL_EQ_COV_SCRATCH_MB", 256);         // Cℓ_to_Cov on ProjEquiRect: cap of the scratch of one slab of ring pairs (engine_equirect_cov.hpp); 0: one pair per slab
+    int eq_factor_scratch_mb = env_int("CMBL_EQ_FACTOR_SCRATCH_MB", 8192);  // sqrt / pinv / logabsdet / solves of BlockDiagEquiRect: cap of the double working copies of one slab of blocks (engine_equirect_factor.hpp); 0: one block per slab
   } opts;
   int* opt_ptr(const std::string& k) {
     if (k == "slice_streams") return &opts.slice_streams;
@@ -137,6 +138,7 @@ struct CtxBase {
     if (k == "row_fill_target") return &opts.row_fill_target;
     if (k == "small_flow") return &opts.small_flow;
     if (k == "eq_cov_scratch_mb") return &opts.eq_cov_scratch_mb;
+    if (k == "eq_factor_scratch_mb") return &opts.eq_factor_scratch_mb;
     return nullptr;
   }
   double theta = 0;

@@ -5,10 +5,11 @@ Tensor layouts are the reference's arrays read row-major: maps (B, P, Nx, Ny) re
 complex == Julia (n, Nx÷2+1, B) with n = Ny (I) or 2 Ny (QU); operator blocks (Nx//2+1, n, n) indexed [m, q, p] == Julia blocks[p, q, m].
 `blocks_from_ref` / `blocks_to_ref` move between that and NumPy arrays indexed [p, q, m] like the reference's.
 
-On the device: the four transforms, `M * f`, `M' * f`, the three operator products, `dot(M1', M2)` and the beams.  On the host, once per
-operator, in float64 and batched over m (numpy.linalg): `sqrt` (SVD, :313-323), `pinv`, `logabsdet` / `logdet`, `solve` (`\\`) and `rdiv`
-(`/`) of two operators, and `+`, `-`, scalar `*`, `/` (torch, elementwise).  `sqrt` / `pinv` / `logabsdet` are cached on the object like the
-reference's `Ref`s.  `Cl_to_Cov` (:430-503) builds the isotropic covariance blocks on the device, in double, from their definition (the reference
+On the device: the four transforms, `M * f`, `M' * f`, the three operator products, `dot(M1', M2)` and the beams.  `sqrt` (SVD, :313-323),
+`pinv`, `logabsdet` / `logdet`, `solve` (`\\`) and `rdiv` (`/`) run once per operator either on the host, in float64 and batched over m
+(numpy.linalg; `factor_on="host"`, the default), or on the device (`factor_on="device"`, or `on="device"` for one call: a batched one-sided
+Jacobi SVD and a batched LU, one workgroup per block, arithmetic in double, blocks up to n = 2048).  `+`, `-`, scalar `*`, `/` are torch,
+elementwise.  `sqrt` / `pinv` / `logabsdet` are cached on the object per path, like the reference's `Ref`s.  `Cl_to_Cov` (:430-503) builds the isotropic covariance blocks on the device, in double, from their definition (the reference
 delegates to CirculantCov.jl, whose own numbers are not compared here).  NOT here: the AD rules; lensing on this projection."""
 import ctypes
 
@@ -19,6 +20,9 @@ from .lib import load_library, check
 from .engine import ProjLambert, MAP, _ptr
 
 AZFOURIER = 3
+SIDE_LEFT, SIDE_RIGHT = 0, 1                   # CMBL_SIDE_* of cmbl_equirect_block_solve
+DEVICE_FACTOR_NMAX = 2048                      # largest block the device factorisations take
+PINV_RTOL = 1e-15                              # numpy.linalg.pinv's default cut
 _PD = ctypes.POINTER(ctypes.c_double)
 
 
@@ -182,15 +186,18 @@ class BlockDiagEquiRect:
     (QUAzFourier), real or complex.  `blocks`: device tensor or array (Nx//2+1, n, n) indexed [m, q, p] (`blocks_from_ref` converts the
     reference's [p, q, m])."""
 
-    def __init__(self, blocks, proj, basis=AZFOURIER):
+    def __init__(self, blocks, proj, basis=AZFOURIER, factor_on="host"):
         if basis != AZFOURIER:
             raise ValueError("BlockDiagEquiRect: the basis is AZFOURIER")
+        if factor_on not in ("host", "device"):
+            raise ValueError("BlockDiagEquiRect: factor_on is 'host' or 'device'")
+        self.factor_on = factor_on
         t = proj.tensor(blocks)
         if t.dim() != 3 or t.shape[0] != proj.Mh or t.shape[1] != t.shape[2] or t.shape[1] not in (proj.Ny, 2 * proj.Ny):
             raise ValueError(f"BlockDiagEquiRect: blocks of shape {tuple(t.shape)}, expected ({proj.Mh}, n, n) with n = Ny or 2 Ny")
         self.proj, self.basis, self.blocks = proj, basis, t.contiguous()
         self.n, self.complex = int(t.shape[1]), bool(t.is_complex())
-        self._sqrt = self._pinv = self._logabsdet = None
+        self._sqrt, self._pinv, self._logabsdet = {}, {}, {}              # caches, keyed by the path ("host" / "device"; pinv: and rtol)
 
     # ---- device products
     def _apply(self, f, adjoint):
@@ -262,10 +269,20 @@ class BlockDiagEquiRect:
         w = np.ascontiguousarray(w, dtype=np.float64)
         p = self.proj
         check(p.lib.cmbl_equirect_block_scale_columns(p._h, _ptr(self.blocks), int(self.complex), self.n, w.ctypes.data_as(_PD), w.size))
-        self._sqrt = self._pinv = self._logabsdet = None
+        self._sqrt, self._pinv, self._logabsdet = {}, {}, {}
         return self
 
-    # ---- host linear algebra, once per operator, float64, batched over m
+    # ---- factorisations, once per operator and path: on the host (numpy.linalg, float64, batched over m) or on the device (one workgroup per
+    #      block, arithmetic in double, cmbl_equirect_block_svd / _logabsdet / _solve); `on` overrides `factor_on` for one call
+    def _on(self, on):
+        on = self.factor_on if on is None else on
+        if on not in ("host", "device"):
+            raise ValueError(f"BlockDiagEquiRect: the factorisations run on 'host' or 'device', not {on!r}")
+        if on == "device" and self.n > DEVICE_FACTOR_NMAX:
+            raise ValueError(f"BlockDiagEquiRect: the device factorisations take blocks up to n = {DEVICE_FACTOR_NMAX}, these have n = {self.n}: "
+                             "the host path remains (on='host')")
+        return on
+
     def _host(self):
         a = self.blocks.detach().cpu().numpy().transpose(0, 2, 1)            # [m, p, q]
         return a.astype(np.complex128 if self.complex else np.float64)
@@ -274,44 +291,97 @@ class BlockDiagEquiRect:
         a = np.ascontiguousarray(np.transpose(a, (0, 2, 1)))
         if not self.complex:
             a = a.real
-        return BlockDiagEquiRect(self.proj.tensor(a), self.proj)
+        return BlockDiagEquiRect(self.proj.tensor(a), self.proj, factor_on=self.factor_on)
 
-    def sqrt(self):
+    def _device_svd(self, rtol, want_sqrt, want_pinv, want_sv=False):
+        """one Jacobi SVD of every block on the device: (sqrt or None, pinv or None, singular values (Mh, n) descending or None)"""
+        p = self.proj
+        new = lambda: BlockDiagEquiRect(torch.empty_like(self.blocks), p, factor_on=self.factor_on)
+        sq, pi = (new() if want_sqrt else None), (new() if want_pinv else None)
+        sv = np.empty((p.Mh, self.n)) if want_sv else None
+        check(p.lib.cmbl_equirect_block_svd(p._h, _ptr(self.blocks), int(self.complex), self.n, float(rtol), _ptr(sq.blocks) if sq else None,
+                                            _ptr(pi.blocks) if pi else None, sv.ctypes.data_as(_PD) if want_sv else None, None))
+        return sq, pi, sv
+
+    def sqrt(self, on=None):
         """U * Diagonal(sqrt.(S)) * V' of the SVD of every block (src/proj_equirect.jl:313-323)"""
-        if self._sqrt is None:
-            u, s, vh = np.linalg.svd(self._host())
-            self._sqrt = self._from_host((u * np.sqrt(s)[:, None, :]) @ vh)
-        return self._sqrt
+        on = self._on(on)
+        if on not in self._sqrt:
+            if on == "host":
+                u, s, vh = np.linalg.svd(self._host())
+                self._sqrt[on] = self._from_host((u * np.sqrt(s)[:, None, :]) @ vh)
+            else:
+                self._sqrt[on] = self._device_svd(PINV_RTOL, True, False)[0]
+        return self._sqrt[on]
 
-    def pinv(self):
-        if self._pinv is None:
-            self._pinv = self._from_host(np.linalg.pinv(self._host()))
-        return self._pinv
+    def pinv(self, rtol=None, on=None):
+        """the pseudo-inverse of every block; singular values at or below rtol * the block's largest are dropped (default 1e-15, numpy.linalg.pinv's)"""
+        on = self._on(on)
+        rtol = PINV_RTOL if rtol is None else float(rtol)
+        if (on, rtol) not in self._pinv:
+            self._pinv[(on, rtol)] = self._from_host(np.linalg.pinv(self._host(), rcond=rtol)) if on == "host" else self._device_svd(rtol, False, True)[1]
+        return self._pinv[(on, rtol)]
 
-    def logabsdet(self):
+    def svdvals(self, on=None):
+        """the singular values of every block, descending: NumPy array (Mh, n) of doubles"""
+        if self._on(on) == "host":
+            return np.linalg.svd(self._host(), compute_uv=False)
+        return self._device_svd(PINV_RTOL, False, False, True)[2]
+
+    def logabsdet(self, on=None):
         """(Σ log|det|, Π sign) over the blocks (src/proj_equirect.jl:342-347)"""
-        if self._logabsdet is None:
-            sign, lad = np.linalg.slogdet(self._host())
-            self._logabsdet = (float(lad.sum()), complex(np.prod(sign)))
-        return self._logabsdet
+        on = self._on(on)
+        if on not in self._logabsdet:
+            if on == "host":
+                sign, lad = np.linalg.slogdet(self._host())
+                self._logabsdet[on] = (float(lad.sum()), complex(np.prod(sign)))
+            else:
+                out = (ctypes.c_double * 3)()
+                p = self.proj
+                check(p.lib.cmbl_equirect_block_logabsdet(p._h, _ptr(self.blocks), int(self.complex), self.n, out))
+                self._logabsdet[on] = (float(out[0]), complex(out[1], out[2]))
+        return self._logabsdet[on]
 
-    def logdet(self):
-        l, s = self.logabsdet()
+    def logdet(self, on=None):
+        l, s = self.logabsdet(on)
         v = l + np.log(s)
         return float(v.real) if abs(v.imag) < 1e-12 else v
 
-    def solve(self, o):
-        """M₁ \\ M₂, blockwise (src/proj_equirect.jl:274-282)"""
-        _same_proj(self.proj, o.proj)
-        r = np.linalg.solve(self._host(), o._host())
-        return (self if self.complex or not o.complex else o)._from_host(r)
+    def _device_solve(self, side, rhs, rhs_complex, field, B=1):
+        p = self.proj
+        out = torch.empty(rhs.shape, dtype=p.CT if (self.complex or rhs_complex) else p.T, device=p.device)
+        check(p.lib.cmbl_equirect_block_solve(p._h, _ptr(self.blocks), int(self.complex), self.n, side, _ptr(rhs), int(rhs_complex), int(field), _ptr(out), int(B)))
+        return out
 
-    def rdiv(self, o):
+    def solve(self, o, on=None):
+        """M₁ \\ M₂, blockwise (src/proj_equirect.jl:274-282), or M \\ f for a field (the reference's mapblocks(\\, M, f)): an `EquiRectField`"""
+        _same_proj(self.proj, o.proj)
+        on = self._on(on)
+        if isinstance(o, EquiRectField):
+            f = o.to(AZFOURIER)
+            if f.arr.shape[2] != self.n:
+                raise ValueError(f"operator blocks of size {self.n} on a field with {f.arr.shape[2]} rows")
+            if on == "host":
+                x = np.linalg.solve(self._host()[None], f.arr.detach().cpu().numpy().astype(np.complex128)[..., None])[..., 0]
+                return EquiRectField(self.proj, self.proj.tensor(x.astype(np.complex64 if self.proj.T == torch.float32 else np.complex128)), AZFOURIER)
+            return EquiRectField(self.proj, self._device_solve(SIDE_LEFT, f.arr, True, True, f.B), AZFOURIER)
+        if o.n != self.n:
+            raise ValueError("operators of different block sizes")
+        if on == "host":
+            r = np.linalg.solve(self._host(), o._host())
+            return (self if self.complex or not o.complex else o)._from_host(r)
+        return BlockDiagEquiRect(self._device_solve(SIDE_LEFT, o.blocks, o.complex, False), self.proj, factor_on=self.factor_on)
+
+    def rdiv(self, o, on=None):
         """M₁ / M₂ = M₁ M₂⁻¹, blockwise"""
         _same_proj(self.proj, o.proj)
-        a, b = self._host(), o._host()
-        r = np.conj(np.transpose(np.linalg.solve(np.conj(np.transpose(b, (0, 2, 1))), np.conj(np.transpose(a, (0, 2, 1)))), (0, 2, 1)))
-        return (self if self.complex or not o.complex else o)._from_host(r)
+        if self._on(on) == "host":
+            a, b = self._host(), o._host()
+            r = np.conj(np.transpose(np.linalg.solve(np.conj(np.transpose(b, (0, 2, 1))), np.conj(np.transpose(a, (0, 2, 1)))), (0, 2, 1)))
+            return (self if self.complex or not o.complex else o)._from_host(r)
+        if o.n != self.n:
+            raise ValueError("operators of different block sizes")
+        return BlockDiagEquiRect(o._device_solve(SIDE_RIGHT, self.blocks, self.complex, False), self.proj, factor_on=self.factor_on)
 
 
 def _cl_array(Cl, lmax):

@@ -94,6 +94,9 @@ SIGNATURES = {
     "cmbl_equirect_block_dot": [_vp, _vp, _vp, _ci, _ci, _pd],
     "cmbl_equirect_block_scale_columns": [_vp, _vp, _ci, _ci, _pd, _ci],
     "cmbl_equirect_beam_pol": [_vp, _vp, _pd, _vp],
+    "cmbl_equirect_block_svd": [_vp, _vp, _ci, _ci, _cd, _vp, _vp, _pd, _pci],
+    "cmbl_equirect_block_logabsdet": [_vp, _vp, _ci, _ci, _pd],
+    "cmbl_equirect_block_solve": [_vp, _vp, _ci, _ci, _ci, _vp, _ci, _ci, _vp, _ci],
     "cmbl_equirect_cov": [_vp, _pd, _pd, _ci, _ci, _pd, _pd, _ci, _vp],
     "cmbl_healpix_pix2ang_host": [_ci, _l, _l, _pd, _pd],
     "cmbl_projector_create": [_vp, _ci, _ci, _pd, _pvp],

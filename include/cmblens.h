@@ -116,6 +116,8 @@ int cmbl_ctx_geometry_host(cmbl_ctx* ctx, int which, double* out_host, size_t n)
  *                                                                   with the staged path to rounding, not bit for bit (tests/test_gpu_small.py)
  *        "eq_cov_scratch_mb"     CMBL_EQ_COV_SCRATCH_MB (256)      cmbl_equirect_cov: cap in MiB of the scratch of one slab of ring pairs (at least one pair per slab);
  *                                                                   changes no result (tests/test_gpu_equirect_cov.py)
+ *        "eq_factor_scratch_mb"  CMBL_EQ_FACTOR_SCRATCH_MB (8192)  cmbl_equirect_block_svd / _logabsdet / _solve: cap in MiB of the double working copies of one slab of
+ *                                                                   blocks (at least one block per slab); changes no result (tests/test_gpu_equirect_factor.py)
  *      (the launch-geometry and prefetch switches change no result at all: tests/test_gpu_boundary.py, tests/test_gpu_fullsize.py)
  *      Unknown names return CMBL_ERR_ARG.  The reference has no counterpart (its switches are Julia keyword arguments). */
 int cmbl_ctx_set_option(cmbl_ctx* ctx, const char* name, int value);
@@ -378,7 +380,26 @@ int cmbl_make_mask(cmbl_ctx* ctx, const int32_t* src_yx_host, int nsrc, int pad,
  *      ngrid = 0: the correlation functions by their three-term recurrences at every separation (exact mode); ngrid >= 4: from a table on ngrid
  *      uniform nodes of [0, π] by 4-point Lagrange interpolation (the reference's CirculantCov uses a spline on 50 000 nodes); 1 ... 3:
  *      CMBL_ERR_SHAPE.  Odd Nx or lmax < 2 with pol = 2, lmax > 100000: CMBL_ERR_SHAPE.  All arithmetic is double in either precision; only the store rounds.
- *      Bit-identical between runs and for every "eq_cov_scratch_mb".  Synchronises the context's stream. */
+ *      Bit-identical between runs and for every "eq_cov_scratch_mb".  Synchronises the context's stream.
+ *   The three factorisation calls below (sqrt, pinv, logabsdet, \ and / of BlockDiagEquiRect, :274-282, 313-347) share these rules: one workgroup
+ *      factorises one block, synchronising by the workgroup barrier alone, every loop bounded at launch; ALL arithmetic is double (real or complex) in
+ *      either precision and only the final store rounds to the block type; the double working copies go through slabs of "eq_factor_scratch_mb";
+ *      results are bit-identical between runs and for every slab size.  n must be Ny or 2 Ny and at most 2048 (CMBL_ERR_SHAPE, checked before
+ *      anything is allocated); an input element that is not finite is CMBL_ERR_NAN, before anything is factorised; an output aliasing an input is
+ *      CMBL_ERR_ARG.  Each call synchronises the context's stream.
+ *   cmbl_equirect_block_svd: one-sided Jacobi SVD of every block (Hestenes: G = A, V = I, column pairs in a round-robin order rotated while
+ *      |g_i' g_j| > n 2^-53 |g_i| |g_j|; a pair whose columns both lie at or below n 2^-53 |A|_F, one of whose columns lies at or below 2^-106 |A|_F, or with an exactly zero norm or product, is
+ *      skipped), until a sweep rotates nothing or 60 sweeps -- then CMBL_ERR_STATE, the message names the block.  σ_k = |g_k|.  out_sqrt (may be
+ *      NULL) = U √S V' = G diag(σ^-1/2) V' with the term dropped where σ_k = 0 exactly and no other cut-off (:313-323); out_pinv (may be NULL) =
+ *      V diag(σ^-2) G' with the term dropped where σ_k <= rtol max σ.  sv_host (may be NULL): (Nx/2+1) n doubles, the singular values of every block
+ *      in descending order; sweeps_host (may be NULL): Nx/2+1 ints, the sweeps each block took.  rtol negative or not finite: CMBL_ERR_ARG.
+ *   cmbl_equirect_block_logabsdet: LU with partial pivoting (largest modulus, a tie to the lowest row) of every block; out_host = (Σ log|u_kk|,
+ *      Re s, Im s), s = Π u_kk / |u_kk| times the permutation parities, summed on the host in double in the order (m, k) (:342-347).  An exactly
+ *      zero pivot gives (-inf, 0, 0) like slogdet and is no error.
+ *   cmbl_equirect_block_solve: side = CMBL_SIDE_LEFT: out = A \ rhs; CMBL_SIDE_RIGHT: out = rhs / A (the left solve with A' on the
+ *      conjugate-transposed right-hand sides).  rhs_kind = CMBL_RHS_BLOCKS: rhs and out are block arrays like A (M₁ \ M₂, M₁ / M₂, :274-282; nbatch
+ *      is ignored); CMBL_RHS_FIELD: AzFourier fields (n, Nx/2+1, nbatch), complex, left side only (M \ f).  a_complex / rhs_complex give the two
+ *      element types; out is complex when either is.  An exactly zero pivot is CMBL_ERR_NAN and the message names the block. */
 int cmbl_equirect_geometry_host(int Ny, int Nx, const double* theta_span, const double* phi_span, double* theta, double* phi,
                                 double* theta_edges, double* phi_edges, double* omega, double* lx);
 int cmbl_equirect_convert(cmbl_ctx* ctx, int basis_in, const void* in, int basis_out, void* out, int npol, int nbatch);
@@ -387,6 +408,13 @@ int cmbl_equirect_block_matmul(cmbl_ctx* ctx, const void* A, int adjA, const voi
 int cmbl_equirect_block_dot(cmbl_ctx* ctx, const void* A, const void* B, int blocks_complex, int n, double* out_host);
 int cmbl_equirect_block_scale_columns(cmbl_ctx* ctx, void* blocks, int blocks_complex, int n, const double* w_host, int nw);
 int cmbl_equirect_beam_pol(cmbl_ctx* ctx, const void* blocksI_real, const double* omega_host, void* out_complex);
+enum { CMBL_SIDE_LEFT = 0, CMBL_SIDE_RIGHT = 1 };
+enum { CMBL_RHS_BLOCKS = 0, CMBL_RHS_FIELD = 1 };
+int cmbl_equirect_block_svd(cmbl_ctx* ctx, const void* blocks, int blocks_complex, int n, double rtol, void* out_sqrt, void* out_pinv,
+                            double* sv_host, int* sweeps_host);
+int cmbl_equirect_block_logabsdet(cmbl_ctx* ctx, const void* blocks, int blocks_complex, int n, double* out_host);
+int cmbl_equirect_block_solve(cmbl_ctx* ctx, const void* A, int a_complex, int n, int side, const void* rhs, int rhs_complex, int rhs_kind,
+                              void* out, int nbatch);
 int cmbl_equirect_cov(cmbl_ctx* ctx, const double* theta_span, const double* phi_span, int pol, int lmax, const double* cl_a, const double* cl_b,
                       int ngrid, void* blocks_out);
 

@@ -634,8 +634,9 @@ CMBLensing.make_mask(f::BaseField{B,<:ProjLambert,<:Any,<:ROCArray}; kwargs...) 
 # ---- ProjEquiRect (src/proj_equirect.jl) for device-backed fields and operators: the azimuthal transforms (:149-178), `M*f`, `M'*f` (:230-240), the three
 # operator products (:254-269, on the matrix cores), `dot(M₁', M₂)` (:358-360) and the beams (:505-533) are one `cmbl_equirect_*` call each
 # (include/cmblens.h has the semantics, the two quirks included: QU needs an even Nx, and QUMap's second assignment wins at columns 0 and Nx÷2).
-# `sqrt`, `pinv`, `logabsdet`, `\`, `/`, `+`, `-` keep the reference's own methods (one-off setup through AMDGPU.jl's LinearAlgebra and broadcasts), and
-# so does `Cℓ_to_Cov` (CirculantCov.jl on the host, then `gpu`).
+# `sqrt`, `pinv` (:313-333), `logabsdet` (:342-347), `\` and `/` of two operators (:274-282) and `M \ f` factorise the blocks on the device, one workgroup per
+# block, in double (`cmbl_equirect_block_svd`, `_logabsdet`, `_solve`; blocks up to n = 2048, larger ones keep the reference's methods), with the reference's
+# caches.  `+`, `-` keep the reference's own methods (AMDGPU.jl's broadcasts), and so does `Cℓ_to_Cov` (CirculantCov.jl on the host, then `gpu`).
 const AZFOURIER = Cint(3)                                                    # CMBL_AZFOURIER
 eq_nbatch(a, nd) = ndims(a) > nd ? size(a, nd + 1) : 1
 function CMBLensing.AzFourier(f::BaseField{Map,<:CMBLensing.ProjEquiRect,<:Any,<:ROCArray})                     # :149-152
@@ -692,6 +693,74 @@ function LinearAlgebra.dot(M₁::Adjoint{<:Any,<:ROCBlockDiag{B}}, M₂::ROCBloc
     GC.@preserve a b out chk(ccall((:cmbl_equirect_block_dot, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}),
                                    hip_ctx(M₂.proj).h, devptr(a), devptr(b), E <: Complex, size(a, 1), out))
     E <: Complex ? E(complex(out[1], out[2])) : E(out[1])
+end
+# sqrt, pinv (:313-333): one Jacobi SVD of every block; pinv cuts at the reference's n eps(T) (LinearAlgebra.pinv's default rtol)
+const EQ_FACTOR_NMAX = 2048
+function equirect_svd!(M::ROCBlockDiag, out_sqrt, out_pinv)
+    blocks = M.blocks
+    n = size(blocks, 1)
+    rtol = Cdouble(n * eps(real(eltype(blocks))))
+    GC.@preserve blocks out_sqrt out_pinv chk(ccall((:cmbl_equirect_block_svd, lib), Cint,
+                                                    (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cint}),
+                                                    hip_ctx(M.proj).h, devptr(blocks), eltype(blocks) <: Complex, n, rtol,
+                                                    out_sqrt === nothing ? C_NULL : devptr(out_sqrt), out_pinv === nothing ? C_NULL : devptr(out_pinv), C_NULL, C_NULL))
+end
+function LinearAlgebra.sqrt(M::ROCBlockDiag{B}) where {B<:CMBLensing.AzBasis}
+    size(M.blocks, 1) > EQ_FACTOR_NMAX && return invoke(LinearAlgebra.sqrt, Tuple{CMBLensing.BlockDiagEquiRect{B}}, M)
+    if !isassigned(M.blocks_sqrt)
+        out = similar(M.blocks)
+        equirect_svd!(M, out, nothing)
+        M.blocks_sqrt[] = out
+    end
+    CMBLensing.BlockDiagEquiRect{B}(M.blocks_sqrt[], M.proj)
+end
+function LinearAlgebra.pinv(M::ROCBlockDiag{B}) where {B<:CMBLensing.AzBasis}
+    size(M.blocks, 1) > EQ_FACTOR_NMAX && return invoke(LinearAlgebra.pinv, Tuple{CMBLensing.BlockDiagEquiRect{B}}, M)
+    if !isassigned(M.blocks_pinv)
+        out = similar(M.blocks)
+        equirect_svd!(M, nothing, out)
+        M.blocks_pinv[] = out
+    end
+    CMBLensing.BlockDiagEquiRect{B}(M.blocks_pinv[], M.proj)
+end
+function LinearAlgebra.logabsdet(M::ROCBlockDiag{B,T}) where {B<:CMBLensing.AzBasis,T}                                                                          # :342-347
+    size(M.blocks, 1) > EQ_FACTOR_NMAX && return invoke(LinearAlgebra.logabsdet, Tuple{CMBLensing.BlockDiagEquiRect{B}}, M)
+    if M.logabsdet[] == (0, 0)
+        blocks = M.blocks
+        out = zeros(Cdouble, 3)
+        GC.@preserve blocks out chk(ccall((:cmbl_equirect_block_logabsdet, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}),
+                                          hip_ctx(M.proj).h, devptr(blocks), eltype(blocks) <: Complex, size(blocks, 1), out))
+        M.logabsdet[] = (T(out[1]), Complex{T}(out[2], out[3]))
+    end
+    M.logabsdet[]
+end
+# M₁ \ M₂ (side 0, CMBL_SIDE_LEFT) and M₁ / M₂ (side 1, CMBL_SIDE_RIGHT: the matrix that is inverted is M₂) (:274-282); rhs_kind 0 = CMBL_RHS_BLOCKS
+function equirect_solve(A::ROCBlockDiag{B}, side::Integer, R::ROCBlockDiag{B}) where {B}
+    a, r = A.blocks, R.blocks
+    out = similar(r, promote_type(eltype(a), eltype(r)))
+    GC.@preserve a r out chk(ccall((:cmbl_equirect_block_solve, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cvoid}, Cint, Cint, Ptr{Cvoid}, Cint),
+                                   hip_ctx(A.proj).h, devptr(a), eltype(a) <: Complex, size(a, 1), side, devptr(r), eltype(r) <: Complex, 0, devptr(out), 1))
+    CMBLensing.BlockDiagEquiRect{B}(out, A.proj)
+end
+function Base.:\(M₁::ROCBlockDiag{B}, M₂::ROCBlockDiag{B}) where {B<:CMBLensing.AzBasis}
+    size(M₁.blocks, 1) > EQ_FACTOR_NMAX && return invoke(\, Tuple{CMBLensing.BlockDiagEquiRect{B},CMBLensing.BlockDiagEquiRect{B}}, M₁, M₂)
+    CMBLensing.promote_metadata_strict(M₁.proj, M₂.proj)
+    equirect_solve(M₁, 0, M₂)
+end
+function Base.:/(M₁::ROCBlockDiag{B}, M₂::ROCBlockDiag{B}) where {B<:CMBLensing.AzBasis}
+    size(M₁.blocks, 1) > EQ_FACTOR_NMAX && return invoke(/, Tuple{CMBLensing.BlockDiagEquiRect{B},CMBLensing.BlockDiagEquiRect{B}}, M₁, M₂)
+    CMBLensing.promote_metadata_strict(M₁.proj, M₂.proj)
+    equirect_solve(M₂, 1, M₁)
+end
+# M \ f, the reference's mapblocks(\, M, f); rhs_kind 1 = CMBL_RHS_FIELD
+function Base.:\(M::ROCBlockDiag{B}, f::BaseField{B,<:CMBLensing.ProjEquiRect,<:Any,<:ROCArray}) where {B<:CMBLensing.AzBasis}
+    CMBLensing.promote_metadata_strict(M.proj, f.metadata)
+    blocks, a = M.blocks, f.arr
+    nb = eq_nbatch(a, 2)
+    out = similar(a)
+    GC.@preserve blocks a out chk(ccall((:cmbl_equirect_block_solve, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Cvoid}, Cint, Cint, Ptr{Cvoid}, Cint),
+                                        hip_ctx(M.proj).h, devptr(blocks), eltype(blocks) <: Complex, size(blocks, 1), 0, devptr(a), true, 1, devptr(out), nb))
+    typeof(f)(out, f.metadata)
 end
 # the Ω steps of Cℓ_to_Beam (:512, 524-530) on device-backed :I covariance blocks
 function equirect_beam(pol::Symbol, Cov::ROCBlockDiag{CMBLensing.AzFourier})
