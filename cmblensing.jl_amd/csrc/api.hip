@@ -26,6 +26,15 @@ static int guard(F&& f) {
 #define BASIS_OK(b) CMBL_REQUIRE((b) >= 0 && (b) <= 2, ERR_ARG, "bad basis: " #b)
 #define POLB_OK(P, B) CMBL_REQUIRE((P) >= 1 && (P) <= 3 && (B) >= 1, ERR_SHAPE, "npol must be 1..3 and nbatch >= 1")
 #define SAME_CTX(ds, L) CMBL_REQUIRE((ds)->ctx == (L)->ctx, ERR_ARG, "dataset and flow belong to different contexts")
+#define SAME_CTX_OP(ds, L) CMBL_REQUIRE((ds)->ctx == (L)->ctx, ERR_ARG, "the data set and the lensing operator belong to different contexts")
+
+// a typed, non-owning view of an operator handle (cmbl_lensop_from_*)
+template <typename H> static int lensop_view(H* L, int kind, cmbl_lensop** out) {
+  return guard([&] {
+    NOTNULL(L); NOTNULL(out);
+    *out = new cmbl_lensop{L->ctx, kind, L};
+  });
+}
 
 #ifdef CMBL_STAMPS
 #define CMBL_STAMPS_UNITS(X) X(main_f32) X(main_f64) X(gen_f32) X(gen_f64) X(small_f32) X(small_f64) X(cty_f32_a) X(cty_f32_b) X(cty_f64_a) X(cty_f64_b) \
@@ -312,6 +321,37 @@ int cmbl_wiener_cg(cmbl_dataset* ds, cmbl_flow* L, const void* d, const void* fs
     CMBL_REQUIRE(B >= 1 && maxit >= 1, ERR_ARG, "nbatch >= 1 and maxit >= 1");
     SAME_CTX(ds, L);
     BY_DTYPE(ds->ctx, do_cg, ds, L, d, fstart, tol, maxit, f_out, hist, nit, B);
+  });
+}
+
+// ---- any lensing operator in the L slot: typed, non-owning views of the operator handles ----
+int cmbl_lensop_from_lenseflow(cmbl_flow* L, cmbl_lensop** out) { return lensop_view(L, LENSOP_FLOW, out); }
+int cmbl_lensop_from_bilinear(cmbl_bilinear* L, cmbl_lensop** out) { return lensop_view(L, LENSOP_BILINEAR, out); }
+int cmbl_lensop_from_powerlens(cmbl_powerlens* L, cmbl_lensop** out) { return lensop_view(L, LENSOP_POWERLENS, out); }
+int cmbl_lensop_destroy(cmbl_lensop* op) { return guard([&] { delete op; }); }
+
+int cmbl_gradientf_logpdf_op(cmbl_dataset* ds, cmbl_lensop* L, const void* f, const void* d, int zero_d, void* out, int B) {
+  return guard([&] {
+    NOTNULL(ds); NOTNULL(L); NOTNULL(f); NOTNULL(out); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1");
+    SAME_CTX_OP(ds, L);
+    BY_DTYPE(ds->ctx, do_gradf_op, ds, L, f, d, zero_d, out, B);
+  });
+}
+int cmbl_wiener_cg_op(cmbl_dataset* ds, cmbl_lensop* L, const void* d, const void* fstart, double tol, int maxit, void* f_out,
+                      double* hist, int* nit, int B) {
+  return guard([&] {
+    NOTNULL(ds); NOTNULL(L); NOTNULL(f_out); NOTNULL(hist); NOTNULL(nit);
+    CMBL_REQUIRE(B >= 1 && maxit >= 1, ERR_ARG, "nbatch >= 1 and maxit >= 1");
+    SAME_CTX_OP(ds, L);
+    BY_DTYPE(ds->ctx, do_cg_op, ds, L, d, fstart, tol, maxit, f_out, hist, nit, B);
+  });
+}
+int cmbl_grad_logpdf_op(cmbl_dataset* ds, cmbl_lensop* L, const void* f, const void* phi, const void* d, double* lp, void* gf, void* gphi,
+                        int B, int quirk) {
+  return guard([&] {
+    NOTNULL(ds); NOTNULL(L); NOTNULL(f); NOTNULL(phi); NOTNULL(lp); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1");
+    SAME_CTX_OP(ds, L);
+    BY_DTYPE(ds->ctx, do_grad_lp_op, ds, L, f, phi, d, lp, gf, gphi, B, quirk);
   });
 }
 

@@ -8,6 +8,7 @@
 //   tu_cty_{f32,f64}_{a,b}.hip   the compile-time-plan kernels of the column side and the plain transforms (engine_ct.hpp CtLaunchY: k_ct_dft,
 //                           k_ct_dftx, k_ct_flow_y, k_ct_delta_y, k_ct_adj_y), lengths of CMBL_CT_LIST_A / _B (kernels_ct.hpp)
 //   tu_ctx_{f32,f64}_{a,b}.hip   ... and of the row side of the fused stages (CtLaunchX: k_ct_adj_x, k_ct_adj_x_dx, k_ct_dft2)
+//   tu_lensop_{f32,f64}.hip the fused column pass of a BilinearLens in a data set (engine_lensop.hpp: k_y_lens)
 //   tu_small_{f32,f64}.hip  the one-launch flows of small maps (engine_small.hpp: k_small_flow, k_small_adj)
 // An entry point reaches typed code in two ways only, and neither makes api.hip instantiate a member of a typed class (members defined in class
 // are inline, and an explicit instantiation DECLARATION does not stop inline functions from being instantiated -- [temp.explicit]/10):
@@ -35,6 +36,8 @@ struct cmbl_clbins { std::unique_ptr<cmbl::ClBins> p; };
 struct cmbl_flow { cmbl_ctx* ctx; std::unique_ptr<cmbl::FlowApi> p; };
 struct cmbl_bilinear { cmbl_ctx* ctx; std::unique_ptr<cmbl::BilinearApi> p; };
 struct cmbl_powerlens { cmbl_ctx* ctx; std::unique_ptr<cmbl::PowerLensApi> p; };
+enum { LENSOP_FLOW = 0, LENSOP_BILINEAR = 1, LENSOP_POWERLENS = 2 };
+struct cmbl_lensop { cmbl_ctx* ctx; int kind; void* h; };                    // non-owning view: h is the cmbl_flow / cmbl_bilinear / cmbl_powerlens of `kind`
 struct cmbl_projector { cmbl_ctx* ctx; std::unique_ptr<cmbl::ProjectorApi> p; };
 struct cmbl_dataset {
   cmbl_ctx* ctx; std::unique_ptr<cmbl::DatasetApi> p;
@@ -62,6 +65,9 @@ namespace cmbl {
   X(T, do_pl_create, (cmbl_powerlens* h, int order, int kind)) \
   X(T, do_gradf, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* f, const void* d, int zero_d, void* out, int B)) \
   X(T, do_cg, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* d, const void* fstart, double tol, int maxit, void* f_out, double* hist, int* nit, int B)) \
+  X(T, do_gradf_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void* d, int zero_d, void* out, int B)) \
+  X(T, do_cg_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* d, const void* fstart, double tol, int maxit, void* f_out, double* hist, int* nit, int B)) \
+  X(T, do_grad_lp_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void* phi, const void* d, double* lp, void* gf, void* gphi, int B, int quirk)) \
   X(T, do_lpm, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, double* lp, void* gfo, void* gphio, int B, int quirk)) \
   X(T, do_hmc, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, const void* mass, const void* white_p, const double* log_u, const uint64_t* seeds, uint64_t step, int nleap, double eps, int always, int quirk, int B, void* phio_out, double* dH, int* accept)) \
   X(T, do_map_step, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* phi, const void* fstart, const void* hinv, double amax, double atol, double cg_tol, int cg_maxit, int quirk, int B, void* f_out, void* phi_out, double* logpdf, double* alpha, int* ncg, int* nls)) \

@@ -16,6 +16,7 @@
 #include "kernels_harm.hpp"
 #include "kernels_generic.hpp"
 #include "kernels_ct.hpp"
+#include "lensops.hpp"
 
 namespace cmbl {
 
@@ -36,11 +37,11 @@ inline void raise_lds_limit(const void* fn, size_t bytes) {
 }
 // kernel classes for the optional per-launch event timing (cmbl_prof_*)
 enum KernelId { K_LAYOUT = 0, K_Y_R2C, K_Y_C2R, K_X_FFT, K_X_GRAD, K_FLOW_Y, K_ADJ_Y, K_ADJ_X, K_DELTA_Y, K_DELTA_ROWS, K_DPHI_Y, K_DPHI_X,
-                K_GRADHESS, K_HARM, K_LINCOMB, K_MASK, K_REDUCE, K_GEN_DFT, K_GEN_POINT, K_CG, K_XPW, K_PWFLAT, K_UD, K_CL, K_BL, K_PL, K_EDT, K_MASK_GAUSS, K_MASK_POINT, K_EQ_APPLY, K_EQ_MATMUL, K_EQ_POINT, K_EQ_COV, K_HPX_BUILD, K_HPX_PROJECT, K_NFFT_SPREAD, K_NFFT_INTERP, K_NFFT_MODES, K_EQ_FACTOR, K_COUNT };
+                K_GRADHESS, K_HARM, K_LINCOMB, K_MASK, K_REDUCE, K_GEN_DFT, K_GEN_POINT, K_CG, K_XPW, K_PWFLAT, K_UD, K_CL, K_BL, K_PL, K_EDT, K_MASK_GAUSS, K_MASK_POINT, K_EQ_APPLY, K_EQ_MATMUL, K_EQ_POINT, K_EQ_COV, K_HPX_BUILD, K_HPX_PROJECT, K_NFFT_SPREAD, K_NFFT_INTERP, K_NFFT_MODES, K_EQ_FACTOR, K_LENS_Y, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"layout", "y_r2c", "y_c2r", "x_fft", "x_grad", "flow_y_fwd", "adj_y", "adj_x", "delta_cols", "delta_rows",
                                                   "dphi_reduce", "dphi_combine", "gradhess_mult", "harm_apply", "lincomb", "mask_mul", "reduce",
                                                   "generic_dft", "generic_pointwise", "cg_update", "x_harm", "harm_dot", "ud_grade", "get_cl", "bilinear", "powerlens", "edt", "mask_gauss", "make_mask",
-                                                  "equirect_apply", "equirect_matmul", "equirect_pointwise", "equirect_cov", "healpix_build", "healpix_project", "nfft_spread", "nfft_interp", "nfft_modes", "equirect_factor"};
+                                                  "equirect_apply", "equirect_matmul", "equirect_pointwise", "equirect_cov", "healpix_build", "healpix_project", "nfft_spread", "nfft_interp", "nfft_modes", "equirect_factor", "lens_y"};
 
 // With profiling on, the launch goes through hipExtLaunchKernelGGL, whose start / stop events carry the kernel's OWN begin and end
 // timestamps (what rocprofv3's kernel trace reports); an event pair recorded around a plain launch also brackets its dispatch (+2 us).
@@ -112,6 +113,7 @@ struct CtxBase {
     int fill_target = env_int("CMBL_FILL_TARGET", 0);
     int row_fill_target = env_int("CMBL_ROW_FILL_TARGET", 0);
     int small_flow = env_int("CMBL_SMALL_FLOW", 1);                       // small maps: a whole flow as ONE launch, one workgroup per slice (kernels_small.hpp): 0 off, 1 up to 64 x 64, 2 wherever compiled (128 x 128)
+    int lens_fused = env_int("CMBL_LENS_FUSED", 0) != 0;                  // BilinearLens in a data set, power-of-two maps: the gather / CSR row sum inside the column pass that follows it (kernels_lensop.hpp)
     int eq_cov_scratch_mb = env_int("CMBL_EQ_COV_SCRATCH_MB", 256);         // Cℓ_to_Cov on ProjEquiRect: cap of the scratch of one slab of ring pairs (engine_equirect_cov.hpp); 0: one pair per slab
     int eq_factor_scratch_mb = env_int("CMBL_EQ_FACTOR_SCRATCH_MB", 8192);  // sqrt / pinv / logabsdet / solves of BlockDiagEquiRect: cap of the double working copies of one slab of blocks (engine_equirect_factor.hpp); 0: one block per slab
   } opts;
@@ -137,6 +139,7 @@ struct CtxBase {
     if (k == "fill_target") return &opts.fill_target;
     if (k == "row_fill_target") return &opts.row_fill_target;
     if (k == "small_flow") return &opts.small_flow;
+    if (k == "lens_fused") return &opts.lens_fused;
     if (k == "eq_cov_scratch_mb") return &opts.eq_cov_scratch_mb;
     if (k == "eq_factor_scratch_mb") return &opts.eq_factor_scratch_mb;
     return nullptr;
@@ -212,6 +215,10 @@ template <typename T, int N> struct CtLaunchX {
   static void adj_x_dx(Ctx<T>* c, const GenRun& r, const GenDft<T>& a, dim3 grid, int Sx, int ws, const GenDft<T>& a1);
   static void dft2(Ctx<T>* c, const GenRun& r, const GenDft<T>& a0, int kind0, dim3 grid, int Sx, int ws, const GenDft<T>& a1, int kind1);
 };
+
+// the table of a BilinearLens as the fused column pass reads it (kernels_lensop.hpp): `base` / `fr` for L (the gather), `rowstart` / `col` / `val`
+// for L' (the sorted CSR of the transpose); engine_bilinear.hpp makes them
+template <typename T> struct LensTab { const unsigned* base; const cx<T>* fr; const unsigned* rowstart; const unsigned* col; const T* val; };
 
 template <typename T>
 struct Ctx : CtxBase {
@@ -367,6 +374,8 @@ struct Ctx : CtxBase {
     if (tile && sizeof(T) == 4) return S / 2;
     return ((cols + S - 1) / S) * slices * 5 < 2L * num_cus ? S / 2 : S;
   }
+  // rfft_y(L in) (transposed: rfft_y(L' in)) of `slices` maps -> mixed layout in one launch; defined in engine_lensop.hpp (tu_lensop_*.hip)
+  void y_lens(bool transposed, const LensTab<T>& tab, const T* in, cx<T>* mixed, long slices);
   bool gen_dft_ct(const GenRun& r, const GenAxis& ax, GenDft<T> a, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
   void gen_dft(const GenRun& r, const GenAxis& ax, GenDft<T> a, long slices);   // defined in engine_gen.hpp (tu_gen_*.hip)
   // The two argument-block layouts of the any-size launches.  x pass: length Nx along the rows of [ky][x] (or [ky][kx]) half planes.
@@ -943,7 +952,7 @@ struct FlowApi {
 };
 
 template <typename T>
-struct Flow : FlowApi {
+struct Flow : FlowApi, LensOps<T> {
   Ctx<T>* c;
   int n;                                  // RK4 steps (src/lenseflow.jl:29 default 7)
   int Bphi = 0;
@@ -1577,6 +1586,23 @@ struct Flow : FlowApi {
     c->from_F(Y0.as<cx<T>>(), B_FOURIER, basis_df, df_out, P, B);
     c->F2ref(P0.as<cx<T>>(), (cx<T>*)dphi_out, B);
   }
+
+  // ---- LensOps<T>: thin forwards (the unfused forms of Dataset<T>) ----------------------------------------------------------------------
+  const char* op_name() const override { return "LenseFlow"; }
+  void op_check(int B) const override { check_ready(B); }
+  void op_set_phi(int basis, const void* phi, int nb) override { set_phi(basis, phi, nb); }
+  void op_lens(const T* in, T* out, int P, int B) override { flow_map(in, out, P, B, false); }
+  void op_lens_F(T* in, T* ftil, cx<T>* F, int P, int B) override {
+    T* m = ftil ? ftil : in;
+    flow_map(in, m, P, B, false);
+    c->rfft2_F(m, F, (long)P * B);
+  }
+  bool op_has_adjoint() const override { return true; }
+  void op_adj_F(const cx<T>* in, cx<T>* out, int P, int B) override { flow_adj_F(in, out, P, B, false); }
+  bool op_has_pullback() const override { return true; }
+  void op_pullback(T* ftil, cx<T>* w, cx<T>* dphi, int P, int B, bool quirk) override { flow_delta(ftil, w, dphi, P, B, true, quirk); }
+  bool op_has_inverse() const override { return true; }
+  void op_inv(const T* in, T* out, int P, int B) override { flow_map(in, out, P, B, true); }
 };
 
 // =================================================================================================
@@ -1679,10 +1705,10 @@ struct Dataset : DatasetApi {
   // From rfft_y(L f) in `a_ftil` (mixed, left intact) to  w = scale * B'M' Cn^-1 (M B L f - d):  w in QU Fourier to `w_F` (F layout) and
   // ifft_x(w) to L.H (mixed), ready for an adjoint / delta flow with h_ready.  Returns where the
   // partial sums of (MBLf - d)' Cn^-1 (MBLf - d) were left.  value_only: stop after the quadratic form.  dd == nullptr: d = 0.   (src/dataset.jl:59-66,76-80)
-  DotOut data_space(Flow<T>& L, const cx<T>* a_ftil, const cx<T>* dd, int dB, T scale, cx<T>* w_F, bool value_only, int B) {
+  // H: the mixed-layout buffer ifft_x(w) goes to (the flow's hbuf_ensure; unused when value_only)
+  DotOut data_space(cx<T>* H, const cx<T>* a_ftil, const cx<T>* dd, int dB, T scale, cx<T>* w_F, bool value_only, int B) {
     const long sl = (long)P * B;
     DotOut qn{};
-    cx<T>* H = value_only ? nullptr : L.hbuf_ensure(sl);
     by_pol([&](auto pp) {
       constexpr int PP = decltype(pp)::value;
       const ModeGeom<T> g = c->geom();
@@ -1728,20 +1754,18 @@ struct Dataset : DatasetApi {
     const long sl = (long)P * B;
     ftil.ensure(sizeof(T) * sl * c->npix());
     lens_from_harmonic(L, f_h, ftil.template as<T>(), B);
-    data_space(L, L.A.template as<cx<T>>(), dd, dB, T(-1), Y, false, B);
+    data_space(L.hbuf_ensure(sl), L.A.template as<cx<T>>(), dd, dB, T(-1), Y, false, B);
     L.flow_adj_F(Y, Y, P, B, false, true);
   }
 
   // mu = M B L f : harmonic F in (f may be nullptr == 0) -> harmonic F out (t2); uses mp2 for maps
   // `ftil_out`: where the lensed maps f~ = L f are left (default: the scratch mp2)
-  void mean(Flow<T>& L, const cx<T>* f_h, cx<T>* out, int B, T* ftil_out = nullptr) {
+  void mean(LensOps<T>& L, const cx<T>* f_h, cx<T>* out, int B, T* ftil_out = nullptr) {
     const long sl = (long)P * B;
     mp2.ensure(sizeof(T) * sl * c->npix());
-    T* m = ftil_out ? ftil_out : mp2.template as<T>();
     c->harm(f_h, out, P, B, 0, nullptr, false, false, true);
     c->F_to_map(out, mp2.template as<T>(), sl);
-    L.flow_map(mp2.template as<T>(), m, P, B, false);
-    c->rfft2_F(m, out, sl);
+    L.op_lens_F(mp2.template as<T>(), ftil_out, out, P, B);
     apply(OP_B, out, out, B, false, true, true);                          // QU Fourier -> (EB) x beam -> QU Fourier
     apply_M(out, B, false, true);
   }
@@ -1749,15 +1773,22 @@ struct Dataset : DatasetApi {
   // gradientf_logpdf (src/dataset.jl:76-80): L'B'M'Cn^-1 (d - M B L f) - Cf^-1 f.  f_h == nullptr means f = 0;
   // d_h == nullptr means d = 0.  All harmonic F layout.  out must not alias f_h.
   void gradientf(Flow<T>& L, const cx<T>* f_h, const cx<T>* dd, cx<T>* out, int B) {
-    const long n = fsize(B);
-    t2.ensure(sizeof(cx<T>) * n);
-    cx<T>* r = t2.template as<cx<T>>();
     if (f_h && fused()) {
+      t2.ensure(sizeof(cx<T>) * fsize(B));
+      cx<T>* r = t2.template as<cx<T>>();
       model_adjoint(L, f_h, dd, B, r, B);
       c->harm(r, r, P, B, 0, nullptr, false, true, false);                 // -> harmonic
       apply(OP_CF_INV, f_h, out, B, false, false, false, r, (T)1, (T)-1);  // out = r - Cf^-1 f
       return;
     }
+    gradientf(static_cast<LensOps<T>&>(L), f_h, dd, out, B);
+  }
+  // ... for any operator with an adjoint: the composition around op_lens_F / op_adj_F
+  void gradientf(LensOps<T>& L, const cx<T>* f_h, const cx<T>* dd, cx<T>* out, int B) {
+    CMBL_REQUIRE(L.op_has_adjoint(), ERR_ARG, std::string(L.op_name()) + ": gradientf_logpdf / the Wiener filter need L', which the reference does not define for this operator");
+    const long n = fsize(B);
+    t2.ensure(sizeof(cx<T>) * n);
+    cx<T>* r = t2.template as<cx<T>>();
     if (f_h) {
       mean(L, f_h, r, B);
       if (dd) c->lincomb1((T*)r, (const T*)dd, (const T*)r, 1.0, -1.0, 2 * n / B, B);
@@ -1769,7 +1800,7 @@ struct Dataset : DatasetApi {
     else apply(OP_CN_INV, r, r, B);
     apply_M(r, B, true, true);
     apply(OP_B, r, r, B, true, true, true);                                // QU Fourier -> (EB) x beam' -> QU Fourier
-    L.flow_adj_F(r, r, P, B, false);
+    L.op_adj_F(r, r, P, B);
     if (f_h) {
       c->harm(r, r, P, B, 0, nullptr, false, true, false);                 // -> harmonic
       apply(OP_CF_INV, f_h, out, B, false, false, false, r, (T)1, (T)-1);  // out = r - Cf^-1 f
@@ -1868,6 +1899,9 @@ struct Dataset : DatasetApi {
   }
   int wiener_cg(Flow<T>& L, const cx<T>* dd, const cx<T>* fstart, double tol, int maxit, cx<T>* f_out, double* hist, int B) {
     if (fused()) return wiener_cg_fused(L, dd, fstart, tol, maxit, f_out, hist, B);
+    return wiener_cg(static_cast<LensOps<T>&>(L), dd, fstart, tol, maxit, f_out, hist, B);
+  }
+  int wiener_cg(LensOps<T>& L, const cx<T>* dd, const cx<T>* fstart, double tol, int maxit, cx<T>* f_out, double* hist, int B) {
     const long n = fsize(B), nr = 2 * n / B;
     xs.ensure(sizeof(cx<T>) * n); rs.ensure(sizeof(cx<T>) * n); zs.ensure(sizeof(cx<T>) * n); ps.ensure(sizeof(cx<T>) * n);
     aps.ensure(sizeof(cx<T>) * n); best.ensure(sizeof(cx<T>) * n); bb.ensure(sizeof(cx<T>) * n);
@@ -1940,6 +1974,43 @@ struct Dataset : DatasetApi {
     return nh;
   }
 
+  // logpdf(ds; f, phi) (src/dataset.jl:59-66) per batch slot and, where asked for, its gradient with respect to f (harmonic) and phi (B planes,
+  // F layout) at once, for any operator whose phi has been set from `phi_F` (one plane):  z = M B L f - d;  w = -B'M'Cn^-1 z;
+  // grad_f = L' w - Cf^-1 f;  grad_phi = pullback(L f)(w) - Cphi^-1 phi -- what gradient(phi -> logpdf(ds; f, phi), phi) of MAP_marg evaluates
+  // (src/maximization.jl:307).  One forward lens and one pass through data space serve the value and both gradients.
+  void grad_logpdf(LensOps<T>& L, const cx<T>* f_h, const cx<T>* phi_F, const cx<T>* dd, double* lp, cx<T>* gf_h, cx<T>* gphi_F, int B, bool quirk) {
+    const long sl = (long)P * B, n = fsize(B), np = c->npix(), pl = c->plane();
+    CMBL_REQUIRE(B <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
+    CMBL_REQUIRE(!gf_h || L.op_has_adjoint(), ERR_ARG, std::string(L.op_name()) + ": the gradient with respect to f needs L', which the reference does not define for this operator");
+    CMBL_REQUIRE(!gphi_F || L.op_has_pullback(), ERR_ARG, std::string(L.op_name()) + ": the reference defines no pullback of L * f with respect to phi for this operator");
+    ftil.ensure(sizeof(T) * sl * np); t1.ensure(sizeof(cx<T>) * n); t2.ensure(sizeof(cx<T>) * n); t3.ensure(sizeof(cx<T>) * n);
+    gphi.ensure(sizeof(cx<T>) * pl); dphi1.ensure(sizeof(cx<T>) * B * pl); qdev.ensure(sizeof(double) * 3 * MAXBATCH);
+    cx<T>*z = t1.template as<cx<T>>(), *cfif = t2.template as<cx<T>>(), *w = t3.template as<cx<T>>(), *cpip = gphi.template as<cx<T>>();
+    double* qd = qdev.template as<double>();
+    mean(L, f_h, z, B, ftil.template as<T>());                              // leaves f~ = L f in ftil
+    c->lincomb1((T*)z, (const T*)z, (const T*)dd, 1.0, -1.0, 2 * n / B, B);
+    apply(OP_CN_INV, z, w, B);                c->dot_F_dev(z, w, P, B, qd + 2 * MAXBATCH);
+    apply(OP_CF_INV, f_h, cfif, B);           c->dot_F_dev(f_h, cfif, P, B, qd);
+    apply(OP_CPHI_INV, phi_F, cpip, 1, false, false, false, nullptr, 0, 1, 1);
+    c->dot_F_dev(phi_F, cpip, 1, 1, qd + MAXBATCH);
+    if (gf_h || gphi_F) {
+      apply_M(w, B, true, true);
+      apply(OP_B, w, w, B, true, true, true, nullptr, 0, (T)-1);            // d/df~ = -B'M'Cn^-1 z, QU Fourier
+      if (gphi_F) {
+        L.op_pullback(ftil.template as<T>(), w, dphi1.template as<cx<T>>(), P, B, quirk);
+        for (int b = 0; b < B; ++b) c->lincomb1((T*)(gphi_F + b * pl), (const T*)(dphi1.template as<cx<T>>() + b * pl), (const T*)cpip, 1.0, -1.0, 2 * pl, 1);
+      } else L.op_adj_F(w, w, P, B);
+      if (gf_h) {
+        c->harm(w, w, P, B, 0, nullptr, false, true, false);                // -> harmonic
+        c->lincomb1((T*)gf_h, (const T*)w, (const T*)cfif, 1.0, -1.0, 2 * n / B, B);
+      }
+    }
+    double q[3 * MAXBATCH];                                                 // (a NaN logpdf is a value, not an error: see logpdf_mixed)
+    CMBL_HIP(hipMemcpyAsync(q, qd, sizeof(double) * 3 * MAXBATCH, hipMemcpyDeviceToHost, c->stream));
+    CMBL_HIP(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < B; ++i) lp[i] = -0.5 * (q[i] + q[MAXBATCH] + q[2 * MAXBATCH + i] + logdet_sum);
+  }
+
   // logpdf(Mixed(ds); f°, phi°) and optionally its gradient.  fo: map (reference layout == internal), phio: F layout S0.
   // gfo (map) / gphio (F) may be nullptr for value only.
   // Fused form (power-of-two maps).  Launches outside the four flows: phi prior (1), precompute (4), the y pass of f° (1), unmix + Cf^-1
@@ -1970,7 +2041,7 @@ struct Dataset : DatasetApi {
     c->y_c2r(a, mp2.template as<T>(), sl);
     L.flow_map(mp2.template as<T>(), ftil.template as<T>(), P, B, false, true, true, &L.A);       // f~ = L f in ftil, rfft_y(f~) in A
     // z = M B L f - d ; z' Cn^-1 z ; w = -B'M'Cn^-1 z  (QU Fourier) with ifft_x(w) ready in L.H
-    parts[2] = data_space(L, L.A.template as<cx<T>>(), d_h.template as<cx<T>>(), Bd, T(-1), w, gfo == nullptr, B);
+    parts[2] = data_space(gfo ? L.hbuf_ensure(sl) : nullptr, L.A.template as<cx<T>>(), d_h.template as<cx<T>>(), Bd, T(-1), w, gfo == nullptr, B);
     double* const outs[3] = {qd, qd + MAXBATCH, qd + 2 * MAXBATCH};
     c->finish_parts(parts, outs, 3, B);
     auto finish_lp = [&]() {

@@ -26,7 +26,7 @@ struct BilinearApi {                         // what the C ABI (api.hip) holds o
 };
 
 template <typename T>
-struct Bilinear : BilinearApi {
+struct Bilinear : BilinearApi, LensOps<T> {
   Ctx<T>* c;
   bool ready = false, identity = false;
   T div = 1;                                 // the deflection maps are divided by this (Δx for ∇ϕ, 1 for pixel-unit maps)
@@ -154,29 +154,93 @@ struct Bilinear : BilinearApi {
     c->map_finish(dst, bo, out, cvt, P, B);
   }
 
-  // pullback of L*f (:165-171): δf = L'Δ in `bdf`; δϕ = ∇'·(Σ_pol Ł(Δ) Ł(∇f̃)), a Fourier plane per batch slot (ABI layout)
-  void grad(const void* f_lensed, int bdel, const void* delta, void* dphi, int bdf, void* df, int P, int B) override {
-    check_ready();
+  // δϕ of the pullback of L*f (:165-171): ∇'·(Σ_pol Ł(Δ) Ł(∇f̃)), a Fourier plane per batch slot, F layout, to dF
+  void grad_phi(const T* f_lensed, const T* dm, int P, int B) {
     const int S = P * B;
     const long np = c->npix(), pl = c->plane();
-    const T* dm = c->as_maps(bdel, delta, cvt, inm, P, B);
     // ∇f̃ in Fourier space (the reference's choice), back to maps
     vF.ensure(sizeof(cx<T>) * 3 * S * pl); gmaps.ensure(sizeof(T) * 2 * S * np); vmaps.ensure(sizeof(T) * 2 * B * np); dF.ensure(sizeof(cx<T>) * B * pl);
     cx<T>* F = vF.as<cx<T>>(); cx<T>* G = F + (long)S * pl;
     const dim3 fg(nblocks(pl));
-    c->rfft2_F((const T*)f_lensed, F, S);
+    c->rfft2_F(f_lensed, F, S);
     CMBL_LAUNCH(c, K_BL, (k_bl_gradmult<T>), fg, 0, c->stream, (const cx<T>*)F, G, c->lx_r.template as<T>(), c->ly.template as<T>(), c->Nx, pl, S);
     c->F_to_map(G, gmaps.as<T>(), 2L * S);
     CMBL_LAUNCH(c, K_BL, (k_bl_polsum<T>), dim3(std::min(pgrid(), 1024u), (unsigned)B), 0, c->stream, dm, (const T*)gmaps.as<T>(),
                 vmaps.as<T>(), np, P, B);
     c->rfft2_F(vmaps.as<T>(), F, 2L * B);
     CMBL_LAUNCH(c, K_BL, (k_bl_div<T>), fg, 0, c->stream, (const cx<T>*)F, dF.as<cx<T>>(), c->lx_r.template as<T>(), c->ly.template as<T>(), c->Nx, pl, B);
+  }
+  // pullback of L*f (:165-171): δf = L'Δ in `bdf`; δϕ in the ABI layout
+  void grad(const void* f_lensed, int bdel, const void* delta, void* dphi, int bdf, void* df, int P, int B) override {
+    check_ready();
+    const int S = P * B;
+    const T* dm = c->as_maps(bdel, delta, cvt, inm, P, B);
+    grad_phi((const T*)f_lensed, dm, P, B);
     c->F2ref(dF.as<cx<T>>(), (cx<T>*)dphi, B);
     // δf = B(Lϕ' * Δ)
     if (identity) return c->convert(B_MAP, dm, bdf, df, P, B, cvt);
     T* dst = c->map_dst(bdf, df, dm, outm, S);
     mul(false, true, dm, dst, S);
     c->map_finish(dst, bdf, df, cvt, P, B);
+  }
+
+  // ---- LensOps<T> (a BilinearLens in the L slot of a data set, src/dataset.jl:223) ----------------------------------------------------
+  // Power-of-two maps with the option "lens_fused": the gather (the row sum over the CSR of L') runs inside the column pass of the transform
+  // that follows it, Ctx::y_lens -- one launch instead of gather, map to HBM, y_r2c.  Any other size: the composition.
+  bool lens_fused() const { return !c->generic && c->opts.lens_fused && !identity; }
+  LensTab<T> tab(bool transposed) {
+    BlTab& t = table(false, transposed);
+    return LensTab<T>{t.base.as<unsigned>(), t.fr.as<cx<T>>(), t.rowstart.as<unsigned>(), t.col.as<unsigned>(), t.val.as<T>()};
+  }
+  // F = rfft2(L m) or rfft2(L' m) of S maps
+  void mul_F(bool transposed, const T* m, cx<T>* F, int S) {
+    if (lens_fused()) {
+      const LensTab<T> t = tab(transposed);
+      cx<T>* mx = c->mixed_scratch(S);
+      c->y_lens(transposed, t, m, mx, S);
+      c->template x_pass<0>(mx, F, S);
+      return;
+    }
+    if (identity) return c->rfft2_F(m, F, S);
+    outm.ensure(sizeof(T) * S * c->npix());
+    mul(false, transposed, m, outm.as<T>(), S);
+    c->rfft2_F(outm.as<T>(), F, S);
+  }
+  const char* op_name() const override { return "BilinearLens"; }
+  void op_check(int) const override { check_ready(); }
+  void op_set_phi(int basis, const void* phi, int nb) override { set_phi(basis, phi, nb); }
+  void op_lens(const T* in, T* out, int P, int B) override {
+    check_ready();
+    if (identity) return c->copy_maps(in, out, (long)P * B);
+    mul(false, false, in, out, P * B);
+  }
+  void op_lens_F(T* in, T* ftil, cx<T>* F, int P, int B) override {
+    check_ready();
+    if (!ftil) return mul_F(false, in, F, P * B);
+    op_lens(in, ftil, P, B);
+    c->rfft2_F(ftil, F, (long)P * B);
+  }
+  bool op_has_adjoint() const override { return true; }
+  void op_adj_F(const cx<T>* in, cx<T>* out, int P, int B) override {
+    check_ready();
+    inm.ensure(sizeof(T) * P * B * c->npix());
+    c->F_to_map(in, inm.as<T>(), (long)P * B);
+    mul_F(true, inm.as<T>(), out, P * B);
+  }
+  bool op_has_pullback() const override { return true; }
+  void op_pullback(T* ftil, cx<T>* w, cx<T>* dphi, int P, int B, bool) override {
+    check_ready();
+    inm.ensure(sizeof(T) * P * B * c->npix());
+    c->F_to_map(w, inm.as<T>(), (long)P * B);
+    grad_phi(ftil, inm.as<T>(), P, B);
+    CMBL_HIP(hipMemcpyAsync(dphi, dF.p, sizeof(cx<T>) * B * c->plane(), hipMemcpyDeviceToDevice, c->stream));
+    mul_F(true, inm.as<T>(), w, P * B);
+  }
+  bool op_has_inverse() const override { return true; }
+  void op_inv(const T* in, T* out, int P, int B) override {
+    check_ready();
+    if (identity) return c->copy_maps(in, out, (long)P * B);
+    solve(false, in, out, 5, P * B);
   }
 };
 

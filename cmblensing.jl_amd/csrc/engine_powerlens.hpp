@@ -33,7 +33,7 @@ template <int FIRST, typename Fn> void by_order(int n, const char* who, Fn&& fn)
 }
 
 template <typename T>
-struct PowerLens : PowerLensApi {
+struct PowerLens : PowerLensApi, LensOps<T> {
   Ctx<T>* c;
   const int order;
   const bool taylens;
@@ -150,6 +150,35 @@ struct PowerLens : PowerLensApi {
       accum(n, dmaps.as<T>(), n == 1 ? fm : dst, dst, n == 1, S);
     }
     c->map_finish(dst, bo, out, fF, P, B);
+  }
+
+  // ---- LensOps<T> (a PowerLens / Taylens in the L slot of a data set): the composition from the launches above, no kernel of its own ----
+  const char* op_name() const override { return taylens ? "Taylens" : "PowerLens"; }
+  void op_check(int) const override { CMBL_REQUIRE(ready, ERR_STATE, "cmbl_powerlens_set_phi / cmbl_powerlens_set_deflection has not been called"); }
+  void op_set_phi(int basis, const void* phi, int nb) override { set_phi(basis, phi, nb); }
+  void op_lens(const T* in, T* out, int P, int B) override { apply(F_FWD, B_MAP, in, B_MAP, out, P, B); }
+  DevBuf opm;
+  void op_lens_F(T* in, T* ftil, cx<T>* F, int P, int B) override {
+    if (!ftil) { opm.ensure(sizeof(T) * P * B * c->npix()); ftil = opm.as<T>(); }
+    op_lens(in, ftil, P, B);
+    c->rfft2_F(ftil, F, (long)P * B);
+  }
+  bool op_has_adjoint() const override { return !taylens; }
+  // r = Ð(g) + Σ_n ... (src/powerlens.jl:54-57) with g given as QU Fourier planes: the sum is accumulated onto them
+  void op_adj_F(const cx<T>* in, cx<T>* out, int P, int B) override {
+    CMBL_REQUIRE(!taylens, ERR_ARG, "Taylens: the reference defines no adjoint (src/taylens.jl:51 is its only action)");
+    op_check(B);
+    const int S = P * B;
+    const long np = c->npix(), pl = c->plane();
+    opm.ensure(sizeof(T) * S * np);
+    if (order > 0) { dF.ensure(sizeof(cx<T>) * (order + 1) * S * pl); dmaps.ensure(sizeof(T) * (order + 1) * S * np); if (!c->generic) c->mixed_scratch((long)(order + 1) * S); }
+    if (in != out) CMBL_HIP(hipMemcpyAsync(out, in, sizeof(cx<T>) * S * pl, hipMemcpyDeviceToDevice, c->stream));
+    c->F_to_map(out, opm.as<T>(), S);
+    for (int n = 1; n <= order; ++n) {
+      premul(n, opm.as<T>(), dmaps.as<T>(), S);
+      c->rfft2_F(dmaps.as<T>(), dF.as<cx<T>>(), (long)(n + 1) * S);
+      combine(n, dF.as<cx<T>>(), out, S);
+    }
   }
 };
 

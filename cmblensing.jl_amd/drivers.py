@@ -245,6 +245,7 @@ def MAP_joint_step(ds, phi, fstart=None, alpha_prev=1.0, alpha_tol=1e-4, alpha_m
     """One iteration of the `MAP_joint` loop body (src/maximization.jl:160-206) at fiducial θ with G = I (:146).
     The line search runs in the field precision T like the reference's `optimize(T(0), T(αmax), Brent(); abs_tol=T(αtol))`:
     Brent's relative tolerance is sqrt(eps(T)) and a NaN logpdf is replaced by (α/αmax)·prevfloat(T(Inf)) (:194-199)."""
+    ds._flow("MAP_joint_step")                                   # refused up front with another operator in ds.L (no pullback of L \ f)
     proj, h = ds.proj, ds.host
     fin = np.finfo(np.float32 if proj.T == torch.float32 else np.float64)
     Ginv_saved = ds.ops["G_inv"]
@@ -273,6 +274,7 @@ def MAP_joint_step(ds, phi, fstart=None, alpha_prev=1.0, alpha_tol=1e-4, alpha_m
 
 def MAP_joint(ds, nsteps=20, phi_start=None, fstart=None, **kw):
     """`MAP_joint(ds; nsteps, fstart)` (src/maximization.jl:116-233) at the dataset's current θ: returns (f, ϕ, history)."""
+    ds._flow("MAP_joint")                                   # refused up front with another operator in ds.L (no pullback of L \ f)
     proj = ds.proj
     B = ds.d.arr.shape[0]
     phi = Field(proj, torch.zeros_like(proj.empty(FOURIER, 1, B)), FOURIER) if phi_start is None else phi_start
@@ -381,6 +383,7 @@ def symplectic_integrate(proj, x0, p0, Lam, U, dUdx, N=50, eps=0.1):
 
 def hmc_step(ds, fo, po, white_p, log_u, N=25, eps=0.01, always_accept=False, alias_quirk=None):
     """`hmc_step` (src/sampling.jl:405-418) over ϕ° with U = logpdf(Mixed(ds)); white_p / log_u are the injected draws."""
+    ds._flow("hmc_step")                                   # refused up front with another operator in ds.L (no pullback of L \ f)
     proj = ds.proj
     Lam = mass_matrix_phi(ds)
     p0 = Field(proj, proj.diag_apply(np.sqrt(Lam)[None], proj.rfft(proj.tensor(white_p)), FOURIER, FOURIER), FOURIER)
@@ -396,6 +399,7 @@ def hmc_step_native(ds, fo, po, white_p=None, log_u=None, seeds=None, step=0, N=
     """The same update as `hmc_step`, as ONE library call (`cmbl_hmc_step`, include/cmblens.h): what a host that is neither Julia nor
     Python calls.  white_p / log_u None: drawn inside the library from `seeds` (one key per batch slot) and `step`, with the stream ids
     `sample_joint(rng="device")` uses.  Returns (ϕ°, ΔH, accept)."""
+    ds._flow("hmc_step_native")                                   # refused up front with another operator in ds.L (no pullback of L \ f)
     import ctypes
     from .lib import check
     proj = ds.proj
@@ -417,6 +421,7 @@ def hmc_step_native(ds, fo, po, white_p=None, log_u=None, seeds=None, step=0, N=
 
 def MAP_joint_step_native(ds, phi, fstart=None, alpha_prev=1.0, alpha_tol=1e-4, alpha_max=None, cg_tol=1e-1, cg_nsteps=500, alias_quirk=None):
     """The loop body of `MAP_joint_step` as ONE library call (`cmbl_map_joint_step`).  Returns dict(f, phi, alpha, logpdf, ncg, linesearch_evals)."""
+    ds._flow("MAP_joint_step_native")                                   # refused up front with another operator in ds.L (no pullback of L \ f)
     import ctypes
     from .lib import check
     proj, h = ds.proj, ds.host
@@ -452,6 +457,7 @@ def sample_f(ds, phi, white_f, white_n, fstart=None, tol=1e-1, nsteps=500):
 def gibbs_step(ds, phi, white_f, white_n, white_p, log_u, N=25, eps=0.01, always_accept=False, theta_pass=None, alias_quirk=None):
     """One `sample_joint` step (src/sampling.jl:187-193, 388-464): f | ϕ,θ -> mix -> HMC ϕ° | f°,θ -> [θ | f°,ϕ°] -> unmix -> logpdf.
     `theta_pass(fo, po)` runs the Gibbs θ passes in the mixed space and leaves the dataset at the new θ (theta.py)."""
+    ds._flow("gibbs_step")                                   # refused up front with another operator in ds.L (no pullback of L \ f)
     f, hist = sample_f(ds, phi, white_f, white_n)
     fo, po = ds.mix(f, phi)
     po2, dH, accept = hmc_step(ds, fo, po, white_p, log_u, N=N, eps=eps, always_accept=always_accept, alias_quirk=alias_quirk)
@@ -486,6 +492,7 @@ def sample_joint(ds, nsamps_per_chain, chain_ids=(0,), base_seed=0, phi_start="p
     initial state as step 1 and its first Gibbs pass is step 2 (:268,277); here the first Gibbs pass is saved as step 1, so
     `always_accept = (step < nburnin_always_accept)` (:400) is evaluated with the reference's step = ours + 1.
     Returns dict(logpdf, dH, accept [nsamps, nchains], phi, f [, theta])."""
+    ds._flow("sample_joint")                                   # refused up front with another operator in ds.L (no pullback of L \ f)
     from .chains import gather_chain_values, chain_seed
     from . import rng as R
     from . import chainfile as CF

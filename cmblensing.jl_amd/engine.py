@@ -618,6 +618,14 @@ class _Adjoint:
         return self.L._apply(FLOW_INVADJ, g, None, *extra, **kw)
 
 
+class _LensOpView(_Handle):
+    """`cmbl_lensop`: a view of a lensing operator's handle (include/cmblens.h); destroying it leaves the operator untouched"""
+    _destroy = "cmbl_lensop_destroy"
+
+    def __init__(self, L):
+        self._open(L.lib, f"cmbl_lensop_from_{L._abi}", L._h)
+
+
 class _LensOp(_Handle):
     """What the lensing operators share on top of cmbl_<_abi>_{create, destroy, set_phi, apply}: `L(ϕ)` / `L.set_phi(ϕ)` re-set ϕ only for a
     different object, `L * f`, `L.ldiv(f)`, `L.adjoint * g`, `L.adjoint.ldiv(g)`.  `extra`: what the class' `_extra` takes (BilinearLens: maxiter).
@@ -630,6 +638,14 @@ class _LensOp(_Handle):
         self.proj, self._phi = proj, None
         self._open(proj.lib, f"cmbl_{self._abi}_create", proj._h, *args)
         self._c_set_phi, self._c_apply = (getattr(self.lib, f"cmbl_{self._abi}_{fn}") for fn in ("set_phi", "apply"))
+
+    def _view(self):
+        """the typed, non-owning `cmbl_lensop` view of this operator that the `cmbl_*_op` entry points take; made once, freed with the operator"""
+        v = self.__dict__.get("_lensop_view")
+        if v is None:
+            v = _LensOpView(self)
+            self.__dict__["_lensop_view"] = v
+        return v._h
 
     def __call__(self, phi):
         """phi: Field (P=1; B=1 unless the class takes a batched ϕ)."""
@@ -782,6 +798,21 @@ def antilensing(L):
     return A.set_deflection(-L._defl[0], -L._defl[1])
 
 
+def _check_lens_slot(proj, L, allow_factory):
+    """What may go into the `L` slot of a data set on `proj`: None (the default LenseFlow), a `_LensOp` on that very `proj`, or (allow_factory) a
+    callable `proj -> _LensOp`.  Raises TypeError / ValueError here, so that a wrong handle never reaches the library."""
+    if L is None and allow_factory:
+        return
+    if isinstance(L, _LensOp):
+        if L.proj is not proj:
+            raise ValueError(f"the lensing operator lives on another projection ({L.proj.Ny} x {L.proj.Nx}, {L.proj.T}) than the data set: make it on ds.proj")
+        return
+    if allow_factory and callable(L):
+        return
+    raise TypeError(f"the L slot of a data set takes a lensing operator (LenseFlow, BilinearLens, PowerLens, Taylens) on its projection, "
+                    f"or a callable proj -> operator; got {type(L).__name__}")
+
+
 class BaseDataSet(_Handle):
     """`BaseDataSet` at fiducial θ (src/dataset.jl:37-57) with the operators resident on the device.
 
@@ -794,10 +825,11 @@ class BaseDataSet(_Handle):
     _ids = dict(Cf_inv=OP_CF_INV, Cn_inv=OP_CN_INV, B=OP_B, Mf=OP_MF, D=OP_D, D_inv=OP_D_INV,
                 precond_inv=OP_PRECOND_INV, Cphi_inv=OP_CPHI_INV, G_inv=OP_G_INV, Mpix=OP_MPIX)
 
-    def __init__(self, proj, P, ops, d=None, logdet_sum=0.0, nsteps=7):
+    def __init__(self, proj, P, ops, d=None, logdet_sum=0.0, nsteps=7, L=None):
         self.proj, self.P = proj, int(P)
+        _check_lens_slot(proj, L, allow_factory=True)               # before anything is created on the device
         self._open(proj.lib, "cmbl_dataset_create", proj._h, self.P)
-        self.L = LenseFlow(proj, nsteps)
+        self.L = LenseFlow(proj, nsteps) if L is None else L
         self.ops = {}
         for k, v in ops.items():
             if v is None:
@@ -817,6 +849,27 @@ class BaseDataSet(_Handle):
         # (and starts every context with plain working-precision sums, the reference's `sum_accuracy_mode`).
         self.alias_quirk = reference_exact()
         check(self.lib.cmbl_dataset_set_logdet(self._h, self.logdet_sum))
+
+    @property
+    def L(self):
+        """The lensing operator of the data set (`load_sim(L = ...)`, src/dataset.jl:223, 306, 333): a `LenseFlow` by default; any `_LensOp` on
+        `ds.proj`, or a callable `proj -> _LensOp` (`BilinearLens`, `lambda p: PowerLens(p, 4)`), may be assigned.  Anything else raises at once."""
+        return self._L
+
+    @L.setter
+    def L(self, op):
+        if not isinstance(op, _LensOp) and callable(op):
+            _check_lens_slot(self.proj, op, allow_factory=True)
+            op = op(self.proj)
+        _check_lens_slot(self.proj, op, allow_factory=False)
+        self._L = op
+
+    def _flow(self, what):
+        """the `LenseFlow` in the slot, for what the reference defines with it alone"""
+        if not isinstance(self._L, LenseFlow):
+            raise NotImplementedError(f"{what} needs the gradient of logpdf(Mixed(ds)), a pullback of `L \\ f`: src/bilinearlens.jl (:165-171) has a "
+                                      f"rule for `L * f` alone, and PowerLens / Taylens have no inverse -- use a LenseFlow in ds.L, not {type(self._L).__name__}")
+        return self._L
 
     def set_logdet(self, logdet_sum):
         self.logdet_sum = float(logdet_sum)
@@ -859,6 +912,8 @@ class BaseDataSet(_Handle):
         minus Cϕ⁻¹ϕ.  f, d may carry B batch slots against one ϕ."""
         d = self.d if d is None else d
         alias_quirk = self.alias_quirk if alias_quirk is None else alias_quirk
+        if not isinstance(self.L, LenseFlow):
+            return self.grad_logpdf(f, phi, d, want_f=False, alias_quirk=alias_quirk)[2]
         ft = self.L(phi) * f.to(MAP)
         z = d.to(HARMONIC) - self._mask(self._apply("B", ft))
         w = self._applyT("B", self._maskT(self._apply("Cn_inv", z)), basis_out=FOURIER)
@@ -867,6 +922,25 @@ class BaseDataSet(_Handle):
         if prior.shape[0] != dphi.arr.shape[0]:
             prior = prior.expand(dphi.arr.shape[0], -1, -1, -1).contiguous()
         return dphi - Field(self.proj, prior, FOURIER)
+
+    def grad_logpdf(self, f, phi, d=None, want_f=True, want_phi=True, alias_quirk=None):
+        """(logpdf(ds; f, ϕ) per batch slot, ∇f [HARMONIC] or None, ∇ϕ [FOURIER, one plane per slot] or None) in one call
+        (`cmbl_grad_logpdf_op`): one forward lens and one pass through data space serve the value and both gradients.  ϕ: one plane, which
+        becomes the operator's.  What the reference does not define for the operator in the slot (∇ϕ with PowerLens / Taylens, ∇f with
+        Taylens) is refused by the library."""
+        f, phi = f.to(HARMONIC), phi.to(FOURIER)
+        d = self.d if d is None else d.to(HARMONIC)
+        alias_quirk = self.alias_quirk if alias_quirk is None else alias_quirk
+        B = f.arr.shape[0]
+        assert d.arr.shape[0] == B and phi.arr.shape[0] == 1
+        lp = (ctypes.c_double * B)()
+        gf = self.proj.empty(HARMONIC, self.P, B) if want_f else None
+        gp = self.proj.empty(FOURIER, 1, B) if want_phi else None
+        L = self.L
+        L.invalidate()
+        check(self.lib.cmbl_grad_logpdf_op(self._h, L._view(), _ptr(f.arr), _ptr(phi.arr), _ptr(d.arr), lp, _ptr(gf), _ptr(gp), B, 1 if alias_quirk else 0))
+        L._phi = phi                                    # the library set the operator's ϕ from this very plane
+        return (np.array(lp[:]), None if gf is None else Field(self.proj, gf, HARMONIC), None if gp is None else Field(self.proj, gp, FOURIER))
 
     def _mask(self, f):
         """M = Mfourier * Mpix (src/dataset.jl:279-285) on a Field; returns HARMONIC"""
@@ -901,32 +975,43 @@ class BaseDataSet(_Handle):
         check(self.lib.cmbl_dataset_set_data(self._h, _ptr(d.arr), d.arr.shape[0]))
 
     def gradientf_logpdf(self, f, phi, d=None, zero_d=False):
-        """src/dataset.jl:76-80"""
+        """src/dataset.jl:76-80.  phi = None: the operator as it was last set (`set_phi` / `set_deflection`)"""
         f = f.to(HARMONIC)
-        L = self.L(phi)
+        L = self.L if phi is None else self.L(phi)
         B = f.arr.shape[0]
         out = self.proj.empty(HARMONIC, self.P, B)
         dd = None if d is None else d.to(HARMONIC).arr
+        if not isinstance(L, LenseFlow):
+            check(self.lib.cmbl_gradientf_logpdf_op(self._h, L._view(), _ptr(f.arr), _ptr(dd), 1 if zero_d else 0, _ptr(out), B))
+            return Field(self.proj, out, HARMONIC)
         check(self.lib.cmbl_gradientf_logpdf(self._h, L._h, _ptr(f.arr), _ptr(dd), 1 if zero_d else 0, _ptr(out), B))
         return Field(self.proj, out, HARMONIC)
 
     def argmaxf_logpdf(self, phi, d=None, fstart=None, tol=1e-1, nsteps=500):
-        """Wiener filter (src/maximization.jl:17-42): returns (f [HARMONIC], history [(i, res_per_batch)])."""
-        L = self.L(phi)
+        """Wiener filter (src/maximization.jl:17-42): returns (f [HARMONIC], history [(i, res_per_batch)]).  phi = None: the operator as it
+        was last set (`set_phi` / `set_deflection`)."""
+        L = self.L if phi is None else self.L(phi)
         dd = self.d if d is None else d.to(HARMONIC)
         B = dd.arr.shape[0]
         out = self.proj.empty(HARMONIC, self.P, B)
         hist = (ctypes.c_double * (nsteps * B))()
         nit = ctypes.c_int(0)
         fs = None if fstart is None else fstart.to(HARMONIC).arr
-        check(self.lib.cmbl_wiener_cg(self._h, L._h, _ptr(dd.arr), _ptr(fs), float(tol), int(nsteps), _ptr(out),
-                                      hist, ctypes.byref(nit), B))
+        if not isinstance(L, LenseFlow):
+            check(self.lib.cmbl_wiener_cg_op(self._h, L._view(), _ptr(dd.arr), _ptr(fs), float(tol), int(nsteps), _ptr(out),
+                                             hist, ctypes.byref(nit), B))
+        else:
+            check(self.lib.cmbl_wiener_cg(self._h, L._h, _ptr(dd.arr), _ptr(fs), float(tol), int(nsteps), _ptr(out),
+                                          hist, ctypes.byref(nit), B))
         h = np.array(hist[: nit.value * B]).reshape(nit.value, B)
         return Field(self.proj, out, HARMONIC), [(i + 1, h[i]) for i in range(nit.value)]
 
     def logpdf_mixed(self, fo, phio):
         """logpdf(Mixed(ds); f°, ϕ°) (src/dataset.jl:84-87)"""
         fo, phio = fo.to(MAP), phio.to(FOURIER)
+        if not isinstance(self.L, LenseFlow):           # composed: unmix through the operator's own inverse (refused by the library where it has none)
+            f, phi = self.unmix(fo, phio)
+            return self.logpdf(f, phi) - self.logdet_mix
         B = fo.arr.shape[0]
         lp = (ctypes.c_double * B)()
         self.L.invalidate()
@@ -935,6 +1020,7 @@ class BaseDataSet(_Handle):
 
     def gradient_logpdf_mixed(self, fo, phio, alias_quirk=None):
         """(logpdf, ∇f° [MAP], ∇ϕ° [FOURIER]) — the "∇lnP" step (test/runbenchmarks.jl:120).  A NaN logpdf is returned as NaN."""
+        self._flow("gradient_logpdf_mixed")
         alias_quirk = self.alias_quirk if alias_quirk is None else alias_quirk
         fo, phio = fo.to(MAP), phio.to(FOURIER)
         B = fo.arr.shape[0]

@@ -54,6 +54,13 @@ SIGNATURES = {
     "cmbl_dataset_set_logdet": [_vp, _cd],
     "cmbl_gradientf_logpdf": [_vp, _vp, _vp, _vp, _ci, _vp, _ci],
     "cmbl_wiener_cg": [_vp, _vp, _vp, _vp, _cd, _ci, _vp, _pd, _pci, _ci],
+    "cmbl_lensop_from_lenseflow": [_vp, _pvp],
+    "cmbl_lensop_from_bilinear": [_vp, _pvp],
+    "cmbl_lensop_from_powerlens": [_vp, _pvp],
+    "cmbl_lensop_destroy": [_vp],
+    "cmbl_gradientf_logpdf_op": [_vp, _vp, _vp, _vp, _ci, _vp, _ci],
+    "cmbl_wiener_cg_op": [_vp, _vp, _vp, _vp, _cd, _ci, _vp, _pd, _pci, _ci],
+    "cmbl_grad_logpdf_op": [_vp, _vp, _vp, _vp, _vp, _pd, _vp, _vp, _ci, _ci],
     "cmbl_logpdf_mixed": [_vp, _vp, _vp, _vp, _pd, _ci],
     "cmbl_grad_logpdf_mixed": [_vp, _vp, _vp, _vp, _pd, _vp, _vp, _ci, _ci],
     "cmbl_hmc_step": [_vp, _vp, _vp, _vp, _vp, _vp, _pd, _pu64, _u64, _ci, _cd, _ci, _ci, _ci, _vp, _pd, _pci],
@@ -129,7 +136,7 @@ def library_path():
 # One object each, then linked.
 # (longest first: the build is a pool of as many compilers as the host has cores)
 UNITS = ["tu_cty_f32_b", "tu_cty_f64_b", "tu_ctx_f32_b", "tu_ctx_f64_b", "tu_cty_f32_a", "tu_cty_f64_a", "tu_main_f32", "tu_main_f64",
-         "tu_ctx_f32_a", "tu_ctx_f64_a", "tu_small_f32", "tu_small_f64", "tu_gen_f32", "tu_gen_f64", "api"]
+         "tu_ctx_f32_a", "tu_ctx_f64_a", "tu_small_f32", "tu_small_f64", "tu_gen_f32", "tu_gen_f64", "tu_lensop_f32", "tu_lensop_f64", "api"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
 

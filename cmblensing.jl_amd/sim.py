@@ -142,13 +142,15 @@ def white_noise(seed, shape):
 
 def load_sim(theta_pix, Nside, pol, cls, T=torch.float32, device=0, muK_arcmin_T=3.0, lknee=100.0, alphaknee=3.0,
              beam_fwhm=0.0, pixel_mask=None, bandpass_lmax=3000, nsteps=7, Nbatch=1, seeds=(1, 2, 3),
-             Nphi=None, Nphi_fac=2, G=None, rng="host", pixel_mask_kwargs=None):
+             Nphi=None, Nphi_fac=2, G=None, rng="host", pixel_mask_kwargs=None, L=None):
     # Nphi: None / "qe" -> N⁰ of the quadratic estimator like the reference; "flat" -> cheap flat level; or an [x,ky] plane
     """`load_sim` (src/dataset.jl:186-338).  `cls`: dict group -> dict {TT,EE,BB,TE,pp} of Cls for the groups
     'unlensed_scalar', 'tensor', 'total' (e.g. decoded from the reference's dat/default_camb_Cls.jld2).
     `pixel_mask_kwargs`: a dict of `make_mask` keywords: Mpix = make_mask(proj; ...) made on the device (:279-281), its point sources drawn
     with `seed` = seeds[0] unless the dict says otherwise (the reference hands make_mask a copy of the simulation's rng).  `pixel_mask`: the
     keywords of the deterministic `border_mask` instead; giving both is a ValueError.
+    `L`: the lensing operator of the data set (`load_sim(L = BilinearLens)`, :223): None = `LenseFlow(proj, nsteps)`, or a callable
+    `proj -> operator` such as `BilinearLens` or `lambda p: PowerLens(p, 4)` (`BaseDataSet` has what each operator covers).
     Returns dict(f, phi, ftilde, d, ds, proj) with Fields on the device."""
     if pixel_mask is not None and pixel_mask_kwargs is not None:
         raise ValueError("load_sim: give pixel_mask (border_mask) or pixel_mask_kwargs (make_mask), not both")
@@ -182,7 +184,7 @@ def load_sim(theta_pix, Nside, pol, cls, T=torch.float32, device=0, muK_arcmin_T
     logdet_sum = Cf.logdet(proj) + Cn.logdet(proj) + HarmOp([Cphi]).logdet(proj)
     ops = dict(Cf_inv=Cf.pinv().p, Cn_inv=Cn.pinv().p, B=Bop.p, Mf=Mf.p, D=D.p, D_inv=D.pinv().p,
                precond_inv=precond.pinv().p, Cphi_inv=_pinv(Cphi)[None], G_inv=_pinv(Gp)[None], Mpix=Mpix)
-    ds = BaseDataSet(proj, P, ops, logdet_sum=logdet_sum, nsteps=nsteps)
+    ds = BaseDataSet(proj, P, ops, logdet_sum=logdet_sum, nsteps=nsteps, L=L)
     Cft = mk(cls["total"])                                                     # Cf̃ (:270)
     ds.host = dict(Cf=Cf, Cn=Cn, Cphi=Cphi, Mf=Mf, B=Bop, D=D, Nphi=Nphi, G=Gp, Mpix=Mpix, precond=precond, Cftilde=Cft,
                    Cfs=Cfs, Cten=Cten, r0=0.2, Aphi0=1.0, s2len=s2len)

@@ -40,6 +40,7 @@ typedef struct cmbl_dataset cmbl_dataset;
 typedef struct cmbl_clbins cmbl_clbins;
 typedef struct cmbl_bilinear cmbl_bilinear;
 typedef struct cmbl_powerlens cmbl_powerlens;
+typedef struct cmbl_lensop cmbl_lensop;
 
 enum { CMBL_OK = 0, CMBL_ERR_ARG = 1, CMBL_ERR_SHAPE = 2, CMBL_ERR_HIP = 3, CMBL_ERR_NAN = 4,
        CMBL_ERR_STATE = 5, CMBL_ERR_ALLOC = 6 };
@@ -114,6 +115,13 @@ int cmbl_ctx_geometry_host(cmbl_ctx* ctx, int which, double* out_host, size_t n)
  *                                                                   the half plane resident in LDS (csrc/kernels_small.hpp): 0 = off, 1 = up to 64 x 64 pixels (faster at every
  *                                                                   batch size), 2 = wherever compiled (up to 128 x 128 in single, 64 x 64 in double precision).  Results agree
  *                                                                   with the staged path to rounding, not bit for bit (tests/test_gpu_small.py)
+ *        "lens_fused"            CMBL_LENS_FUSED (0)               a BilinearLens in the L slot of a data set (cmbl_*_op), power-of-two maps: 1 = the bilinear gather and the row sum
+ *                                                                   of the transpose run inside the column pass of the transform behind them (csrc/kernels_lensop.hpp), one launch
+ *                                                                   instead of gather, map, y_r2c; 0 = the composition from the stand-alone launches.  Other sizes always take the
+ *                                                                   composition.  The two agree to rounding (tests/test_gpu_lensop_dataset.py).
+ *                                                                   Default 0 at every size: measured on MI355X, the Wiener-filter CG iteration with 0 / with 1 takes 0.215 / 0.227 ms at 1024^2 QU fp32 B = 1,
+ *                                                                   0.934 / 1.063 ms at B = 8, 1.186 / 1.417 ms at 2048^2 QU fp64 B = 1, 8.367 / 10.320 ms at B = 8 (profiles/lensop_wf_times.txt):
+ *                                                                   the fused pass is slower everywhere and stays an option.
  *        "eq_cov_scratch_mb"     CMBL_EQ_COV_SCRATCH_MB (256)      cmbl_equirect_cov: cap in MiB of the scratch of one slab of ring pairs (at least one pair per slab);
  *                                                                   changes no result (tests/test_gpu_equirect_cov.py)
  *        "eq_factor_scratch_mb"  CMBL_EQ_FACTOR_SCRATCH_MB (8192)  cmbl_equirect_block_svd / _logabsdet / _solve: cap in MiB of the double working copies of one slab of
@@ -466,6 +474,30 @@ int cmbl_gradientf_logpdf(cmbl_dataset* ds, cmbl_flow* L, const void* f, const v
  * fstart may be NULL; res_hist_host has room for maxit*nbatch doubles; *nit_host = history length. */
 int cmbl_wiener_cg(cmbl_dataset* ds, cmbl_flow* L, const void* d, const void* fstart, double tol, int maxit,
                    void* f_out, double* res_hist_host, int* nit_host, int nbatch);
+/* ---- any lensing operator in the L slot of a data set (load_sim(L = ...), src/dataset.jl:223, 306, 333; src/bilinearlens.jl:10-17) --------
+ * A cmbl_lensop is a typed, NON-OWNING view of an operator handle: destroying the view leaves the operator untouched, and the operator must
+ * outlive its views.  The operator and the data set must live on the same context (CMBL_ERR_ARG).  What the reference does not define for an
+ * operator is refused with CMBL_ERR_ARG and a message, never approximated: the adjoint of a Taylens (so cmbl_gradientf_logpdf_op /
+ * cmbl_wiener_cg_op with it, src/taylens.jl:51), the pullback with respect to phi of a PowerLens / Taylens (gphi_out, src/powerlens.jl).
+ * Through a view of a LenseFlow the first two calls run the very code of cmbl_gradientf_logpdf / cmbl_wiener_cg, bit for bit.
+ * cmbl_hmc_step, cmbl_map_joint_step and cmbl_*logpdf_mixed stay with cmbl_flow*: src/bilinearlens.jl has no pullback of L \ f. */
+int cmbl_lensop_from_lenseflow(cmbl_flow* L, cmbl_lensop** out);
+int cmbl_lensop_from_bilinear(cmbl_bilinear* L, cmbl_lensop** out);
+int cmbl_lensop_from_powerlens(cmbl_powerlens* L, cmbl_lensop** out);
+int cmbl_lensop_destroy(cmbl_lensop* op);            /* the operator itself is untouched */
+/* gradientf_logpdf (src/dataset.jl:76-80) and argmaxf_logpdf (src/maximization.jl:17-42): layouts and semantics of cmbl_gradientf_logpdf /
+ * cmbl_wiener_cg.  The operator is used as it was last set (set_phi / set_deflection); CMBL_ERR_STATE before either. */
+int cmbl_gradientf_logpdf_op(cmbl_dataset* ds, cmbl_lensop* L, const void* f, const void* d, int use_zero_d, void* out, int nbatch);
+int cmbl_wiener_cg_op(cmbl_dataset* ds, cmbl_lensop* L, const void* d, const void* fstart, double tol, int maxit,
+                      void* f_out, double* res_hist_host, int* nit_host, int nbatch);
+/* logpdf(ds; f, phi) (src/dataset.jl:59-66) per batch slot to lp_host, and where asked for its gradient with respect to f (gf_out, HARMONIC) and
+ * phi (gphi_out, FOURIER, nbatch planes) at once: the phi part is the pullback of L*f (src/flowops.jl:40-54, src/bilinearlens.jl:165-171)
+ * applied to B'M'Cn^-1 (d - M B L f), minus Cphi^-1 phi -- gradient(phi -> logpdf(ds; f, phi), phi) of MAP_marg (src/maximization.jl:307).
+ * Sets the operator's phi from `phi` (FOURIER, one plane).  f HARMONIC; d = NULL uses ds.d; gf_out and gphi_out may each be NULL.
+ * alias_quirk is read by the LenseFlow view only.  Synchronises the context's stream. */
+int cmbl_grad_logpdf_op(cmbl_dataset* ds, cmbl_lensop* L, const void* f, const void* phi, const void* d,
+                        double* lp_host, void* gf_out, void* gphi_out, int nbatch, int alias_quirk);
+
 /* logpdf(Mixed(ds); f°, phi°) and its gradient (src/dataset.jl:84-117, src/maximization.jl:178):
  * fo MAP, phio FOURIER; gfo MAP, gphio FOURIER.  L's phi is overwritten with G \ phi°. */
 int cmbl_logpdf_mixed(cmbl_dataset* ds, cmbl_flow* L, const void* fo, const void* phio, double* lp_host, int nbatch);
