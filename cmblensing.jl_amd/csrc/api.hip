@@ -310,7 +310,8 @@ int cmbl_gradientf_logpdf(cmbl_dataset* ds, cmbl_flow* L, const void* f, const v
   return guard([&] {
     NOTNULL(ds); NOTNULL(L); NOTNULL(f); NOTNULL(out); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1");
     SAME_CTX(ds, L);
-    BY_DTYPE(ds->ctx, do_gradf, ds, L, f, d, zero_d, out, B);
+    cmbl_lensop v{L->ctx, LENSOP_FLOW, L};
+    BY_DTYPE(ds->ctx, do_gradf_op, ds, &v, f, d, zero_d, out, B);
   });
 }
 
@@ -320,7 +321,8 @@ int cmbl_wiener_cg(cmbl_dataset* ds, cmbl_flow* L, const void* d, const void* fs
     NOTNULL(ds); NOTNULL(L); NOTNULL(f_out); NOTNULL(hist); NOTNULL(nit);
     CMBL_REQUIRE(B >= 1 && maxit >= 1, ERR_ARG, "nbatch >= 1 and maxit >= 1");
     SAME_CTX(ds, L);
-    BY_DTYPE(ds->ctx, do_cg, ds, L, d, fstart, tol, maxit, f_out, hist, nit, B);
+    cmbl_lensop v{L->ctx, LENSOP_FLOW, L};
+    BY_DTYPE(ds->ctx, do_cg_op, ds, &v, d, fstart, tol, maxit, f_out, hist, nit, B);
   });
 }
 

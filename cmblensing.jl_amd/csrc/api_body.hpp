@@ -58,47 +58,21 @@ template <typename T> void do_logdet(cmbl_ctx* ctx, const void* d, int nplanes, 
   c->ref2F_real((const T*)d, c->tmpB.template as<T>(), nplanes);
   c->logdet_F(c->tmpB.template as<T>(), nplanes, out);
 }
-template <typename T>
-void do_gradf(cmbl_dataset* dsh, cmbl_flow* Lh, const void* f, const void* d, int zero_d, void* out, int B) {
-  Dataset<T>& ds = typed<Dataset<T>>(dsh); Flow<T>& L = typed<Flow<T>>(Lh);
-  Ctx<T>* c = ds.c;
-  const long n = ds.fsize(B);
-  ds.cvt.ensure(sizeof(cx<T>) * 3 * n);
-  cx<T>* fF = ds.cvt.template as<cx<T>>(); cx<T>* dF = fF + n; cx<T>* oF = dF + n;
-  c->ref2F((const cx<T>*)f, fF, (long)ds.P * B);
-  const cx<T>* dd = nullptr;
-  if (!zero_d) {
-    if (d) { c->ref2F((const cx<T>*)d, dF, (long)ds.P * B); dd = dF; }
-    else { CMBL_REQUIRE(ds.Bd == B, ERR_SHAPE, "dataset data batch size differs from nbatch"); dd = ds.d_h.template as<cx<T>>(); }
-  }
-  ds.gradientf(L, fF, dd, oF, B);
-  c->F2ref(oF, (cx<T>*)out, (long)ds.P * B);
-}
-template <typename T>
-void do_cg(cmbl_dataset* dsh, cmbl_flow* Lh, const void* d, const void* fstart, double tol, int maxit, void* f_out, double* hist, int* nit, int B) {
-  Dataset<T>& ds = typed<Dataset<T>>(dsh); Flow<T>& L = typed<Flow<T>>(Lh);
-  Ctx<T>* c = ds.c;
-  const long n = ds.fsize(B);
-  ds.cvt.ensure(sizeof(cx<T>) * 3 * n);
-  cx<T>* dF = ds.cvt.template as<cx<T>>(); cx<T>* sF = dF + n; cx<T>* oF = sF + n;
-  const cx<T>* dd;
-  if (d) { c->ref2F((const cx<T>*)d, dF, (long)ds.P * B); dd = dF; }
-  else { CMBL_REQUIRE(ds.Bd == B, ERR_SHAPE, "dataset data batch size differs from nbatch"); dd = ds.d_h.template as<cx<T>>(); }
-  const cx<T>* fs = nullptr;
-  if (fstart) { c->ref2F((const cx<T>*)fstart, sF, (long)ds.P * B); fs = sF; }
-  *nit = ds.wiener_cg(L, dd, fs, tol, maxit, oF, hist, B);
-  c->F2ref(oF, (cx<T>*)f_out, (long)ds.P * B);
-  CMBL_HIP(hipStreamSynchronize(c->stream));
-}
 // the operator behind a view, as Dataset<T> sees it
 template <typename T> LensOps<T>& lensop_of(cmbl_lensop* v) {
   if (v->kind == LENSOP_FLOW) return typed<Flow<T>>(static_cast<cmbl_flow*>(v->h));
   if (v->kind == LENSOP_BILINEAR) return typed<Bilinear<T>>(static_cast<cmbl_bilinear*>(v->h));
   return typed<PowerLens<T>>(static_cast<cmbl_powerlens*>(v->h));
 }
+// the data of a call in the F layout: `d` (reference layout, converted into dF) or, d == NULL, what the data set holds
+template <typename T> const cx<T>* data_of(Dataset<T>& ds, const void* d, cx<T>* dF, int B) {
+  if (d) { ds.c->ref2F((const cx<T>*)d, dF, (long)ds.P * B); return dF; }
+  CMBL_REQUIRE(ds.Bd == B, ERR_SHAPE, "dataset data batch size differs from nbatch");
+  return ds.d_h.template as<cx<T>>();
+}
+// (cmbl_gradientf_logpdf and cmbl_wiener_cg come here too, with a view of their LenseFlow)
 template <typename T>
 void do_gradf_op(cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void* d, int zero_d, void* out, int B) {
-  if (Lh->kind == LENSOP_FLOW) return do_gradf<T>(dsh, static_cast<cmbl_flow*>(Lh->h), f, d, zero_d, out, B);
   Dataset<T>& ds = typed<Dataset<T>>(dsh); LensOps<T>& L = lensop_of<T>(Lh);
   Ctx<T>* c = ds.c;
   L.op_check(B);
@@ -106,26 +80,18 @@ void do_gradf_op(cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void* 
   ds.cvt.ensure(sizeof(cx<T>) * 3 * n);
   cx<T>* fF = ds.cvt.template as<cx<T>>(); cx<T>* dF = fF + n; cx<T>* oF = dF + n;
   c->ref2F((const cx<T>*)f, fF, (long)ds.P * B);
-  const cx<T>* dd = nullptr;
-  if (!zero_d) {
-    if (d) { c->ref2F((const cx<T>*)d, dF, (long)ds.P * B); dd = dF; }
-    else { CMBL_REQUIRE(ds.Bd == B, ERR_SHAPE, "dataset data batch size differs from nbatch"); dd = ds.d_h.template as<cx<T>>(); }
-  }
-  ds.gradientf(L, fF, dd, oF, B);
+  ds.gradientf(L, fF, zero_d ? nullptr : data_of(ds, d, dF, B), oF, B);
   c->F2ref(oF, (cx<T>*)out, (long)ds.P * B);
 }
 template <typename T>
 void do_cg_op(cmbl_dataset* dsh, cmbl_lensop* Lh, const void* d, const void* fstart, double tol, int maxit, void* f_out, double* hist, int* nit, int B) {
-  if (Lh->kind == LENSOP_FLOW) return do_cg<T>(dsh, static_cast<cmbl_flow*>(Lh->h), d, fstart, tol, maxit, f_out, hist, nit, B);
   Dataset<T>& ds = typed<Dataset<T>>(dsh); LensOps<T>& L = lensop_of<T>(Lh);
   Ctx<T>* c = ds.c;
   L.op_check(B);
   const long n = ds.fsize(B);
   ds.cvt.ensure(sizeof(cx<T>) * 3 * n);
   cx<T>* dF = ds.cvt.template as<cx<T>>(); cx<T>* sF = dF + n; cx<T>* oF = sF + n;
-  const cx<T>* dd;
-  if (d) { c->ref2F((const cx<T>*)d, dF, (long)ds.P * B); dd = dF; }
-  else { CMBL_REQUIRE(ds.Bd == B, ERR_SHAPE, "dataset data batch size differs from nbatch"); dd = ds.d_h.template as<cx<T>>(); }
+  const cx<T>* dd = data_of(ds, d, dF, B);
   const cx<T>* fs = nullptr;
   if (fstart) { c->ref2F((const cx<T>*)fstart, sF, (long)ds.P * B); fs = sF; }
   *nit = ds.wiener_cg(L, dd, fs, tol, maxit, oF, hist, B);
@@ -145,9 +111,7 @@ void do_grad_lp_op(cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void
   cx<T>* fF = ds.cvt.template as<cx<T>>(); cx<T>* dF = fF + n; cx<T>* gF = dF + n; cx<T>* pF = gF + n; cx<T>* gpF = pF + pl;
   c->ref2F((const cx<T>*)f, fF, (long)ds.P * B);
   c->ref2F((const cx<T>*)phi, pF, 1);
-  const cx<T>* dd;
-  if (d) { c->ref2F((const cx<T>*)d, dF, (long)ds.P * B); dd = dF; }
-  else { CMBL_REQUIRE(ds.Bd == B, ERR_SHAPE, "dataset data batch size differs from nbatch"); dd = ds.d_h.template as<cx<T>>(); }
+  const cx<T>* dd = data_of(ds, d, dF, B);
   ds.grad_logpdf(L, fF, pF, dd, lp, gf ? gF : nullptr, gphi ? gpF : nullptr, B, quirk != 0);
   if (gf) c->F2ref(gF, (cx<T>*)gf, (long)ds.P * B);
   if (gphi) c->F2ref(gpF, (cx<T>*)gphi, B);

@@ -2,8 +2,8 @@
 // entry points and the dispatch on a context's precision.  The build is split by explicit instantiation (lib.py builds the objects in parallel):
 //   api.hip                 extern "C" entry points, argument checks, error plumbing -- instantiates NO kernel and nothing of Flow<T>, Bilinear<T>,
 //                           PowerLens<T>, Projector<T>, Dataset<T> or Drivers<T> (tests/test_boundary.py reads the object's symbols)
-//   tu_main_{f32,f64}.hip   every body of CMBL_API_BODIES (api_body.hpp) and with them Ctx<T>, Flow<T>, Bilinear<T>, PowerLens<T>, Dataset<T>, Drivers<T>, their
-//                           vtables and their kernels
+//   tu_main_{f32,f64}.hip   every body of CMBL_API_BODIES (api_body.hpp) and with them Ctx<T>, Flow<T> (engine.hpp), Bilinear<T>, PowerLens<T>, Dataset<T>
+//                           (engine_dataset.hpp), Drivers<T> (drivers.hpp), their vtables and their kernels
 //   tu_gen_{f32,f64}.hip    the host side of the any-size transform launches (engine_gen.hpp) and the run-time-plan kernels k_gen_dft*
 //   tu_cty_{f32,f64}_{a,b}.hip   the compile-time-plan kernels of the column side and the plain transforms (engine_ct.hpp CtLaunchY: k_ct_dft,
 //                           k_ct_dftx, k_ct_flow_y, k_ct_delta_y, k_ct_adj_y), lengths of CMBL_CT_LIST_A / _B (kernels_ct.hpp)
@@ -18,6 +18,7 @@
 //     the handle with typed<Flow<T>>(L) etc., a static_cast).
 #pragma once
 #include "engine.hpp"
+#include "engine_dataset.hpp"
 #include "drivers.hpp"
 #include "engine_ud.hpp"
 #include "engine_cl.hpp"
@@ -63,8 +64,6 @@ namespace cmbl {
   X(T, do_dataset_create, (cmbl_dataset* h, int npol)) \
   X(T, do_bl_create, (cmbl_bilinear* h)) \
   X(T, do_pl_create, (cmbl_powerlens* h, int order, int kind)) \
-  X(T, do_gradf, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* f, const void* d, int zero_d, void* out, int B)) \
-  X(T, do_cg, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* d, const void* fstart, double tol, int maxit, void* f_out, double* hist, int* nit, int B)) \
   X(T, do_gradf_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void* d, int zero_d, void* out, int B)) \
   X(T, do_cg_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* d, const void* fstart, double tol, int maxit, void* f_out, double* hist, int* nit, int B)) \
   X(T, do_grad_lp_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void* phi, const void* d, double* lp, void* gf, void* gphi, int B, int quirk)) \

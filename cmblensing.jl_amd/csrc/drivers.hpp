@@ -5,7 +5,7 @@
 // Control flow on the host, every field operation one of the engine's launches; all fields in the internal F layout here (the C ABI
 // wrappers in api.hip convert at the edges).  Nothing new is computed on the device except two plane-wise helpers (sqrt, pinv).
 #pragma once
-#include "engine.hpp"
+#include "engine_dataset.hpp"
 
 namespace cmbl {
 

@@ -1,0 +1,487 @@
+// The data model on top of Ctx<T> and a lensing operator (LensOps<T>): Dataset<T> with its operators, the Wiener filter and the posterior
+// with its gradients.  Included by api_decl.hpp and drivers.hpp.
+#pragma once
+#include "engine.hpp"
+
+namespace cmbl {
+
+// =================================================================================================
+// Data model, Wiener filter, posterior   (src/dataset.jl, src/maximization.jl, src/numerical_algorithms.jl)
+enum OpId { OP_CF_INV = 0, OP_CN_INV, OP_B, OP_MF, OP_D, OP_D_INV, OP_PRECOND_INV, OP_CPHI_INV, OP_G_INV, OP_MPIX, OP_COUNT };
+
+struct DatasetApi {                        // what the C ABI (api.hip) holds of a dataset (see FlowApi)
+  double logdet_sum = 0;
+  virtual ~DatasetApi() = default;
+  virtual void set_op(int which, const void* planes, int nplanes) = 0;
+  virtual void set_data(const void* d_ref, int B) = 0;
+};
+
+template <typename T>
+struct Dataset : DatasetApi {
+  Ctx<T>* c;
+  int P;
+  struct Op { DevBuf buf; int nplanes = 0; const T* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; int kind = 0; };
+  Op ops[OP_COUNT];
+  DevBuf d_h; int Bd = 0;                  // data, F layout harmonic
+  // scratch
+  DevBuf t1, t2, t3, mp, mp2, xs, rs, zs, ps, aps, best, bb, phiF, gphi, dphi1, dphi2, fh, fhat, ftil, cvt;
+
+  Dataset(Ctx<T>* ctx, int npol) : c(ctx), P(npol) { CMBL_REQUIRE(npol >= 1 && npol <= 3, ERR_ARG, "npol must be 1, 2 or 3"); }
+
+  void set_op(int which, const void* planes, int nplanes) override {
+    CMBL_REQUIRE(which >= 0 && which < OP_COUNT, ERR_ARG, "bad operator id");
+    Op& o = ops[which];
+    if (which == OP_MPIX) {
+      CMBL_REQUIRE(nplanes == 1, ERR_ARG, "pixel mask is one map");
+      o.buf.ensure(sizeof(T) * c->npix());
+      CMBL_HIP(hipMemcpyAsync(o.buf.p, planes, sizeof(T) * c->npix(), hipMemcpyDeviceToDevice, c->stream));
+      o.nplanes = 1; o.d[0] = o.buf.template as<T>(); o.kind = 1;
+      return;
+    }
+    const bool s0 = (which == OP_CPHI_INV || which == OP_G_INV);
+    CMBL_REQUIRE(s0 ? nplanes == 1 : (nplanes == P || (P == 3 && nplanes == 5)), ERR_SHAPE, "wrong number of planes for this operator");
+    o.buf.ensure(sizeof(T) * nplanes * c->plane());
+    c->ref2F_real((const T*)planes, o.buf.template as<T>(), nplanes);
+    o.nplanes = nplanes; o.kind = (nplanes == 5) ? 2 : 1;
+    for (int k = 0; k < 5; ++k) o.d[k] = k < nplanes ? o.buf.template as<T>() + (size_t)k * c->plane() : nullptr;
+  }
+  const Op& op(int which) const {
+    CMBL_REQUIRE(ops[which].nplanes > 0, ERR_STATE, "a required dataset operator has not been set");
+    return ops[which];
+  }
+  bool has(int which) const { return ops[which].nplanes > 0; }
+  void apply(int which, const cx<T>* in, cx<T>* out, int B, bool transpose = false, bool in_qu = false, bool out_qu = false,
+             const cx<T>* z = nullptr, T alpha = 0, T beta = 1, int Pp = -1) {
+    const Op& o = op(which);
+    c->harm(in, out, Pp < 0 ? P : Pp, B, o.kind, o.d, transpose, in_qu, out_qu, z, alpha, beta);
+  }
+  void set_data(const void* d_ref, int B) override {
+    d_h.ensure(sizeof(cx<T>) * (long)P * B * c->plane());
+    c->ref2F((const cx<T>*)d_ref, d_h.template as<cx<T>>(), (long)P * B);
+    Bd = B;
+  }
+  long fsize(int B) const { return (long)P * B * c->plane(); }
+
+  // x (QU Fourier, F layout) <- rfft2(mask .* irfft2(x)): x pass, column kernel (c2r, mask, r2c in LDS), x pass
+  void pixel_mask(cx<T>* x, long sl) {
+    if (c->generic) {
+      mp.ensure(sizeof(T) * sl * c->npix());
+      c->F_to_map(x, mp.template as<T>(), sl); c->mask_mul(mp.template as<T>(), mp.template as<T>(), ops[OP_MPIX].d[0], sl); c->rfft2_F(mp.template as<T>(), x, sl);
+      return;
+    }
+    cx<T>* m = c->mixed_scratch(sl);
+    c->template x_pass<1>(x, m, sl); c->y_mask(m, m, ops[OP_MPIX].d[0], sl); c->template x_pass<0>(m, x, sl);
+  }
+  // x (harmonic F) -> M x = Mf * (Mpix * x) ; transpose: Mpix' * (Mf' * x)   (src/dataset.jl:279-285)
+  // qu: the pixel side of M is exchanged in QU Fourier (x comes in QU Fourier for M, goes out in QU Fourier for M'), so that the beam
+  // next to it does the basis change in its own launch instead of a launch of its own
+  void apply_M(cx<T>* x, int B, bool transpose, bool qu = false) {
+    const long sl = (long)P * B;
+    if (!has(OP_MPIX)) { apply(OP_MF, x, x, B, transpose, qu && !transpose, qu && transpose); return; }
+    if (!transpose) {
+      if (!qu) c->harm(x, x, P, B, 0, nullptr, false, false, true);        // -> QU Fourier
+      pixel_mask(x, sl);
+      apply(OP_MF, x, x, B, false, true, false);
+    } else {
+      apply(OP_MF, x, x, B, true, false, true);
+      pixel_mask(x, sl);
+      if (!qu) c->harm(x, x, P, B, 0, nullptr, false, true, false);
+    }
+  }
+
+  // ---- fused path (kernels_harm.hpp; power-of-two maps) ----------------------------------------------------------------------------
+  bool fused() const { return !c->generic && c->opts.fused_harm; }
+  OpRef<T> opref(int which, bool transpose = false) const {
+    const Op& o = op(which);
+    OpRef<T> r{};
+    for (int k = 0; k < 5; ++k) r.d[k] = o.d[k];
+    r.kind = o.kind; r.transpose = transpose ? 1 : 0;
+    return r;
+  }
+  template <typename Fn> void by_pol(Fn&& fn) const {
+    if (P == 1) fn(std::integral_constant<int, 1>{}); else if (P == 2) fn(std::integral_constant<int, 2>{}); else fn(std::integral_constant<int, 3>{});
+  }
+  DevBuf m1;                                 // mixed-layout scratch of the data-space part
+  // From rfft_y(L f) in `a_ftil` (mixed, left intact) to  w = scale * B'M' Cn^-1 (M B L f - d):  w in QU Fourier to `w_F` (F layout) and
+  // ifft_x(w) to L.H (mixed), ready for an adjoint / delta flow with h_ready.  Returns where the
+  // partial sums of (MBLf - d)' Cn^-1 (MBLf - d) were left.  value_only: stop after the quadratic form.  dd == nullptr: d = 0.   (src/dataset.jl:59-66,76-80)
+  // H: the mixed-layout buffer ifft_x(w) goes to (the flow's hbuf_ensure; unused when value_only)
+  DotOut data_space(cx<T>* H, const cx<T>* a_ftil, const cx<T>* dd, int dB, T scale, cx<T>* w_F, bool value_only, int B) {
+    const long sl = (long)P * B;
+    DotOut qn{};
+    by_pol([&](auto pp) {
+      constexpr int PP = decltype(pp)::value;
+      const ModeGeom<T> g = c->geom();
+      if (has(OP_MPIX)) {
+        m1.ensure(sizeof(cx<T>) * sl * c->mplane());
+        cx<T>* m = m1.template as<cx<T>>();
+        PwChain<T, PP> b1{g, {}, 1, 1, nullptr, T(0), nullptr, T(1)};
+        b1.ch.push(opref(OP_B));
+        c->template x_pw<PP, false>(a_ftil, m, b1, B);                                  // beam
+        c->y_mask(m, m, ops[OP_MPIX].d[0], sl);                                         // pixel mask
+        PwResid<T, PP> rs{g, {}, {}, opref(OP_CN_INV), dd, dB, T(1), nullptr};
+        rs.pre.push(opref(OP_MF)); rs.post.push(opref(OP_MF, true));
+        qn = c->template x_pw<PP, false>(m, value_only ? nullptr : m, rs, B, false, Ctx<T>::PART_QN);   // Fourier mask, residual, Cn^-1, quadratic form, Fourier mask'
+        if (value_only) return;
+        c->y_mask(m, m, ops[OP_MPIX].d[0], sl);                                         // pixel mask'
+        PwChain<T, PP> b2{g, {}, 1, 1, nullptr, T(0), w_F, scale};
+        b2.ch.push(opref(OP_B, true));
+        c->template x_pw<PP, false>(m, H, b2, B);                                       // beam', w stored, ifft_x(w) -> H
+      } else {
+        PwResid<T, PP> rs{g, {}, {}, opref(OP_CN_INV), dd, dB, scale, value_only ? nullptr : w_F};
+        rs.pre.push(opref(OP_B)); rs.pre.push(opref(OP_MF));
+        rs.post.push(opref(OP_MF, true)); rs.post.push(opref(OP_B, true));
+        qn = c->template x_pw<PP, false>(a_ftil, H, rs, B, false, Ctx<T>::PART_QN);
+      }
+    });
+    return qn;
+  }
+  // f (harmonic F) -> L f: leaves the lensed maps in `ftil` and rfft_y(L f) in L.A
+  void lens_from_harmonic(Flow<T>& L, const cx<T>* f_h, T* ftil, int B) {
+    const long sl = (long)P * B;
+    mp2.ensure(sizeof(T) * sl * c->npix());
+    cx<T>* a = L.abuf_ensure(L.A, sl);
+    by_pol([&](auto pp) {
+      constexpr int PP = decltype(pp)::value;
+      PwChain<T, PP> r{c->geom(), {}, 0, 1, nullptr, T(0), nullptr, T(1)};
+      c->template x_pw<PP, true>(f_h, a, r, B, true);                                   // EB -> QU, ifft_x, Hermitian rows projected
+    });
+    c->y_c2r(a, mp2.template as<T>(), sl);
+    L.flow_map(mp2.template as<T>(), ftil, P, B, false, true, true, &L.A);
+  }
+  // Y = L'B'M'Cn^-1 (d - M B L f)   (QU Fourier, F layout; the data part of gradientf_logpdf)
+  void model_adjoint(Flow<T>& L, const cx<T>* f_h, const cx<T>* dd, int dB, cx<T>* Y, int B) {
+    const long sl = (long)P * B;
+    ftil.ensure(sizeof(T) * sl * c->npix());
+    lens_from_harmonic(L, f_h, ftil.template as<T>(), B);
+    data_space(L.hbuf_ensure(sl), L.A.template as<cx<T>>(), dd, dB, T(-1), Y, false, B);
+    L.flow_adj_F(Y, Y, P, B, false, true);
+  }
+
+  // mu = M B L f : harmonic F in (f may be nullptr == 0) -> harmonic F out (t2); uses mp2 for maps
+  // `ftil_out`: where the lensed maps f~ = L f are left (default: the scratch mp2)
+  void mean(LensOps<T>& L, const cx<T>* f_h, cx<T>* out, int B, T* ftil_out = nullptr) {
+    const long sl = (long)P * B;
+    mp2.ensure(sizeof(T) * sl * c->npix());
+    c->harm(f_h, out, P, B, 0, nullptr, false, false, true);
+    c->F_to_map(out, mp2.template as<T>(), sl);
+    L.op_lens_F(mp2.template as<T>(), ftil_out, out, P, B);
+    apply(OP_B, out, out, B, false, true, true);                          // QU Fourier -> (EB) x beam -> QU Fourier
+    apply_M(out, B, false, true);
+  }
+
+  // gradientf_logpdf (src/dataset.jl:76-80): L'B'M'Cn^-1 (d - M B L f) - Cf^-1 f.  f_h == nullptr means f = 0;
+  // d_h == nullptr means d = 0.  All harmonic F layout.  out must not alias f_h.  A LenseFlow on a power-of-two map runs the fused form;
+  // any other operator with an adjoint (and f = 0) the composition around op_lens_F / op_adj_F
+  void gradientf(LensOps<T>& L, const cx<T>* f_h, const cx<T>* dd, cx<T>* out, int B) {
+    CMBL_REQUIRE(L.op_has_adjoint(), ERR_ARG, std::string(L.op_name()) + ": gradientf_logpdf / the Wiener filter need L', which the reference does not define for this operator");
+    const long n = fsize(B);
+    t2.ensure(sizeof(cx<T>) * n);
+    cx<T>* r = t2.template as<cx<T>>();
+    Flow<T>* flow = fused() ? L.as_flow() : nullptr;
+    if (f_h && flow) {
+      model_adjoint(*flow, f_h, dd, B, r, B);
+    } else {
+      if (f_h) {
+        mean(L, f_h, r, B);
+        if (dd) c->lincomb1((T*)r, (const T*)dd, (const T*)r, 1.0, -1.0, 2 * n / B, B);
+      } else {
+        CMBL_REQUIRE(dd != nullptr, ERR_ARG, "gradientf with f = 0 and d = 0 is identically zero");
+        CMBL_HIP(hipMemcpyAsync(r, dd, sizeof(cx<T>) * n, hipMemcpyDeviceToDevice, c->stream));
+      }
+      if (f_h && !dd) apply(OP_CN_INV, r, r, B, false, false, false, nullptr, 0, (T)-1);       // d = 0: the sign of -(M B L f) rides along
+      else apply(OP_CN_INV, r, r, B);
+      apply_M(r, B, true, true);
+      apply(OP_B, r, r, B, true, true, true);                              // QU Fourier -> (EB) x beam' -> QU Fourier
+      L.op_adj_F(r, r, P, B);
+    }
+    if (f_h) {
+      c->harm(r, r, P, B, 0, nullptr, false, true, false);                 // -> harmonic
+      apply(OP_CF_INV, f_h, out, B, false, false, false, r, (T)1, (T)-1);  // out = r - Cf^-1 f
+    } else {
+      c->harm(r, out, P, B, 0, nullptr, false, true, false);
+    }
+  }
+
+  // conjugate_gradient (src/numerical_algorithms.jl:73-134) driving argmaxf_logpdf (src/maximization.jl:17-42).
+  // a0 = gradientf(f=0,d=0) is identically zero for this linear model (all operators finite), so it is not evaluated.
+  // The scalars (res, alpha, beta, best residual, history, stop flag) live on the device (CgState): an iteration is enqueued
+  // without waiting for its reductions; the host reads the stop flag of iteration i-1 while iteration i runs.
+  DevBuf cg_scal, cg_hist, qdev, cg_rzfin;
+  int* cg_flag_host = nullptr;                 // pinned: [slot][up to 8 flags]
+  hipEvent_t cg_ev[2] = {nullptr, nullptr};
+  ~Dataset() {
+    if (cg_flag_host) (void)hipHostFree(cg_flag_host);
+    for (auto& e : cg_ev) if (e) (void)hipEventDestroy(e);
+  }
+  // What the two forms of the iteration share.  cg_begin: the vectors, the scalar block (`sd`; its ints follow nd doubles per slot), the
+  // pinned flags and their events, b = -gradientf(f=0, d), the start iterate x and r = b - A x.  cg_end: the best iterate, the history and
+  // the NaN check.  The flag blocks differ (CgScal: 6 ints, `done` and `better` by parity; CgState: 4 ints), so they are given as `nflag`
+  // ints at `flags` with the NaN flag at index i_nan and the length of the history at i_nh.
+  struct CgVecs { long n, nr; cx<T>*x, *r, *z, *p, *Ap, *bx, *b; double* sd; int* si; double* hist; };
+  CgVecs cg_begin(LensOps<T>& L, const cx<T>* dd, const cx<T>* fstart, int maxit, int nd, int B) {
+    CgVecs v;
+    v.n = fsize(B); v.nr = 2 * v.n / B;
+    DevBuf* const bufs[7] = {&xs, &rs, &zs, &ps, &aps, &best, &bb};
+    for (DevBuf* d : bufs) d->ensure(sizeof(cx<T>) * v.n);
+    v.x = xs.template as<cx<T>>(); v.r = rs.template as<cx<T>>(); v.z = zs.template as<cx<T>>(); v.p = ps.template as<cx<T>>();
+    v.Ap = aps.template as<cx<T>>(); v.bx = best.template as<cx<T>>(); v.b = bb.template as<cx<T>>();
+    CMBL_REQUIRE(B <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
+    cg_scal.ensure(sizeof(double) * nd * MAXBATCH + sizeof(int) * 8);
+    cg_hist.ensure(sizeof(double) * (size_t)maxit * B);
+    if (!cg_flag_host) {
+      CMBL_HIP(hipHostMalloc((void**)&cg_flag_host, sizeof(int) * 16, hipHostMallocDefault));
+      for (auto& e : cg_ev) CMBL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    v.sd = cg_scal.template as<double>(); v.si = reinterpret_cast<int*>(v.sd + nd * MAXBATCH); v.hist = cg_hist.template as<double>();
+    hipStream_t sm = c->stream;
+    std::vector<double> one(B, 1.0), mone(B, -1.0);
+    // b = -gradientf(f=0, d) = -L'B'M'Cn^-1 d
+    gradientf(L, nullptr, dd, v.b, B);
+    c->lincomb((T*)v.b, (T*)v.b, nullptr, mone.data(), nullptr, v.nr, B);
+    if (fstart) {
+      CMBL_HIP(hipMemcpyAsync(v.x, fstart, sizeof(cx<T>) * v.n, hipMemcpyDeviceToDevice, sm));
+      gradientf(L, v.x, nullptr, v.Ap, B);                                          // A x
+      c->lincomb((T*)v.r, (T*)v.b, (T*)v.Ap, one.data(), mone.data(), v.nr, B);     // r = b - A x
+    } else {
+      CMBL_HIP(hipMemsetAsync(v.x, 0, sizeof(cx<T>) * v.n, sm));
+      CMBL_HIP(hipMemcpyAsync(v.r, v.b, sizeof(cx<T>) * v.n, hipMemcpyDeviceToDevice, sm));
+    }
+    return v;
+  }
+  void cg_post_flags(int slot, const int* flags, int nflag) {
+    CMBL_HIP(hipMemcpyAsync(cg_flag_host + 8 * slot, flags, sizeof(int) * nflag, hipMemcpyDeviceToHost, c->stream));
+    CMBL_HIP(hipEventRecord(cg_ev[slot], c->stream));
+  }
+  const int* cg_wait_flags(int slot) { CMBL_HIP(hipEventSynchronize(cg_ev[slot])); return cg_flag_host + 8 * slot; }
+  int cg_end(const CgVecs& v, cx<T>* f_out, double* hist, const int* flags, int nflag, int i_nan, int i_nh, int B) {
+    hipStream_t sm = c->stream;
+    CMBL_HIP(hipMemcpyAsync(f_out, v.bx, sizeof(cx<T>) * v.n, hipMemcpyDeviceToDevice, sm));
+    int fl[8];
+    CMBL_HIP(hipMemcpyAsync(fl, flags, sizeof(int) * nflag, hipMemcpyDeviceToHost, sm));
+    CMBL_HIP(hipStreamSynchronize(sm));
+    const int nh = fl[i_nh];
+    CMBL_HIP(hipMemcpy(hist, v.hist, sizeof(double) * (size_t)nh * B, hipMemcpyDeviceToHost));
+    CMBL_REQUIRE(fl[i_nan] == 0, ERR_NAN, "NaN residual in conjugate gradient");
+    return nh;
+  }
+  // Fused form of the same iteration (a LenseFlow on a power-of-two map): per iteration the two flows, 7 launches between them (basis change + ifft_x,
+  // c2r, beam, mask, Fourier mask / Cn^-1 / Fourier mask', mask', beam' + ifft_x) and 3 after them (A p and p'Ap -> alpha; x, r, r'z ->
+  // beta and the stop test; p and the best iterate).  Every scalar is produced by the launch that produced its sum.
+  int wiener_cg_fused(Flow<T>& L, const cx<T>* dd, const cx<T>* fstart, double tol, int maxit, cx<T>* f_out, double* hist, int B) {
+    const CgVecs v = cg_begin(L, dd, fstart, maxit, 7, B);
+    cx<T>*x = v.x, *r = v.r, *p = v.p, *Y = v.z, *Ap = v.Ap, *bx = v.bx;
+    cg_rzfin.ensure(sizeof(double) * MAXBATCH);
+    CgScal st;
+    st.res = v.sd; st.best = v.sd + 2 * MAXBATCH;
+    st.hist = v.hist;
+    st.done = v.si; st.better = v.si + 2; st.nan = v.si + 4; st.nh = v.si + 5;
+    hipStream_t sm = c->stream;
+    const ModeGeom<T> g = c->geom();
+    const double sc = c->dot_scale();
+    by_pol([&](auto pp) {
+      constexpr int PP = decltype(pp)::value;
+      const DotOut o = c->pw_flat(PwCgStart<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, bx}, B, Ctx<T>::PART_CG_RZ);
+      CMBL_LAUNCH(c, K_CG, (k_cg_init<T>), dim3(1), 0, sm, st, o, sc, B);
+    });
+    cg_post_flags(0, st.done, 6);
+    int par = 0;
+    if (cg_wait_flags(0)[4] == 0) {                                         // a NaN start residual is reported below
+      for (int it = 2; it <= maxit; ++it) {
+        model_adjoint(L, p, nullptr, B, Y, B);                              // Y = -L'B'M'Cn^-1 M B L p
+        by_pol([&](auto pp) {
+          constexpr int PP = decltype(pp)::value;
+          const DotOut oA = c->pw_flat(PwCgAp<T, PP>{g, opref(OP_CF_INV), Y, p, Ap}, B, Ctx<T>::PART_CG_PAP);                // A p = Y - Cf^-1 p
+          const DotOut oR = c->pw_flat(PwCgXr<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, Ap, st, par, oA, sc}, B, Ctx<T>::PART_CG_RZ);   // alpha ; x, r
+          // beta, stop test ; p, best iterate.  Every block needs r'z of ALL slots (`all(res < bestres)`, :111): up to 16 slots it adds
+          // their partials itself in its prologue; beyond that one small launch finishes them first (O(B) instead of O(B^2) per block)
+          const double* rzf = nullptr;
+          if (B > 16) { double* const o1[1] = {cg_rzfin.as<double>()}; c->finish_parts(&oR, o1, 1, B); rzf = o1[0]; }
+          c->pw_flat(PwCgP<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, bx, st, par, tol, oR, sc, rzf}, B);
+        });
+        par ^= 1;
+        cg_post_flags(it & 1, st.done, 6);
+        if (it > 2 && cg_wait_flags((it - 1) & 1)[it & 1] != 0) break;      // previous iteration's flags: it left `done` at parity (it - 2) & 1
+      }
+    }
+    return cg_end(v, f_out, hist, st.done, 6, 4, 5, B);
+  }
+  int wiener_cg(LensOps<T>& L, const cx<T>* dd, const cx<T>* fstart, double tol, int maxit, cx<T>* f_out, double* hist, int B) {
+    if (Flow<T>* flow = fused() ? L.as_flow() : nullptr) return wiener_cg_fused(*flow, dd, fstart, tol, maxit, f_out, hist, B);
+    const CgVecs v = cg_begin(L, dd, fstart, maxit, 6, B);
+    const long n = v.n, nr = v.nr;
+    cx<T>*x = v.x, *r = v.r, *z = v.z, *p = v.p, *Ap = v.Ap, *bx = v.bx;
+    CgState st;
+    double* sd = v.sd;
+    st.res = sd; st.pAp = sd + MAXBATCH; st.res2 = sd + 2 * MAXBATCH; st.alpha = sd + 3 * MAXBATCH; st.beta = sd + 4 * MAXBATCH; st.best = sd + 5 * MAXBATCH;
+    st.hist = v.hist;
+    st.done = v.si; st.nan = v.si + 1; st.nh = v.si + 2; st.better = v.si + 3;
+    hipStream_t sm = c->stream;
+    const unsigned gx = (unsigned)std::min<long>((nr + NTP - 1) / NTP, 2048);
+    apply(OP_PRECOND_INV, r, z, B);
+    CMBL_HIP(hipMemcpyAsync(p, z, sizeof(cx<T>) * n, hipMemcpyDeviceToDevice, sm));
+    c->dot_F_dev(r, z, P, B, st.res);
+    CMBL_LAUNCH_NT(c, K_CG, 64, k_cg_start, dim3(1), 0, sm, st, B);
+    CMBL_HIP(hipMemcpyAsync(bx, x, sizeof(cx<T>) * n, hipMemcpyDeviceToDevice, sm));
+    cg_post_flags(0, st.done, 2);
+    if (cg_wait_flags(0)[1] == 0) {                                         // a NaN start residual is reported below
+      for (int it = 2; it <= maxit; ++it) {
+        gradientf(L, p, nullptr, Ap, B);
+        c->dot_F_dev(p, Ap, P, B, st.pAp);
+        CMBL_LAUNCH_NT(c, K_CG, 64, k_cg_alpha, dim3(1), 0, sm, st, B);
+        CMBL_LAUNCH(c, K_CG, (k_cg_xr<T>), dim3(gx, B), 0, sm, (T*)x, (T*)r, (const T*)p, (const T*)Ap, st, nr);
+        apply(OP_PRECOND_INV, r, z, B);
+        c->dot_F_dev(r, z, P, B, st.res2);
+        CMBL_LAUNCH_NT(c, K_CG, 64, k_cg_beta, dim3(1), 0, sm, st, B, tol);
+        CMBL_LAUNCH(c, K_CG, (k_cg_p<T>), dim3(gx, B), 0, sm, (T*)p, (const T*)z, st, nr);
+        CMBL_LAUNCH(c, K_CG, (k_cg_keep_best<T>), dim3(gx), 0, sm, (T*)bx, (const T*)x, st, 2 * n);
+        cg_post_flags(it & 1, st.done, 2);
+        if (it > 2 && cg_wait_flags((it - 1) & 1)[0] != 0) break;           // flags of the previous iteration
+      }
+    }
+    return cg_end(v, f_out, hist, st.done, 4, 1, 2, B);
+  }
+
+  // What grad_logpdf and the composed logpdf_mixed share, for nphi planes of phi (1, or one per slot):  z = M B L f - d with f~ = L f left in
+  // ftil;  w = Cn^-1 z,  Cf^-1 f  and  Cphi^-1 phi  with the three sets of quadratic forms in qdev, which stay on the device until read_logpdf.
+  // adjoint: w <- -B'M'Cn^-1 z = d/df~ (QU Fourier).  The prior terms are only handed out: each caller forms its own sums with them.
+  struct Posterior { cx<T>*w, *cfif, *cpip; };
+  Posterior posterior(LensOps<T>& L, const cx<T>* f_h, const cx<T>* phi_F, int nphi, const cx<T>* dd, bool adjoint, int B) {
+    const long n = fsize(B);
+    CMBL_REQUIRE(B <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
+    ftil.ensure(sizeof(T) * (long)P * B * c->npix()); t1.ensure(sizeof(cx<T>) * n); t2.ensure(sizeof(cx<T>) * n); t3.ensure(sizeof(cx<T>) * n);
+    gphi.ensure(sizeof(cx<T>) * nphi * c->plane()); qdev.ensure(sizeof(double) * 3 * MAXBATCH);
+    cx<T>*z = t1.template as<cx<T>>(), *cfif = t2.template as<cx<T>>(), *w = t3.template as<cx<T>>(), *cpip = gphi.template as<cx<T>>();
+    double* qd = qdev.template as<double>();
+    mean(L, f_h, z, B, ftil.template as<T>());                              // leaves f~ = L f in ftil
+    c->lincomb1((T*)z, (const T*)z, (const T*)dd, 1.0, -1.0, 2 * n / B, B);
+    apply(OP_CN_INV, z, w, B);                c->dot_F_dev(z, w, P, B, qd + 2 * MAXBATCH);
+    apply(OP_CF_INV, f_h, cfif, B);           c->dot_F_dev(f_h, cfif, P, B, qd);
+    apply(OP_CPHI_INV, phi_F, cpip, nphi, false, false, false, nullptr, 0, 1, 1);
+    c->dot_F_dev(phi_F, cpip, 1, nphi, qd + MAXBATCH);
+    if (adjoint) {
+      apply_M(w, B, true, true);
+      apply(OP_B, w, w, B, true, true, true, nullptr, 0, (T)-1);
+    }
+    return {w, cfif, cpip};
+  }
+  // logpdf per slot from the three sets of sums in qdev, read back ONCE, after everything else of the call has been enqueued (a read-back
+  // per term drained the stream three times in the middle of a gradient evaluation).  phi_stride: 1 with a phi per slot, 0 with one phi.
+  // A NaN logpdf is a VALUE, not an error: MAP_joint's line search penalises it (src/maximization.jl:194-199) and hmc_step
+  // rejects the proposal (log(rand()) < NaN is false, src/sampling.jl:414), so it must reach the caller.
+  void read_logpdf(double* lp, int B, int phi_stride) {
+    double q[3 * MAXBATCH];
+    CMBL_HIP(hipMemcpyAsync(q, qdev.template as<double>(), sizeof(double) * 3 * MAXBATCH, hipMemcpyDeviceToHost, c->stream));
+    CMBL_HIP(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < B; ++i) lp[i] = -0.5 * (q[i] + q[MAXBATCH + i * phi_stride] + q[2 * MAXBATCH + i] + logdet_sum);
+  }
+
+  // logpdf(ds; f, phi) (src/dataset.jl:59-66) per batch slot and, where asked for, its gradient with respect to f (harmonic) and phi (B planes,
+  // F layout) at once, for any operator whose phi has been set from `phi_F` (one plane):  z = M B L f - d;  w = -B'M'Cn^-1 z;
+  // grad_f = L' w - Cf^-1 f;  grad_phi = pullback(L f)(w) - Cphi^-1 phi -- what gradient(phi -> logpdf(ds; f, phi), phi) of MAP_marg evaluates
+  // (src/maximization.jl:307).  One forward lens and one pass through data space serve the value and both gradients.
+  void grad_logpdf(LensOps<T>& L, const cx<T>* f_h, const cx<T>* phi_F, const cx<T>* dd, double* lp, cx<T>* gf_h, cx<T>* gphi_F, int B, bool quirk) {
+    const long n = fsize(B), pl = c->plane();
+    CMBL_REQUIRE(!gf_h || L.op_has_adjoint(), ERR_ARG, std::string(L.op_name()) + ": the gradient with respect to f needs L', which the reference does not define for this operator");
+    CMBL_REQUIRE(!gphi_F || L.op_has_pullback(), ERR_ARG, std::string(L.op_name()) + ": the reference defines no pullback of L * f with respect to phi for this operator");
+    dphi1.ensure(sizeof(cx<T>) * B * pl);
+    const Posterior q = posterior(L, f_h, phi_F, 1, dd, gf_h || gphi_F, B);
+    cx<T>* w = q.w;
+    if (gphi_F) {
+      L.op_pullback(ftil.template as<T>(), w, dphi1.template as<cx<T>>(), P, B, quirk);
+      for (int b = 0; b < B; ++b) c->lincomb1((T*)(gphi_F + b * pl), (const T*)(dphi1.template as<cx<T>>() + b * pl), (const T*)q.cpip, 1.0, -1.0, 2 * pl, 1);
+    } else if (gf_h) L.op_adj_F(w, w, P, B);
+    if (gf_h) {
+      c->harm(w, w, P, B, 0, nullptr, false, true, false);                  // -> harmonic
+      c->lincomb1((T*)gf_h, (const T*)w, (const T*)q.cfif, 1.0, -1.0, 2 * n / B, B);
+    }
+    read_logpdf(lp, B, 0);
+  }
+
+  // logpdf(Mixed(ds); f°, phi°) and optionally its gradient.  fo: map (reference layout == internal), phio: F layout S0.
+  // gfo (map) / gphio (F) may be nullptr for value only.
+  // Fused form (power-of-two maps).  Launches outside the four flows: phi prior (1), precompute (4), the y pass of f° (1), unmix + Cf^-1
+  // + its quadratic form + ifft_x (1), c2r (1), the data-space part (5 with a pixel mask, 1 without), D'^-1 between the delta flows (1),
+  // per delta flow the first d/dx pass and the delta-phi epilogue (1 + 3), the final irfft2 (2): 25 with a pixel mask.
+  void logpdf_mixed_fused(Flow<T>& L, const T* fo, const cx<T>* phio_F, double* lp, T* gfo, cx<T>* gphio_F, int B, bool quirk) {
+    const long sl = (long)P * B, n = fsize(B), np = c->npix(), pl = c->plane();
+    phiF.ensure(sizeof(cx<T>) * B * pl); fhat.ensure(sizeof(T) * sl * np); ftil.ensure(sizeof(T) * sl * np);
+    fh.ensure(sizeof(cx<T>) * n); t2.ensure(sizeof(cx<T>) * n); t3.ensure(sizeof(cx<T>) * n);
+    gphi.ensure(sizeof(cx<T>) * B * pl); dphi1.ensure(sizeof(cx<T>) * B * pl);
+    mp2.ensure(sizeof(T) * sl * np);
+    cx<T>*phi = phiF.template as<cx<T>>(), *f_h = fh.template as<cx<T>>(), *w = t3.template as<cx<T>>(), *cfif = t2.template as<cx<T>>();
+    cx<T>* cpip = gphi.template as<cx<T>>();
+    CMBL_REQUIRE(B <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
+    qdev.ensure(sizeof(double) * 3 * MAXBATCH);
+    double* qd = qdev.template as<double>();
+    // phi = G \ phi° ; Cphi^-1 phi ; phi' Cphi^-1 phi
+    DotOut parts[3];
+    parts[1] = c->pw_flat(PwPhiPrior<T>{c->lam.template as<T>(), pl, op(OP_G_INV).d[0], op(OP_CPHI_INV).d[0], phio_F, phi, cpip}, B, Ctx<T>::PART_QP);
+    L.set_phi_F(phi, B);
+    // fhat = L \ f° (its y transform stays in A3) ; f = D \ fhat ; Cf^-1 f ; f' Cf^-1 f ; the y-transformed f goes straight into the forward flow
+    L.flow_map(fo, fhat.template as<T>(), P, B, true, false, true, &L.A3);
+    cx<T>* a = L.abuf_ensure(L.A, sl);
+    by_pol([&](auto pp) {
+      constexpr int PP = decltype(pp)::value;
+      parts[0] = c->template x_pw<PP, false>(L.A3.template as<cx<T>>(), a, PwUnmixPrior<T, PP>{c->geom(), opref(OP_D_INV), opref(OP_CF_INV), f_h, cfif}, B, true, Ctx<T>::PART_QF);
+    });
+    c->y_c2r(a, mp2.template as<T>(), sl);
+    L.flow_map(mp2.template as<T>(), ftil.template as<T>(), P, B, false, true, true, &L.A);       // f~ = L f in ftil, rfft_y(f~) in A
+    // z = M B L f - d ; z' Cn^-1 z ; w = -B'M'Cn^-1 z  (QU Fourier) with ifft_x(w) ready in L.H
+    parts[2] = data_space(gfo ? L.hbuf_ensure(sl) : nullptr, L.A.template as<cx<T>>(), d_h.template as<cx<T>>(), Bd, T(-1), w, gfo == nullptr, B);
+    double* const outs[3] = {qd, qd + MAXBATCH, qd + 2 * MAXBATCH};
+    c->finish_parts(parts, outs, 3, B);
+    if (!gfo) { read_logpdf(lp, B, 1); return; }
+    // pullback through f~ = L f : delta flow t 1->0 from (f~, w, 0)
+    L.flow_delta(ftil.template as<T>(), w, dphi1.template as<cx<T>>(), P, B, true, quirk, true, &L.A, true);
+    // g_f = df1 - Cf^-1 f (harmonic) ; d/dfhat = D' \ g_f -> QU Fourier, with its ifft_x in L.H
+    by_pol([&](auto pp) {
+      constexpr int PP = decltype(pp)::value;
+      PwChain<T, PP> ch{c->geom(), {}, 1, 1, cfif, T(-1), w, T(1)};
+      ch.ch.push(opref(OP_D_INV, true));
+      c->template x_pw<PP, true>(w, L.hbuf_ensure(sl), ch, B);
+    });
+    // pullback through fhat = L \ f° : delta flow t 0->1 from (fhat, w, 0); the epilogue forms d/dphi° = G' \ (dphi1 + dphi2 - Cphi^-1 phi)
+    const DphiTail<T> tail{dphi1.template as<cx<T>>(), cpip, op(OP_G_INV).d[0]};
+    L.flow_delta(fhat.template as<T>(), w, gphio_F, P, B, false, quirk, true, &L.A3, true, &tail);
+    c->F_to_map(w, gfo, sl);                                                // d/df° in f°'s basis (QU map)
+    read_logpdf(lp, B, 1);
+  }
+  void logpdf_mixed(Flow<T>& L, const T* fo, const cx<T>* phio_F, double* lp, T* gfo, cx<T>* gphio_F, int B, bool quirk) {
+    CMBL_REQUIRE(Bd == B, ERR_SHAPE, "dataset data batch size differs from nbatch");
+    if (fused()) return logpdf_mixed_fused(L, fo, phio_F, lp, gfo, gphio_F, B, quirk);
+    const long sl = (long)P * B, n = fsize(B), np = c->npix(), pl = c->plane();
+    phiF.ensure(sizeof(cx<T>) * B * pl); fhat.ensure(sizeof(T) * sl * np); fh.ensure(sizeof(cx<T>) * n);
+    dphi1.ensure(sizeof(cx<T>) * B * pl); dphi2.ensure(sizeof(cx<T>) * B * pl);
+    cx<T>*phi = phiF.template as<cx<T>>(), *f_h = fh.template as<cx<T>>();
+    // phi = G \ phi°
+    apply(OP_G_INV, phio_F, phi, B, false, false, false, nullptr, 0, 1, 1);
+    L.set_phi_F(phi, B);
+    // fhat = L \ f° ; f = D \ fhat
+    L.flow_map(fo, fhat.template as<T>(), P, B, true);
+    c->rfft2_F(fhat.template as<T>(), f_h, sl);
+    apply(OP_D_INV, f_h, f_h, B, false, true, false);
+    // z = M B L f - d ; the quadratic forms ; with a gradient, d/df~ = -B'M'Cn^-1 z -> QU Fourier
+    const Posterior q = posterior(L, f_h, phi, B, d_h.template as<cx<T>>(), gfo != nullptr, B);
+    cx<T>*w = q.w, *cfif = q.cfif, *cpip = q.cpip;
+    if (!gfo) { read_logpdf(lp, B, 1); return; }
+    // pullback through f~ = L f : delta flow t 1->0 from (f~, w, 0)
+    L.flow_delta(ftil.template as<T>(), w, dphi1.template as<cx<T>>(), P, B, true, quirk);
+    // g_f = df1 - Cf^-1 f   (harmonic) ; then d/dfhat = D' \ g_f  -> QU Fourier
+    c->harm(w, w, P, B, 0, nullptr, false, true, false);
+    c->lincomb1((T*)w, (const T*)w, (const T*)cfif, 1.0, -1.0, 2 * n / B, B);
+    apply(OP_D_INV, w, w, B, true, false, true);
+    // pullback through fhat = L \ f° : delta flow t 0->1 from (fhat, w, 0)
+    L.flow_delta(fhat.template as<T>(), w, dphi2.template as<cx<T>>(), P, B, false, quirk);
+    // d/df° in f°'s basis (QU map)
+    c->F_to_map(w, gfo, sl);
+    // g_phi = dphi1 + dphi2 - Cphi^-1 phi ; d/dphi° = G' \ g_phi
+    cx<T>* g = dphi1.template as<cx<T>>();
+    c->lincomb1((T*)g, (const T*)g, (const T*)dphi2.p, 1.0, 1.0, 2 * pl, B);
+    c->lincomb1((T*)g, (const T*)g, (const T*)cpip, 1.0, -1.0, 2 * pl, B);
+    apply(OP_G_INV, g, gphio_F, B, true, false, false, nullptr, 0, 1, 1);
+    read_logpdf(lp, B, 1);
+  }
+};
+
+}  // namespace cmbl

@@ -7,10 +7,14 @@
 
 namespace cmbl {
 
+template <typename T> struct Flow;
+
 template <typename T>
 struct LensOps {
   virtual ~LensOps() = default;
   virtual const char* op_name() const = 0;
+  // the LenseFlow behind this operator, for the fused forms of Dataset<T> that only it has; nullptr for every other operator
+  virtual Flow<T>* as_flow() { return nullptr; }
   // the operator has its phi (ERR_STATE otherwise) and takes B batch slots of f against it (ERR_SHAPE otherwise)
   virtual void op_check(int B) const = 0;
   // phi in the ABI's layout (basis MAP / FOURIER / HARMONIC), nb planes; the operators that refuse a batched phi fail with ERR_SHAPE

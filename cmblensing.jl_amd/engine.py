@@ -981,10 +981,7 @@ class BaseDataSet(_Handle):
         B = f.arr.shape[0]
         out = self.proj.empty(HARMONIC, self.P, B)
         dd = None if d is None else d.to(HARMONIC).arr
-        if not isinstance(L, LenseFlow):
-            check(self.lib.cmbl_gradientf_logpdf_op(self._h, L._view(), _ptr(f.arr), _ptr(dd), 1 if zero_d else 0, _ptr(out), B))
-            return Field(self.proj, out, HARMONIC)
-        check(self.lib.cmbl_gradientf_logpdf(self._h, L._h, _ptr(f.arr), _ptr(dd), 1 if zero_d else 0, _ptr(out), B))
+        check(self.lib.cmbl_gradientf_logpdf_op(self._h, L._view(), _ptr(f.arr), _ptr(dd), 1 if zero_d else 0, _ptr(out), B))
         return Field(self.proj, out, HARMONIC)
 
     def argmaxf_logpdf(self, phi, d=None, fstart=None, tol=1e-1, nsteps=500):
@@ -997,12 +994,8 @@ class BaseDataSet(_Handle):
         hist = (ctypes.c_double * (nsteps * B))()
         nit = ctypes.c_int(0)
         fs = None if fstart is None else fstart.to(HARMONIC).arr
-        if not isinstance(L, LenseFlow):
-            check(self.lib.cmbl_wiener_cg_op(self._h, L._view(), _ptr(dd.arr), _ptr(fs), float(tol), int(nsteps), _ptr(out),
-                                             hist, ctypes.byref(nit), B))
-        else:
-            check(self.lib.cmbl_wiener_cg(self._h, L._h, _ptr(dd.arr), _ptr(fs), float(tol), int(nsteps), _ptr(out),
-                                          hist, ctypes.byref(nit), B))
+        check(self.lib.cmbl_wiener_cg_op(self._h, L._view(), _ptr(dd.arr), _ptr(fs), float(tol), int(nsteps), _ptr(out),
+                                         hist, ctypes.byref(nit), B))
         h = np.array(hist[: nit.value * B]).reshape(nit.value, B)
         return Field(self.proj, out, HARMONIC), [(i + 1, h[i]) for i in range(nit.value)]
 

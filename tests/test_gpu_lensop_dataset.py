@@ -270,14 +270,14 @@ def test_lenseflow_view_runs_the_old_entry_points(prec, case):
     F, f, phi, d = fields(C, sd, case)
     B = f.arr.shape[0]
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-    want = ds.gradientf_logpdf(f, phi).arr
+    want = ds.gradientf_logpdf(f, phi).arr                                     # cmbl_gradientf_logpdf_op through the view ...
     got = p.empty(C.HARMONIC, ds.P, B)
-    ok(ds.lib.cmbl_gradientf_logpdf_op(ds._h, ds.L._view(), ptr(f.arr), None, 0, ptr(got), B))
+    ok(ds.lib.cmbl_gradientf_logpdf(ds._h, ds.L._h, ptr(f.arr), None, 0, ptr(got), B))      # ... and the flow-typed symbol
     assert torch.equal(got, want)
-    fw, h = ds.argmaxf_logpdf(phi, tol=0.0, nsteps=6)
+    fw, h = ds.argmaxf_logpdf(phi, tol=0.0, nsteps=6)                          # cmbl_wiener_cg_op
     got = p.empty(C.HARMONIC, ds.P, B)
     hist, nit = (ctypes.c_double * (6 * B))(), ctypes.c_int(0)
-    ok(ds.lib.cmbl_wiener_cg_op(ds._h, ds.L._view(), ptr(d.arr), None, 0.0, 6, ptr(got), hist, ctypes.byref(nit), B))
+    ok(ds.lib.cmbl_wiener_cg(ds._h, ds.L._h, ptr(d.arr), None, 0.0, 6, ptr(got), hist, ctypes.byref(nit), B))
     assert torch.equal(got, fw.arr) and nit.value == 6
     assert np.array_equal(np.array(hist[:6 * B]).reshape(6, B), hist_array(h))
     # ... and the one call for value and both gradients agrees with the composition LenseFlow keeps in Python

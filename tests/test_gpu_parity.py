@@ -366,6 +366,26 @@ def test_logpdf_mixed_and_gradient(prec, pol, Nside, scale32=1.0):
         close(("grad ϕ°", quirk), gp_g.arr.cpu().numpy(), gp, 6e-6 * s32 if prec == "f32" else 3e-9)               # 2.0e-6
 
 
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_composed_posterior_on_a_power_of_two_map(prec, monkeypatch):
+    """Option "fused_harm" off: pixel_mask, gradientf, wiener_cg and logpdf_mixed run their composed (unfused) forms on a power-of-two map,
+    which otherwise run at any-size shapes only.  Same fields, same oracle and the same class bounds as the two tests it calls (measured at
+    this shape: every comparison at most 0.35 of its bound; the largest is the fp32 8-step CG iterate, 1.4e-6 against 4e-6)."""
+    monkeypatch.setenv("CMBL_NO_FUSED_HARM", "1")   # read when the context is created
+    test_dataset_gradientf_and_wiener(prec, "P", (64, 128), True)
+    test_logpdf_mixed_and_gradient(prec, "P", (64, 128))
+    # the composed branch really ran: a gradient call launches no fused row pass (kernel class x_harm, which only the fused forms use)
+    C, so, sd = _dataset_pair(prec, "P", (64, 128))
+    ds, p = sd["ds"], sd["proj"]
+    fo, po = ds.mix(sd["f"], sd["phi"])
+    p.prof_enable()
+    p.prof_reset()
+    ds.gradient_logpdf_mixed(fo, po)
+    table = p.prof_table()
+    p.prof_enable(False)
+    assert "harm_apply" in table and "x_harm" not in table, sorted(table)
+
+
 def test_errors_are_status_codes():
     C = _pkg()
     with pytest.raises(C.CmblError) as e:
