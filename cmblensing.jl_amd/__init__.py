@@ -10,7 +10,7 @@ from .engine import (ProjLambert, LenseFlow, BilinearLens, PowerLens, Taylens, a
                      FLOW_FWD, FLOW_INV, FLOW_ADJ, FLOW_INVADJ, reference_exact, ud_grade, pixwin, UD_MAP, UD_FOURIER,
                      get_Cl, get_Dl, get_l4Cl, get_rhol, cov_to_Cl, make_mask)
 from .equirect import (ProjEquiRect, EquiRectField, BlockDiagEquiRect, AZFOURIER, Cl_to_Beam, Cl_to_Cov, simulate, equirect_geometry,   # noqa: F401
-                       blocks_from_ref, blocks_to_ref)
+                       blocks_from_ref, blocks_to_ref, EquiRectDataSet)
 from .healpix import (ProjHealpix, HealpixField, HealpixMap, Projector, project, pix2ang_ring, npix2nside)   # noqa: F401
 from .sim import (Cls, load_sim, noise_cls, beam_cls, lowpass, cl_to_2d, HarmOp, border_mask)   # noqa: F401
 from .chains import partition_chains, chain_seed, gather_chain_values, allreduce_sum   # noqa: F401

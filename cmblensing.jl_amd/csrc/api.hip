@@ -682,6 +682,55 @@ int cmbl_equirect_block_solve(cmbl_ctx* ctx, const void* A, int a_complex, int n
   });
 }
 
+// ---- NoLensingDataSet on ProjEquiRect (engine_equirect_ds.hpp) ---------------------------------------------------------------
+int cmbl_eqds_create(cmbl_ctx* ctx, int npol, cmbl_eqds** out) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(out);
+    auto h = std::make_unique<cmbl_eqds>();
+    h->ctx = ctx;
+    BY_DTYPE(ctx, do_eqds_create, h.get(), npol);
+    *out = h.release();
+  });
+}
+int cmbl_eqds_destroy(cmbl_eqds* ds) { return guard([&] { delete ds; }); }
+int cmbl_eqds_set_block_op(cmbl_eqds* ds, int which, const void* blocks_dev, int blocks_complex, int n) {
+  return guard([&] { NOTNULL(ds); ds->p->set_block_op(which, blocks_dev, blocks_complex != 0, n); });
+}
+int cmbl_eqds_set_pixel_op(cmbl_eqds* ds, int which, const void* map_dev, int nplanes) {
+  return guard([&] { NOTNULL(ds); ds->p->set_pixel_op(which, map_dev, nplanes); });
+}
+int cmbl_eqds_set_logdet(cmbl_eqds* ds, double v) { return guard([&] { NOTNULL(ds); ds->p->logdet_sum = v; }); }
+int cmbl_eqds_mean(cmbl_eqds* ds, const void* f, void* d_out, int B) {
+  return guard([&] { NOTNULL(ds); NOTNULL(f); NOTNULL(d_out); ds->p->mean(f, d_out, B); });
+}
+int cmbl_eqds_gradientf_logpdf(cmbl_eqds* ds, const void* f, const void* d, void* out, int B) {
+  return guard([&] {
+    NOTNULL(ds); NOTNULL(out);
+    CMBL_REQUIRE(out != f, ERR_ARG, "eqds_gradientf_logpdf: out must not alias f");
+    ds->p->gradientf(f, d, out, B);
+  });
+}
+int cmbl_eqds_logpdf(cmbl_eqds* ds, const void* f, const void* d, double* lp, int B) {
+  return guard([&] { NOTNULL(ds); NOTNULL(f); NOTNULL(d); NOTNULL(lp); ds->p->logpdf(f, d, lp, B); });
+}
+int cmbl_eqds_wiener_cg(cmbl_eqds* ds, const void* d, const void* fstart, double tol, int maxit, void* f_out, double* hist, int* nit, int B) {
+  return guard([&] {
+    NOTNULL(ds); NOTNULL(d); NOTNULL(f_out); NOTNULL(hist); NOTNULL(nit);
+    CMBL_REQUIRE(maxit >= 1, ERR_ARG, "eqds_wiener_cg: maxit >= 1");
+    *nit = ds->p->wiener_cg(d, fstart, tol, maxit, f_out, hist, B);
+  });
+}
+int cmbl_equirect_field_dot(cmbl_ctx* ctx, int basis, const void* a, const void* b, int npol, int B, double* out_host) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(a); NOTNULL(b); NOTNULL(out_host);
+    CMBL_REQUIRE(basis == CMBL_MAP || basis == CMBL_AZFOURIER, ERR_ARG, "equirect_field_dot: the bases are CMBL_MAP and CMBL_AZFOURIER");
+    CMBL_REQUIRE(npol == 1 || npol == 2, ERR_ARG, "equirect_field_dot: npol must be 1 or 2");
+    CMBL_REQUIRE(npol == 1 || ctx->p->Nx % 2 == 0, ERR_SHAPE, "equirect_field_dot: QUAzFourier needs an even Nx");
+    CMBL_REQUIRE(B >= 1 && B <= 65535, ERR_SHAPE, "equirect_field_dot: nbatch must lie in [1, 65535]");
+    BY_DTYPE(ctx, do_eq_field_dot, ctx, basis, a, b, npol, B, out_host);
+  });
+}
+
 // ---- HEALPix <-> Cartesian projection (src/proj_healpix.jl) ------------------------------------------------------------------
 int cmbl_healpix_pix2ang_host(int nside, long first, long n, double* theta, double* phi) {
   return guard([&] {

@@ -264,5 +264,7 @@ template <typename T> void do_eq_svd(cmbl_ctx* ctx, const void* blocks, bool cpl
 template <typename T> void do_eq_logabsdet(cmbl_ctx* ctx, const void* blocks, bool cplx, int n, double* out) { equirect_block_logabsdet<T>(C<T>(ctx), blocks, cplx, n, out); }
 template <typename T> void do_eq_solve(cmbl_ctx* ctx, const void* A, bool acplx, int n, int side, const void* rhs, bool rcplx, int kind, void* out, int B) { equirect_block_solve<T>(C<T>(ctx), A, acplx, n, side, rhs, rcplx, kind, out, B); }
 template <typename T> void do_eq_cov(cmbl_ctx* ctx, const double* tspan, const double* pspan, int pol, int lmax, const double* cl_a, const double* cl_b, int ngrid, void* blocks) { equirect_cov<T>(C<T>(ctx), tspan, pspan, pol, lmax, cl_a, cl_b, ngrid, blocks); }
+template <typename T> void do_eqds_create(cmbl_eqds* h, int npol) { h->p = std::make_unique<EqDataset<T>>(C<T>(h->ctx), npol); }
+template <typename T> void do_eq_field_dot(cmbl_ctx* ctx, int basis, const void* a, const void* b, int npol, int B, double* out) { equirect_field_dot<T>(C<T>(ctx), basis, a, b, npol, B, out); }
 
 }  // namespace cmbl

@@ -1,7 +1,7 @@
 // What api.hip (the entry points) and the per-precision translation units share: the handle structs, the list of the typed bodies behind the
 // entry points and the dispatch on a context's precision.  The build is split by explicit instantiation (lib.py builds the objects in parallel):
 //   api.hip                 extern "C" entry points, argument checks, error plumbing -- instantiates NO kernel and nothing of Flow<T>, Bilinear<T>,
-//                           PowerLens<T>, Projector<T>, Dataset<T> or Drivers<T> (tests/test_boundary.py reads the object's symbols)
+//                           PowerLens<T>, Projector<T>, Dataset<T>, EqDataset<T> or Drivers<T> (tests/test_boundary.py reads the object's symbols)
 //   tu_main_{f32,f64}.hip   every body of CMBL_API_BODIES (api_body.hpp) and with them Ctx<T>, Flow<T> (engine.hpp), Bilinear<T>, PowerLens<T>, Dataset<T>
 //                           (engine_dataset.hpp), Drivers<T> (drivers.hpp), their vtables and their kernels
 //   tu_gen_{f32,f64}.hip    the host side of the any-size transform launches (engine_gen.hpp) and the run-time-plan kernels k_gen_dft*
@@ -12,7 +12,7 @@
 //   tu_small_{f32,f64}.hip  the one-launch flows of small maps (engine_small.hpp: k_small_flow, k_small_adj)
 // An entry point reaches typed code in two ways only, and neither makes api.hip instantiate a member of a typed class (members defined in class
 // are inline, and an explicit instantiation DECLARATION does not stop inline functions from being instantiated -- [temp.explicit]/10):
-//   * a virtual member of the precision-free base its handle owns (CtxBase, FlowApi, DatasetApi, BilinearApi, PowerLensApi, ProjectorApi): set_phi, apply, grad, ... and the
+//   * a virtual member of the precision-free base its handle owns (CtxBase, FlowApi, DatasetApi, EqDatasetApi, BilinearApi, PowerLensApi, ProjectorApi): set_phi, apply, grad, ... and the
 //     destructors.  The typed objects are made by the creators below, so their vtables are emitted in tu_main_* alone.
 //   * BY_DTYPE(ctx, do_x, args...): a body of the list below, for what takes typed pointers or needs the typed object (which it gets back from
 //     the handle with typed<Flow<T>>(L) etc., a static_cast).
@@ -28,6 +28,7 @@
 #include "engine_equirect.hpp"
 #include "engine_equirect_cov.hpp"
 #include "engine_equirect_factor.hpp"
+#include "engine_equirect_ds.hpp"
 #include "engine_healpix.hpp"
 #include "engine_nfft.hpp"
 #include "../../include/cmblens.h"
@@ -40,6 +41,7 @@ struct cmbl_powerlens { cmbl_ctx* ctx; std::unique_ptr<cmbl::PowerLensApi> p; };
 enum { LENSOP_FLOW = 0, LENSOP_BILINEAR = 1, LENSOP_POWERLENS = 2 };
 struct cmbl_lensop { cmbl_ctx* ctx; int kind; void* h; };                    // non-owning view: h is the cmbl_flow / cmbl_bilinear / cmbl_powerlens of `kind`
 struct cmbl_projector { cmbl_ctx* ctx; std::unique_ptr<cmbl::ProjectorApi> p; };
+struct cmbl_eqds { cmbl_ctx* ctx; std::unique_ptr<cmbl::EqDatasetApi> p; };
 struct cmbl_dataset {
   cmbl_ctx* ctx; std::unique_ptr<cmbl::DatasetApi> p;
   std::map<const cmbl::FlowApi*, std::shared_ptr<void>> drv;                 // driver scratch (a Drivers<T>, deleter and all) per (dataset, flow) pair
@@ -85,6 +87,8 @@ namespace cmbl {
   X(T, do_eq_svd, (cmbl_ctx* ctx, const void* blocks, bool cplx, int n, double rtol, void* out_sqrt, void* out_pinv, double* sv, int* sweeps)) \
   X(T, do_eq_logabsdet, (cmbl_ctx* ctx, const void* blocks, bool cplx, int n, double* out)) \
   X(T, do_eq_solve, (cmbl_ctx* ctx, const void* A, bool acplx, int n, int side, const void* rhs, bool rcplx, int kind, void* out, int B)) \
+  X(T, do_eqds_create, (cmbl_eqds* h, int npol)) \
+  X(T, do_eq_field_dot, (cmbl_ctx* ctx, int basis, const void* a, const void* b, int npol, int B, double* out)) \
   X(T, do_projector_create, (cmbl_projector* h, int nside, int kind, const double* params, int method))
 
 #define CMBL_API_DECLARE(T, name, params) template <typename T> void name params;

@@ -9,6 +9,30 @@ namespace cmbl {
 // Data model, Wiener filter, posterior   (src/dataset.jl, src/maximization.jl, src/numerical_algorithms.jl)
 enum OpId { OP_CF_INV = 0, OP_CN_INV, OP_B, OP_MF, OP_D, OP_D_INV, OP_PRECOND_INV, OP_CPHI_INV, OP_G_INV, OP_MPIX, OP_COUNT };
 
+// The host's view of a CG's device-resident flags, shared by every solver that keeps its scalars on the device (Dataset::wiener_cg, EqDataset::wiener_cg):
+// two pinned slots of up to 8 ints and an event each.  post: copy the flags after what has been enqueued and mark the point; wait: the flags as
+// they were at that point, without draining the stream -- the host reads the stop flag of iteration i - 1 while iteration i runs.
+struct CgFlagMirror {
+  int* host = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  CgFlagMirror() = default;
+  CgFlagMirror(const CgFlagMirror&) = delete; CgFlagMirror& operator=(const CgFlagMirror&) = delete;
+  ~CgFlagMirror() {
+    if (host) (void)hipHostFree(host);
+    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+  }
+  void ensure() {
+    if (host) return;
+    CMBL_HIP(hipHostMalloc((void**)&host, sizeof(int) * 16, hipHostMallocDefault));
+    for (auto& e : ev) CMBL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  void post(int slot, const int* flags_dev, int nflag, hipStream_t stream) {
+    CMBL_HIP(hipMemcpyAsync(host + 8 * slot, flags_dev, sizeof(int) * nflag, hipMemcpyDeviceToHost, stream));
+    CMBL_HIP(hipEventRecord(ev[slot], stream));
+  }
+  const int* wait(int slot) { CMBL_HIP(hipEventSynchronize(ev[slot])); return host + 8 * slot; }
+};
+
 struct DatasetApi {                        // what the C ABI (api.hip) holds of a dataset (see FlowApi)
   double logdet_sum = 0;
   virtual ~DatasetApi() = default;
@@ -208,12 +232,7 @@ struct Dataset : DatasetApi {
   // The scalars (res, alpha, beta, best residual, history, stop flag) live on the device (CgState): an iteration is enqueued
   // without waiting for its reductions; the host reads the stop flag of iteration i-1 while iteration i runs.
   DevBuf cg_scal, cg_hist, qdev, cg_rzfin;
-  int* cg_flag_host = nullptr;                 // pinned: [slot][up to 8 flags]
-  hipEvent_t cg_ev[2] = {nullptr, nullptr};
-  ~Dataset() {
-    if (cg_flag_host) (void)hipHostFree(cg_flag_host);
-    for (auto& e : cg_ev) if (e) (void)hipEventDestroy(e);
-  }
+  CgFlagMirror cg_flags;                       // pinned: [slot][up to 8 flags]
   // What the two forms of the iteration share.  cg_begin: the vectors, the scalar block (`sd`; its ints follow nd doubles per slot), the
   // pinned flags and their events, b = -gradientf(f=0, d), the start iterate x and r = b - A x.  cg_end: the best iterate, the history and
   // the NaN check.  The flag blocks differ (CgScal: 6 ints, `done` and `better` by parity; CgState: 4 ints), so they are given as `nflag`
@@ -229,10 +248,7 @@ struct Dataset : DatasetApi {
     CMBL_REQUIRE(B <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
     cg_scal.ensure(sizeof(double) * nd * MAXBATCH + sizeof(int) * 8);
     cg_hist.ensure(sizeof(double) * (size_t)maxit * B);
-    if (!cg_flag_host) {
-      CMBL_HIP(hipHostMalloc((void**)&cg_flag_host, sizeof(int) * 16, hipHostMallocDefault));
-      for (auto& e : cg_ev) CMBL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
+    cg_flags.ensure();
     v.sd = cg_scal.template as<double>(); v.si = reinterpret_cast<int*>(v.sd + nd * MAXBATCH); v.hist = cg_hist.template as<double>();
     hipStream_t sm = c->stream;
     std::vector<double> one(B, 1.0), mone(B, -1.0);
@@ -249,11 +265,8 @@ struct Dataset : DatasetApi {
     }
     return v;
   }
-  void cg_post_flags(int slot, const int* flags, int nflag) {
-    CMBL_HIP(hipMemcpyAsync(cg_flag_host + 8 * slot, flags, sizeof(int) * nflag, hipMemcpyDeviceToHost, c->stream));
-    CMBL_HIP(hipEventRecord(cg_ev[slot], c->stream));
-  }
-  const int* cg_wait_flags(int slot) { CMBL_HIP(hipEventSynchronize(cg_ev[slot])); return cg_flag_host + 8 * slot; }
+  void cg_post_flags(int slot, const int* flags, int nflag) { cg_flags.post(slot, flags, nflag, c->stream); }
+  const int* cg_wait_flags(int slot) { return cg_flags.wait(slot); }
   int cg_end(const CgVecs& v, cx<T>* f_out, double* hist, const int* flags, int nflag, int i_nan, int i_nh, int B) {
     hipStream_t sm = c->stream;
     CMBL_HIP(hipMemcpyAsync(f_out, v.bx, sizeof(cx<T>) * v.n, hipMemcpyDeviceToDevice, sm));

@@ -10,7 +10,7 @@ On the device: the four transforms, `M * f`, `M' * f`, the three operator produc
 (numpy.linalg; `factor_on="host"`, the default), or on the device (`factor_on="device"`, or `on="device"` for one call: a batched one-sided
 Jacobi SVD and a batched LU, one workgroup per block, arithmetic in double, blocks up to n = 2048).  `+`, `-`, scalar `*`, `/` are torch,
 elementwise.  `sqrt` / `pinv` / `logabsdet` are cached on the object per path, like the reference's `Ref`s.  `Cl_to_Cov` (:430-503) builds the isotropic covariance blocks on the device, in double, from their definition (the reference
-delegates to CirculantCov.jl, whose own numbers are not compared here).  NOT here: the AD rules; lensing on this projection."""
+delegates to CirculantCov.jl, whose own numbers are not compared here).  `EquiRectDataSet` is the reference's NoLensingDataSet on this projection with its Wiener filter on the device.  NOT here: the AD rules; lensing on this projection."""
 import ctypes
 
 import numpy as np
@@ -117,6 +117,17 @@ class EquiRectField:
         """dot(a, b) = dot(Ł(a).arr, Ł(b).arr) (src/proj_equirect.jl:355): the plain dot product of the map arrays, batch included"""
         _same_proj(self.proj, other.proj)
         return float(torch.dot(self.to(MAP).arr.reshape(-1), other.to(MAP).arr.reshape(-1)))
+
+    def dot_batch(self, other):
+        """dot(a, b) per batch slot (src/proj_equirect.jl:355), on the device in double with no transform: of the map arrays, or -- both fields in
+        the AZFOURIER basis -- the same number formed there (`cmbl_equirect_field_dot`; exact for images of maps).  NumPy array (B,)."""
+        _same_proj(self.proj, other.proj)
+        o = other.to(self.basis)
+        if o.B != self.B or o.P != self.P:
+            raise ValueError("dot_batch: fields of different batch size or spin")
+        out = np.empty(self.B)
+        check(self.proj.lib.cmbl_equirect_field_dot(self.proj._h, self.basis, _ptr(self.arr), _ptr(o.arr), self.P, self.B, out.ctypes.data_as(_PD)))
+        return out
 
     # f[:Ix], f[:Il] (spin 0); f[:Qx], f[:Ux], f[:Px], f[:Pl] (spin 2) (src/proj_equirect.jl:181-196)
     def __getitem__(self, k):
@@ -444,3 +455,222 @@ def simulate(M, seed=0, nbatch=1):
     P = M.n // p.Ny
     white = p._ctx.randn([int(seed) + b for b in range(int(nbatch))], 0, P)
     return M.sqrt() * EquiRectField(p, white, MAP)
+
+
+# ---- NoLensingDataSet on ProjEquiRect (src/dataset.jl:37-47, 59-80, 129-132; src/maximization.jl:17-42) ---------------------------------------
+EQDS_CF_INV, EQDS_B, EQDS_PRECOND_INV, EQDS_CN_INV = 0, 1, 2, 3           # CMBL_EQDS_* block operators
+EQDS_MASK, EQDS_CN_INV_PIX = 0, 1                                          # CMBL_EQDS_* map-diagonal operators
+
+
+def maps_images_to_images(op):
+    """How far the blocks of `op` at columns m = 0 and m = Nx/2 are from mapping images of maps to images of maps: the largest violation over the
+    two columns, relative to the block's largest element -- of being real (spin 0), of commuting with v -> S conj(v), S the swap of the two
+    halves (spin 2).  0.0 for an operator that qualifies exactly; `EquiRectDataSet` accepts up to 64 ulp of the projection's precision."""
+    p = op.proj
+    cols = [0, p.Nx // 2] if p.Nx % 2 == 0 else [0]
+    worst = 0.0
+    for m in cols:
+        H = op.blocks[m]
+        scale = float(H.abs().max()) or 1.0
+        if op.n == p.Ny:
+            dev = float(H.imag.abs().max()) if op.complex else 0.0
+        else:
+            dev = float((H - torch.roll(H, (p.Ny, p.Ny), (0, 1)).conj()).abs().max())
+        worst = max(worst, dev / scale)
+    return worst
+
+
+def _sandwich(X, A):
+    """A' X A, X and A each a BlockDiagEquiRect or a real scalar (times the identity)"""
+    if not isinstance(A, BlockDiagEquiRect):
+        return X * (A * A)
+    if not isinstance(X, BlockDiagEquiRect):
+        return (A.H * A) * X
+    return A.H * (X * A)
+
+
+class EquiRectDataSet:
+    """The reference's `NoLensingDataSet` (src/dataset.jl:37-47) on a ProjEquiRect:  d = M B f + noise,  f ~ N(0, Cf),  noise ~ N(0, Cn).
+
+    `Cf`, `B` (None: identity): `BlockDiagEquiRect`.  `M` (None: identity): map-diagonal, planes (P or 1, Nx, Ny) (the reference's
+    `Diagonal(::EquiRectMap)`).  `Cn`: a `BlockDiagEquiRect`, or map-diagonal -- a VARIANCE map (P or 1, Nx, Ny) for inhomogeneous white noise.
+    `d`: a MAP field, the default data of the methods.  The preconditioner is pinv(pinv(Cf) + B̂' M̂' pinv(Cn̂) M̂ B̂) (:129-132), a `BlockDiagEquiRect`
+    formed once; the hats default to the operators where those are block-diagonal, and where `M` / `Cn` is map-diagonal `Mhat=` / `Cnhat=` are
+    REQUIRED (a `BlockDiagEquiRect` or a real scalar times the identity): the reference has no default that type-checks, and none is guessed.
+
+    The reference's `argmaxf_logpdf` (src/maximization.jl:17-42) begins with `zero(diag(ds.Cf))` and defines no `diag(::BlockDiagEquiRect)`, so as
+    written it does not run on such a data set; this is its algorithm (`conjugate_gradient`, src/numerical_algorithms.jl:73-134) on its own
+    operators, started from the zero field of Cf's basis.  PRECONDITION: every block operator maps images of maps to images of maps (see
+    `maps_images_to_images`; `Cl_to_Cov` and `Cl_to_Beam` produce such blocks): the solver holds its vectors in the Az basis, which is the
+    reference's inner product under that condition only.  The constructor checks the two columns concerned and refuses otherwise."""
+
+    def __init__(self, proj, Cf, Cn, d=None, M=None, B=None, Cnhat=None, Mhat=None, Bhat=None):
+        self.proj, self.Cf, self.Cn, self.M, self.B, self.d = proj, Cf, Cn, None, B, None
+        if not isinstance(Cf, BlockDiagEquiRect):
+            raise ValueError("EquiRectDataSet: Cf is a BlockDiagEquiRect")
+        _same_proj(proj, Cf.proj)
+        self.P = Cf.n // proj.Ny
+        self.cn_block = isinstance(Cn, BlockDiagEquiRect)
+        if M is not None:
+            self.M = self._planes(M, "M")
+        if not self.cn_block:
+            self.Cn = self._planes(Cn, "Cn")
+        if M is not None and Mhat is None:
+            raise ValueError("EquiRectDataSet: M is map-diagonal, so Mhat= is required (a BlockDiagEquiRect or a real scalar): the reference has no default that type-checks")
+        if not self.cn_block and Cnhat is None:
+            raise ValueError("EquiRectDataSet: Cn is map-diagonal, so Cnhat= is required (a BlockDiagEquiRect or a real scalar): the reference has no default that type-checks")
+        self.Bhat = Bhat if Bhat is not None else B
+        self.Mhat = Mhat if Mhat is not None else 1.0
+        self.Cnhat = Cnhat if Cnhat is not None else Cn
+        tol = 64 * torch.finfo(proj.T).eps
+        for name, op in (("Cf", Cf), ("B", B), ("Cn", Cn if self.cn_block else None), ("Bhat", self.Bhat), ("Mhat", self.Mhat), ("Cnhat", self.Cnhat)):
+            if isinstance(op, BlockDiagEquiRect):
+                _same_proj(proj, op.proj)
+                if op.n != Cf.n:
+                    raise ValueError(f"EquiRectDataSet: {name} has blocks of size {op.n}, Cf of size {Cf.n}")
+                v = maps_images_to_images(op)
+                if v > tol:
+                    raise ValueError(f"EquiRectDataSet: the blocks of {name} at columns 0 and Nx/2 do not map images of maps to images of maps "
+                                     f"(relative violation {v:.2e}): real blocks for spin 0, blocks commuting with v -> S conj(v) for spin 2")
+        self.CfI = Cf.pinv()
+        self.CnI = Cn.pinv() if self.cn_block else (1.0 / self.Cn).contiguous()
+        self._precond = None
+        self._h = ctypes.c_void_p()
+        check(proj.lib.cmbl_eqds_create(proj._h, self.P, ctypes.byref(self._h)))
+        self._set_block(EQDS_CF_INV, self.CfI)
+        if B is not None:
+            self._set_block(EQDS_B, B)
+        if self.cn_block:
+            self._set_block(EQDS_CN_INV, self.CnI)
+        else:
+            check(proj.lib.cmbl_eqds_set_pixel_op(self._h, EQDS_CN_INV_PIX, _ptr(self.CnI), int(self.CnI.shape[0])))
+        if self.M is not None:
+            check(proj.lib.cmbl_eqds_set_pixel_op(self._h, EQDS_MASK, _ptr(self.M), int(self.M.shape[0])))
+        ld_n = Cn.logdet() if self.cn_block else float(torch.log(self.Cn.double()).sum()) * (self.P / self.Cn.shape[0])
+        self.logdet_sum = float(np.real(Cf.logdet())) + float(np.real(ld_n))
+        check(proj.lib.cmbl_eqds_set_logdet(self._h, self.logdet_sum))
+        if d is not None:
+            self.d = self._data(d)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self.proj.lib.cmbl_eqds_destroy(h)
+
+    def _planes(self, a, name):
+        p = self.proj
+        t = p.tensor(a.arr[0] if isinstance(a, EquiRectField) else a)
+        if t.dim() == 2:
+            t = t[None]
+        if t.dim() != 3 or t.shape[0] not in (1, self.P) or tuple(t.shape[1:]) != (p.Nx, p.Ny) or t.dtype != p.T:
+            raise ValueError(f"EquiRectDataSet: {name} is map-diagonal: planes (P or 1, Nx, Ny) of the projection's precision, not {tuple(t.shape)} / {t.dtype}")
+        return t.contiguous()
+
+    def _set_block(self, which, op):
+        self._keep = getattr(self, "_keep", {})
+        self._keep[which] = op                                               # the library holds a view: keep the array alive
+        check(self.proj.lib.cmbl_eqds_set_block_op(self._h, which, _ptr(op.blocks), int(op.complex), op.n))
+
+    def _field(self, f):
+        f = f if isinstance(f, EquiRectField) else EquiRectField(self.proj, f, AZFOURIER)
+        f = f.to(AZFOURIER)
+        if f.P != self.P:
+            raise ValueError("EquiRectDataSet: a field of the wrong spin")
+        return f
+
+    def _data(self, d, B=None):
+        if d is None:
+            d = self.d
+            if d is None:
+                raise ValueError("EquiRectDataSet: no data given and none held")
+        d = d if isinstance(d, EquiRectField) else EquiRectField(self.proj, d, MAP)
+        d = d.to(MAP)
+        if d.P != self.P or (B is not None and d.B != B):
+            raise ValueError("EquiRectDataSet: data of the wrong spin or batch size")
+        return d
+
+    def mean(self, f):
+        """M B f (src/dataset.jl:68-73 without L): a MAP field"""
+        f = self._field(f)
+        p = self.proj
+        out = torch.empty((f.B, self.P, p.Nx, p.Ny), dtype=p.T, device=p.device)
+        check(p.lib.cmbl_eqds_mean(self._h, _ptr(f.arr), _ptr(out), f.B))
+        return EquiRectField(p, out, MAP)
+
+    def _noise(self, white):
+        if self.cn_block:
+            return (self.Cn.sqrt() * white).to(MAP)
+        return EquiRectField(self.proj, white.arr * torch.sqrt(self.Cn)[None], MAP)
+
+    def simulate(self, seed=0, nbatch=1, white=None):
+        """(f, d): f = sqrt(Cf) * white, d = M B f + sqrt(Cn) * white' (src/dataset.jl:49-57), the white maps from the device generator (Philox keyed
+        by seed + slot; streams 0 and 1) as in `equirect.simulate`, or given as `white=(wf, wn)` (MAP fields)."""
+        p = self.proj
+        if white is None:
+            seeds = [int(seed) + b for b in range(int(nbatch))]
+            white = tuple(EquiRectField(p, p._ctx.randn(seeds, s, self.P), MAP) for s in (0, 1))
+        f = self.Cf.sqrt() * white[0]
+        return f, self.mean(f) + self._noise(white[1])
+
+    def logpdf(self, f, d=None):
+        """-½ [ (d - MBf)' Cn⁻¹ (d - MBf) + f' Cf⁻¹ f + logdet Cn + logdet Cf ] per batch slot (src/dataset.jl:59-66): NumPy array (B,)"""
+        f = self._field(f)
+        d = self._data(d, f.B)
+        out = np.empty(f.B)
+        check(self.proj.lib.cmbl_eqds_logpdf(self._h, _ptr(f.arr), _ptr(d.arr), out.ctypes.data_as(_PD), f.B))
+        return out
+
+    def gradientf_logpdf(self, f, d=None):
+        """B' M' Cn⁻¹ (d - M B f) - Cf⁻¹ f (src/dataset.jl:76-80 without L), an AZFOURIER field.  `f=None`: f = 0; `d=0`: d = 0; `d=None`: the data held."""
+        f = None if f is None else self._field(f)
+        zero_d = d is not None and not isinstance(d, EquiRectField) and np.ndim(d) == 0 and d == 0
+        d = None if zero_d else self._data(d, None if f is None else f.B)
+        if f is None and d is None:
+            raise ValueError("gradientf_logpdf: f = 0 and d = 0")
+        B = f.B if f is not None else d.B
+        p = self.proj
+        out = torch.empty((B, p.Mh, self.P * p.Ny), dtype=p.CT, device=p.device)
+        check(p.lib.cmbl_eqds_gradientf_logpdf(self._h, _ptr(f.arr) if f is not None else None, _ptr(d.arr) if d is not None else None, _ptr(out), B))
+        return EquiRectField(p, out, AZFOURIER)
+
+    def preconditioner(self):
+        """pinv(pinv(Cf) + B̂' M̂' pinv(Cn̂) M̂ B̂) (src/dataset.jl:129-132), the operator multiplied onto the residual: a `BlockDiagEquiRect`, formed once"""
+        if self._precond is None:
+            X = self.Cnhat.pinv() if isinstance(self.Cnhat, BlockDiagEquiRect) else 1.0 / float(self.Cnhat)
+            X = _sandwich(X, self.Mhat if isinstance(self.Mhat, BlockDiagEquiRect) else float(self.Mhat))
+            if self.Bhat is not None:
+                X = _sandwich(X, self.Bhat)
+            if isinstance(X, BlockDiagEquiRect):
+                tot = self.CfI + X
+            else:
+                eye = torch.eye(self.CfI.n, dtype=self.CfI.blocks.dtype, device=self.proj.device)
+                tot = BlockDiagEquiRect(self.CfI.blocks + float(X) * eye[None], self.proj)
+            self._precond = tot.pinv()
+            self._set_block(EQDS_PRECOND_INV, self._precond)
+        return self._precond
+
+    def argmaxf_logpdf(self, d=None, fstart=None, tol=1e-1, nsteps=500):
+        """The Wiener filter argmax_f logpdf (src/maximization.jl:17-42) by the reference's preconditioned CG (src/numerical_algorithms.jl:73-134),
+        entirely on the device: (f, history), f the best-`res` iterate (AZFOURIER), history the residuals dot(r, z), NumPy (iterations, B).  Stops
+        when all(res < tol)."""
+        d = self._data(d)
+        fs = None if fstart is None else self._field(fstart)
+        if fs is not None and fs.B != d.B:
+            raise ValueError("argmaxf_logpdf: fstart and d of different batch sizes")
+        self.preconditioner()
+        p = self.proj
+        out = torch.empty((d.B, p.Mh, self.P * p.Ny), dtype=p.CT, device=p.device)
+        hist = np.empty((int(nsteps), d.B))
+        nit = ctypes.c_int(0)
+        check(p.lib.cmbl_eqds_wiener_cg(self._h, _ptr(d.arr), _ptr(fs.arr) if fs is not None else None, float(tol), int(nsteps), _ptr(out),
+                                        hist.ctypes.data_as(_PD), ctypes.byref(nit), d.B))
+        return EquiRectField(p, out, AZFOURIER), hist[:nit.value].copy()
+
+    def sample_f(self, seed=0, d=None, white=None, offset=False, **kw):
+        """A posterior sample of f (src/maximization.jl:56-62): sim.f + argmaxf_logpdf(d - sim.d), sim = simulate(seed, B) or from `white=(wf, wn)`.
+        The reference's `offset=true` adds a₀ = gradientf(f = 0, d = 0), identically zero for this model: accepted, does nothing.  `kw` go to
+        `argmaxf_logpdf`.  Returns (f, history)."""
+        d = self._data(d)
+        sf, sd = self.simulate(seed, d.B, white=white)
+        f, hist = self.argmaxf_logpdf(d - sd, **kw)
+        return sf + f, hist

@@ -105,6 +105,16 @@ SIGNATURES = {
     "cmbl_equirect_block_logabsdet": [_vp, _vp, _ci, _ci, _pd],
     "cmbl_equirect_block_solve": [_vp, _vp, _ci, _ci, _ci, _vp, _ci, _ci, _vp, _ci],
     "cmbl_equirect_cov": [_vp, _pd, _pd, _ci, _ci, _pd, _pd, _ci, _vp],
+    "cmbl_eqds_create": [_vp, _ci, _pvp],
+    "cmbl_eqds_destroy": [_vp],
+    "cmbl_eqds_set_block_op": [_vp, _ci, _vp, _ci, _ci],
+    "cmbl_eqds_set_pixel_op": [_vp, _ci, _vp, _ci],
+    "cmbl_eqds_set_logdet": [_vp, _cd],
+    "cmbl_eqds_mean": [_vp, _vp, _vp, _ci],
+    "cmbl_eqds_gradientf_logpdf": [_vp, _vp, _vp, _vp, _ci],
+    "cmbl_eqds_logpdf": [_vp, _vp, _vp, _pd, _ci],
+    "cmbl_eqds_wiener_cg": [_vp, _vp, _vp, _cd, _ci, _vp, _pd, _pci, _ci],
+    "cmbl_equirect_field_dot": [_vp, _ci, _vp, _vp, _ci, _ci, _pd],
     "cmbl_healpix_pix2ang_host": [_ci, _l, _l, _pd, _pd],
     "cmbl_projector_create": [_vp, _ci, _ci, _pd, _pvp],
     "cmbl_projector_create_method": [_vp, _ci, _ci, _pd, _ci, _pvp],

@@ -426,6 +426,50 @@ int cmbl_equirect_block_solve(cmbl_ctx* ctx, const void* A, int a_complex, int n
 int cmbl_equirect_cov(cmbl_ctx* ctx, const double* theta_span, const double* phi_span, int pol, int lmax, const double* cl_a, const double* cl_b,
                       int ngrid, void* blocks_out);
 
+/* ---- NoLensingDataSet on ProjEquiRect (src/dataset.jl:37-47, 68-80): d = M B f + noise, f ~ N(0, Cf), noise ~ N(0, Cn), and its Wiener filter.
+ * Cf^-1, B, the preconditioner and (block form) Cn^-1 are BlockDiagEquiRect arrays [m][q][p] of the context's precision; M and (pixel form) Cn^-1 are
+ * map-diagonal: nplanes = 1 or npol planes (Ny, Nx), the reference's Diagonal(::EquiRectMap).  Fields are CMBL_AZFOURIER arrays (n, Nx/2+1, nbatch),
+ * n = npol Ny; data are CMBL_MAP arrays (Ny, Nx, npol, nbatch).  nbatch <= 256.
+ *   The reference's argmaxf_logpdf (src/maximization.jl:17-42) begins with zero(diag(ds.Cf)) and defines no diag(::BlockDiagEquiRect), so as written
+ *   it does not run on such a data set: what is built here is its algorithm (conjugate_gradient, src/numerical_algorithms.jl:73-134) on its operators
+ *   (model :68-73, hand gradient :76-80 without L, preconditioner :129-132), with the zero field of Cf's basis as the start.
+ *   PRECONDITION of every entry point below: each block operator maps images of maps to images of maps -- spin-0 blocks are real at columns m = 0 and
+ *   m = Nx/2; spin-2 blocks at those columns commute with v -> S conj(v), S the swap of the two halves of the 2 Ny vector (the [[G, X], [conj X, conj G]]
+ *   blocks of cmbl_equirect_cov and cmbl_equirect_beam_pol).  The CG vectors are held in the Az basis and their dot products are the map dot
+ *   (src/proj_equirect.jl:355) formed there, which is the reference's inner product under this precondition only.  It is not checked here.
+ *   cmbl_eqds_create: npol = 1 (spin 0) or 2 (spin 2; an odd Nx is CMBL_ERR_SHAPE, :166), else CMBL_ERR_ARG.
+ *   cmbl_eqds_set_block_op: a NON-OWNING view (the arrays are gigabytes): the caller keeps `blocks_dev` alive and unchanged while the data set uses it.
+ *      n != npol Ny is CMBL_ERR_SHAPE.  blocks_dev == NULL unsets CMBL_EQDS_B (identity) or CMBL_EQDS_CN_INV; for the others it is CMBL_ERR_ARG.
+ *      CMBL_EQDS_PRECOND_INV is the operator MULTIPLIED onto the residual: pinv(pinv(Cf) + B^' M^' pinv(Cn^) M^ B^) (:129-132).
+ *   cmbl_eqds_set_pixel_op: the planes are COPIED.  map_dev == NULL unsets.  nplanes other than 1 or npol: CMBL_ERR_SHAPE.  CMBL_EQDS_CN_INV_PIX holds 1 / variance.
+ *   cmbl_eqds_set_logdet: logdet Cn + logdet Cf, set by the caller like cmbl_dataset_set_logdet.
+ *   cmbl_eqds_mean: d_out = M B f (:68-73 without L).
+ *   cmbl_eqds_gradientf_logpdf: B' M' Cn^-1 (d - M B f) - Cf^-1 f (:76-80 without L).  f_az == NULL: f = 0; d_map == NULL: d = 0; both: CMBL_ERR_ARG.
+ *   cmbl_eqds_logpdf: lp_host[b] = -1/2 [ (d - MBf)' Cn^-1 (d - MBf) + f' Cf^-1 f + logdet ] (:59-66).  Synchronises.
+ *   cmbl_eqds_wiener_cg: preconditioned CG on A = Cf^-1 + B'M'Cn^-1 M B, b = B'M'Cn^-1 d with the semantics of cmbl_wiener_cg: res = dot(r, z), stop when
+ *      all(res < tol), the best-res iterate goes to f_out, res_hist_host (maxit * nbatch doubles) gets *nit_host residual vectors, a NaN residual is
+ *      CMBL_ERR_NAN.  fstart_az == NULL starts from zero.  Scalars, history and flags live on the device; no host synchronisation inside an iteration.
+ *      Every output has one writer and one order of operations: two runs are bit-identical.
+ *   State: CMBL_ERR_STATE when CMBL_EQDS_CF_INV is missing, when no form or both forms of Cn^-1 are set (mean needs none), or (wiener_cg) when
+ *      CMBL_EQDS_PRECOND_INV is missing.  nbatch outside [1, 256]: CMBL_ERR_SHAPE.
+ *   cmbl_equirect_field_dot: out_host[b] = dot(a_b, b_b) (src/proj_equirect.jl:355) per batch slot, in double, two stages, fixed order.  basis CMBL_MAP:
+ *      the plain dot of the map arrays; CMBL_AZFOURIER: the same number for images of maps, spin 0: sum_m w_m Re(conj(a) b) with w = 1 at m = 0 and
+ *      m = Nx/2 (even Nx), 2 elsewhere; spin 2: over all 2 Ny rows with w = 1/2 at columns 0 and Nx/2, 1 elsewhere.  Synchronises. */
+typedef struct cmbl_eqds cmbl_eqds;
+enum { CMBL_EQDS_CF_INV = 0, CMBL_EQDS_B = 1, CMBL_EQDS_PRECOND_INV = 2, CMBL_EQDS_CN_INV = 3 };   /* block operators */
+enum { CMBL_EQDS_MASK = 0, CMBL_EQDS_CN_INV_PIX = 1 };                                               /* map-diagonal operators */
+int cmbl_eqds_create(cmbl_ctx* ctx, int npol, cmbl_eqds** out);
+int cmbl_eqds_destroy(cmbl_eqds* ds);
+int cmbl_eqds_set_block_op(cmbl_eqds* ds, int which, const void* blocks_dev, int blocks_complex, int n);
+int cmbl_eqds_set_pixel_op(cmbl_eqds* ds, int which, const void* map_dev, int nplanes);
+int cmbl_eqds_set_logdet(cmbl_eqds* ds, double logdet_sum);
+int cmbl_eqds_mean(cmbl_eqds* ds, const void* f_az, void* d_out_map, int nbatch);
+int cmbl_eqds_gradientf_logpdf(cmbl_eqds* ds, const void* f_az, const void* d_map, void* out_az, int nbatch);
+int cmbl_eqds_logpdf(cmbl_eqds* ds, const void* f_az, const void* d_map, double* lp_host, int nbatch);
+int cmbl_eqds_wiener_cg(cmbl_eqds* ds, const void* d_map, const void* fstart_az, double tol, int maxit, void* f_out_az, double* res_hist_host,
+                        int* nit_host, int nbatch);
+int cmbl_equirect_field_dot(cmbl_ctx* ctx, int basis, const void* a, const void* b, int npol, int nbatch, double* out_host);
+
 /* ---- small helpers used by the drivers above the hot kernels
  * axpby: out = a[b]*x + b[b]*y per batch slot (y may be NULL) -- the FieldTuple / Field broadcasts of the CG, line-search
  *        and leapfrog updates (src/numerical_algorithms.jl:102-107, src/sampling.jl:29-31).
