@@ -11,7 +11,7 @@ from .engine import (ProjLambert, LenseFlow, BilinearLens, PowerLens, Taylens, a
                      get_Cl, get_Dl, get_l4Cl, get_rhol, cov_to_Cl, make_mask)
 from .equirect import (ProjEquiRect, EquiRectField, BlockDiagEquiRect, AZFOURIER, Cl_to_Beam, Cl_to_Cov, simulate, equirect_geometry,   # noqa: F401
                        blocks_from_ref, blocks_to_ref, EquiRectDataSet)
-from .healpix import (ProjHealpix, HealpixField, HealpixMap, Projector, project, pix2ang_ring, npix2nside)   # noqa: F401
+from .healpix import (ProjHealpix, HealpixField, HealpixMap, Projector, project, project_adjoint, pix2ang_ring, npix2nside)   # noqa: F401
 from .sim import (Cls, load_sim, noise_cls, beam_cls, lowpass, cl_to_2d, HarmOp, border_mask)   # noqa: F401
 from .chains import partition_chains, chain_seed, gather_chain_values, allreduce_sum   # noqa: F401
 from .drivers import (quadratic_estimate, MAP_joint, MAP_joint_step, hmc_step, sample_f, gibbs_step, symplectic_integrate,   # noqa: F401

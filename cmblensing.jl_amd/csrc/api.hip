@@ -777,6 +777,20 @@ int cmbl_project_to_healpix(cmbl_projector* P, int basis_in, const void* in, voi
     P->p->to_healpix(basis_in, in, hpx_out, npol, nbatch);
   });
 }
+int cmbl_project_to_cart_adjoint(cmbl_projector* P, const void* map_cot, void* hpx_out, int npol, int nbatch) {
+  return guard([&] {
+    NOTNULL(P); NOTNULL(map_cot); NOTNULL(hpx_out); POLB_OK(npol, nbatch);
+    CMBL_REQUIRE(map_cot != hpx_out, ERR_ARG, "project_to_cart_adjoint: out must not alias the input");
+    P->p->to_cart_adjoint(map_cot, hpx_out, npol, nbatch);
+  });
+}
+int cmbl_project_to_healpix_adjoint(cmbl_projector* P, const void* hpx_cot, void* map_out, int npol, int nbatch) {
+  return guard([&] {
+    NOTNULL(P); NOTNULL(hpx_cot); NOTNULL(map_out); POLB_OK(npol, nbatch);
+    CMBL_REQUIRE(hpx_cot != map_out, ERR_ARG, "project_to_healpix_adjoint: out must not alias the input");
+    P->p->to_healpix_adjoint(hpx_cot, map_out, npol, nbatch);
+  });
+}
 
 #ifdef CMBL_STAMPS
 // phase timestamps of the last stamped launch (tools/gpu_stamps*.py) of the translation unit CMBL_STAMPS_TU (kernels_fft.hpp CMBL_STAMPS_READER)

@@ -12,6 +12,9 @@
 // context `fc` that the projector owns (same device, stream and precision -- the two-context route of ud_grade):
 //   to_healpix   rfft2 (c) -> F2ref -> k_nfft_embed -> ref2F -> C2R (fc) -> k_nfft_interp
 //   to_cart      k_nfft_spread -> rfft2 (fc) -> F2ref -> k_nfft_extract -> ref2F -> C2R (c) -> k_nfft_rot_cart (QU only)
+// The transposes (pullbacks) are the same two pipelines with the rotation moved to the other end and the scales exchanged:
+//   to_healpix^T  k_nfft_spread<ROT> -> ... the to_cart pipeline ... -> C2R (c), scale 1 / (Ny Nx), no k_nfft_rot_cart
+//   to_cart^T     k_nfft_rot_cart<ADJ> into a scratch copy -> ... the to_healpix pipeline ... -> k_nfft_interp<no rotation>, scale 1 / Npatch
 // Both fine grids are real (field and window are real), so every transform is R2C / C2R.  The scales 1 / (Ny Nx) and Ny Nx / Npatch are folded
 // into k_nfft_embed / k_nfft_extract together with the 1 / (4 Ny Nx) resp. 1 / (Ny Nx) of the C2R that follows.
 // The nodes are fixed per projector: the constructor sorts them once by tile of the fine grid (nfft_bin_nodes, host, stable) and keeps the
@@ -98,6 +101,7 @@ struct NfftProjector : Projector<T> {
   std::unique_ptr<Ctx<T>> fc;                // the fine grid's context
   DevBuf nty, ntx, npx, nc2, ns2, noff, decy, decx;
   DevBuf cref, cF, fref, fF, fmap;           // coarse / fine half planes in reference and F layout, fine maps
+  DevBuf rotm;                               // the rotated copy of a cotangent on the patch (to_cart_adjoint)
   NfftNodes<T> nd{};
   NfftModes<T> md{};
   int ntiles = 0;
@@ -179,7 +183,41 @@ struct NfftProjector : Projector<T> {
     c->ref2F(cref.as<cx<T>>(), cF.as<cx<T>>(), sl);
     c->F_to_map(cF.as<cx<T>>(), (T*)map_out, sl);
     if (P >= 2)
-      CMBL_LAUNCH(c, K_NFFT_MODES, (k_nfft_rot_cart<T>), dim3(nblocks(ncart), (unsigned)B), 0, c->stream, (T*)map_out, this->c2.template as<T>(), this->s2.template as<T>(), ncart, P);
+      CMBL_LAUNCH(c, K_NFFT_MODES, (k_nfft_rot_cart<T>), dim3(nblocks(ncart), (unsigned)B), 0, c->stream, (const T*)map_out, (T*)map_out, this->c2.template as<T>(), this->s2.template as<T>(), ncart, P);
+  }
+
+  // to_healpix^T: mbar_g = 1 / (Ny Nx) sum_{p in patch} K(x_p - x_g) (Rh(psi_p)^T hbar)_p -- the to_cart pipeline with the rotation on the node
+  // values as they are loaded, no k_nfft_rot_cart, and the scale 1 / (Ny Nx) (the C2R's own) in place of 1 / Npatch
+  void to_healpix_adjoint(const void* hpx_cot, void* map_out, int P, int B) override {
+    const long sl = (long)P * B;
+    ensure(sl);
+    CMBL_LAUNCH(c, K_NFFT_SPREAD, (k_nfft_spread<T, W, true>), dim3((unsigned)ntiles, (unsigned)B), 0, c->stream, (const T*)hpx_cot, fmap.as<T>(), nd, npix, P);
+    fc->rfft2_F(fmap.as<T>(), fF.as<cx<T>>(), sl);
+    fc->F2ref(fF.as<cx<T>>(), fref.as<cx<T>>(), sl);
+    CMBL_LAUNCH(c, K_NFFT_MODES, (k_nfft_extract<T>), dim3(nblocks(c->plane()), (unsigned)sl), 0, c->stream, fref.as<cx<T>>(), cref.as<cx<T>>(), md, c->Ny, c->Nx, (T)1);
+    c->ref2F(cref.as<cx<T>>(), cF.as<cx<T>>(), sl);
+    c->F_to_map(cF.as<cx<T>>(), (T*)map_out, sl);
+  }
+
+  // to_cart^T: hbar_p = 1 / Npatch sum_g K(x_g - x_p) (Rc(psi_g)^T mbar)_g on the patch, exactly 0 elsewhere -- the to_healpix pipeline on a
+  // rotated copy of the input (the caller's array is not modified), no rotation at the nodes, and 1 / Npatch in place of 1 / (Ny Nx)
+  void to_cart_adjoint(const void* map_cot, void* hpx_out, int P, int B) override {
+    const long sl = (long)P * B;
+    ensure(sl);
+    const T* m = (const T*)map_cot;
+    if (P >= 2) {
+      rotm.ensure(sizeof(T) * sl * ncart);
+      CMBL_LAUNCH(c, K_NFFT_MODES, (k_nfft_rot_cart<T, true>), dim3(nblocks(ncart), (unsigned)B), 0, c->stream, m, rotm.as<T>(), this->c2.template as<T>(), this->s2.template as<T>(), ncart, P);
+      m = rotm.as<T>();
+    }
+    c->rfft2_F(m, cF.as<cx<T>>(), sl);
+    c->F2ref(cF.as<cx<T>>(), cref.as<cx<T>>(), sl);
+    const T scale = (T)(4.0 * (double)c->Ny * c->Nx / (double)nd.n);         // the fine C2R divides by 4 Ny Nx; the definition by Npatch
+    CMBL_LAUNCH(c, K_NFFT_MODES, (k_nfft_embed<T>), dim3(nblocks(fc->plane()), (unsigned)sl), 0, c->stream, cref.as<cx<T>>(), fref.as<cx<T>>(), md, c->Ny, c->Nx, scale);
+    fc->ref2F(fref.as<cx<T>>(), fF.as<cx<T>>(), sl);
+    fc->F_to_map(fF.as<cx<T>>(), fmap.as<T>(), sl);
+    CMBL_HIP(hipMemsetAsync(hpx_out, 0, sizeof(T) * (size_t)npix * P * B, c->stream));
+    CMBL_LAUNCH(c, K_NFFT_INTERP, (k_nfft_interp<T, W, false>), dim3(nblocks(nd.n)), 0, c->stream, fmap.as<T>(), (T*)hpx_out, nd, npix, P, B);
   }
 };
 

@@ -12,6 +12,7 @@
 //   k_hpx_compact     the two ascending lists from the flags and the scanned block counts; (i, j), ψ, cos 2ψ, sin 2ψ of the touched pixels
 //   k_hpx_to_cart     HEALPix -> Cartesian gather, QU rotation of :243-244 fused
 //   k_hpx_to_healpix  Cartesian -> HEALPix gather (Images.bilinear_interpolation, outside = 0), QU rotation of :332-333 fused
+//   k_hpx_adjoint     the transpose of either gather: a gather over the CSR of the transposed table, the transposed rotation on the input
 #pragma once
 #include <cmath>
 #include "common.hpp"
@@ -334,6 +335,80 @@ __global__ __launch_bounds__(NTP) void k_hpx_to_healpix(const T* __restrict__ ma
       hb[(long)q * npix] = fma(U, ss, Q * cc);
       hb[(long)(q + 1) * npix] = fma(-Q, ss, U * cc);
     }
+  }
+}
+
+// ---- the transposes (pullbacks) of the two gathers ---------------------------------------------------------------------------------------
+// Both are gathers over a CSR of the transposed table (engine_healpix.hpp builds it): a row is an OUTPUT element, its entries the (input
+// element, corner) pairs that read it in the forward direction, ordered by ascending input element, then by corner.
+//   to_cart^T     row = a HEALPix pixel some Cartesian pixel reads (rowout), entry = Cartesian pixel c (its value, cos 2ψ_c, sin 2ψ_c), weight w[c][k]
+//   to_healpix^T  row = a Cartesian pixel (all of them, rowout null), entry = slot t of the touched list (value at src[t] = the pixel, ψ_t), weight v[t][k]
+template <typename T> struct HpxCsr {
+  const int* rowstart;                               // nrows + 1
+  const int* rowout;                                 // output element of row r; null: r itself
+  const int* ent;                                    // per entry: slot of the forward table
+  const T* val;                                      // per entry: the forward weight, as the forward kernel rounds it
+  const int* src;                                    // input element of a slot; null: the slot itself
+  const T* c2; const T* s2;                          // per slot
+  int nrows;
+};
+constexpr int HPX_ADJ_NT = 64;                       // one wave per workgroup: a long row holds back its own wave and nothing else
+constexpr int HPX_ADJ_NB = 4;                        // batch entries per pass over a row (NP * HPX_ADJ_NB accumulators in registers)
+constexpr int HPX_ADJ_AHEAD = 4;                     // entries whose loads are issued together
+
+// out[o_r] = Σ_entries val * (R^T in[src])  for every slice: one thread per row, the row summed in its stored order in T, one fma per entry
+// (bit-identical between runs, the contract of k_bl_csr); an entry is read once per HPX_ADJ_NB batch entries and reused over their planes.
+// The rotation acts on the INPUT, at the entry's ψ: TO_SPHERE (to_cart^T) Q' = Q cos 2ψ + U sin 2ψ, U' = U cos 2ψ - Q sin 2ψ (the transpose of
+// :243-244); otherwise (to_healpix^T) Q' = Q cos 2ψ - U sin 2ψ, U' = U cos 2ψ + Q sin 2ψ (the transpose of :332-333).  Rows have any length:
+// there is no bound and no barrier, and the waves of a launch retire independently.  A row without entries writes 0.
+// in (nin, NP, nbatch), out (nout, NP, nbatch).  grid ceil(nrows / HPX_ADJ_NT), HPX_ADJ_NT threads
+template <typename T, int NP, bool TO_SPHERE>
+__global__ __launch_bounds__(HPX_ADJ_NT) void k_hpx_adjoint(const T* __restrict__ in, T* __restrict__ out, const HpxCsr<T> A, long nin, long nout, int nbatch) {
+  const int r = blockIdx.x * HPX_ADJ_NT + threadIdx.x;
+  if (r >= A.nrows) return;
+  const int s = A.rowstart[r], e = A.rowstart[r + 1];
+  const long o = A.rowout ? A.rowout[r] : r;
+  for (int b0 = 0; b0 < nbatch; b0 += HPX_ADJ_NB) {
+    const int nb = nbatch - b0 < HPX_ADJ_NB ? nbatch - b0 : HPX_ADJ_NB;
+    T acc[HPX_ADJ_NB][NP];
+#pragma unroll
+    for (int q = 0; q < HPX_ADJ_NB; ++q)
+#pragma unroll
+      for (int k = 0; k < NP; ++k) acc[q][k] = 0;
+    // one entry: the dependent loads slot -> (pixel, cos, sin) -> values, then the row's next fma
+    auto add = [&](int k, T v) {
+      const long i = A.src ? A.src[k] : k;
+      T cc = 1, ss = 0;
+      if constexpr (NP >= 2) { cc = A.c2[k]; ss = A.s2[k]; }
+#pragma unroll
+      for (int q = 0; q < HPX_ADJ_NB; ++q)
+        if (q < nb) {
+          const T* ib = in + (long)(b0 + q) * NP * nin + i;
+          if constexpr (NP != 2) acc[q][0] = fma(v, ib[0], acc[q][0]);
+          if constexpr (NP >= 2) {
+            const T Q = ib[(long)(NP - 2) * nin], U = ib[(long)(NP - 1) * nin];
+            const T rq = TO_SPHERE ? fma(U, ss, Q * cc) : fma(-U, ss, Q * cc);
+            const T ru = TO_SPHERE ? fma(-Q, ss, U * cc) : fma(Q, ss, U * cc);
+            acc[q][NP - 2] = fma(v, rq, acc[q][NP - 2]);
+            acc[q][NP - 1] = fma(v, ru, acc[q][NP - 1]);
+          }
+        }
+    };
+    // HPX_ADJ_AHEAD entries at a time, so that their chains of dependent loads overlap; the fma chain keeps the stored order
+    int p = s;
+    for (; p + HPX_ADJ_AHEAD <= e; p += HPX_ADJ_AHEAD) {
+      int k[HPX_ADJ_AHEAD]; T v[HPX_ADJ_AHEAD];
+#pragma unroll
+      for (int u = 0; u < HPX_ADJ_AHEAD; ++u) { k[u] = A.ent[p + u]; v[u] = A.val[p + u]; }
+#pragma unroll
+      for (int u = 0; u < HPX_ADJ_AHEAD; ++u) add(k[u], v[u]);
+    }
+    for (; p < e; ++p) add(A.ent[p], A.val[p]);
+#pragma unroll
+    for (int q = 0; q < HPX_ADJ_NB; ++q)
+      if (q < nb)
+#pragma unroll
+        for (int k = 0; k < NP; ++k) out[((long)(b0 + q) * NP + k) * nout + o] = acc[q][k];
   }
 }
 

@@ -10,6 +10,8 @@
 //   k_nfft_spread    HEALPix pixels of the patch -> fine grid, one workgroup per tile of the fine grid                    (HEALPix -> Cartesian)
 //   k_nfft_extract   fine half plane -> coarse half plane: the transpose of k_nfft_embed
 //   k_nfft_rot_cart  QU rotation at the Cartesian pixels, in place
+// The transposes of the two directions reuse the same kernels: k_nfft_spread<ROT> rotates the node values as it loads them,
+// k_nfft_interp<ROT = false> does not rotate, k_nfft_rot_cart<ADJ> applies the transposed rotation into a scratch array.
 // Half planes are in the reference layout [kx slot][ky] (ky fastest, natural order), which both contexts convert to and from.
 #pragma once
 #include <cmath>
@@ -77,8 +79,9 @@ __global__ __launch_bounds__(NTP) void k_nfft_embed(const cx<T>* __restrict__ F,
 
 // fine maps (2Ny, 2Nx, npol, nbatch) -> HEALPix (npix, npol, nbatch), which the host has zeroed: one thread per node, the 2 w window values in
 // registers, reused over all slices.  Each value is sum_dx wx[dx] (sum_dy wy[dy] g[x][y]) in that order.  QU as in :332-333:
-// Q' = Q cos 2 psi + U sin 2 psi, U' = U cos 2 psi - Q sin 2 psi.  grid ceil(n / NTP)
-template <typename T, int W>
+// Q' = Q cos 2 psi + U sin 2 psi, U' = U cos 2 psi - Q sin 2 psi.  ROT = false (the transpose of to_cart, whose rotation sits at the Cartesian
+// pixels): no rotation.  grid ceil(n / NTP)
+template <typename T, int W, bool ROT = true>
 __global__ __launch_bounds__(NTP) void k_nfft_interp(const T* __restrict__ fine, T* __restrict__ hpx, const NfftNodes<T> nd, long npix, int npol, int nbatch) {
   const int s = blockIdx.x * NTP + threadIdx.x;
   if (s >= nd.n) return;
@@ -114,8 +117,8 @@ __global__ __launch_bounds__(NTP) void k_nfft_interp(const T* __restrict__ fine,
     if (npol != 2) { hb[0] = val(gb); q = 1; }
     if (npol >= 2) {
       const T Q = val(gb + (long)q * nfine), U = val(gb + (long)(q + 1) * nfine);
-      hb[(long)q * npix] = fma(U, ss, Q * cc);
-      hb[(long)(q + 1) * npix] = fma(-Q, ss, U * cc);
+      hb[(long)q * npix] = ROT ? fma(U, ss, Q * cc) : Q;
+      hb[(long)(q + 1) * npix] = ROT ? fma(-Q, ss, U * cc) : U;
     }
   }
 }
@@ -126,8 +129,10 @@ __global__ __launch_bounds__(NTP) void k_nfft_interp(const T* __restrict__ fine,
 // nodes ascending) as ONE list -- the up to nine CSR ranges end to end -- NFFT_CHUNK at a time: the workgroup stages first cell, the 2 W window
 // values and the npol values of each node of the chunk in LDS, then every cell adds the nodes whose window covers it.  A cell's distance from a node's first cell is taken modulo the grid,
 // so a window that wraps, and a grid of fewer than three tiles, need no special case.  Every cell of the grid is written once (zeros included).
+// ROT (the transpose of to_healpix): QU are rotated as they are staged, by the transpose of :332-333 at the node,
+// Q' = Q cos 2 psi - U sin 2 psi, U' = U cos 2 psi + Q sin 2 psi.
 // grid (ntY ntX, nbatch)
-template <typename T, int W>
+template <typename T, int W, bool ROT = false>
 __global__ __launch_bounds__(NTP) void k_nfft_spread(const T* __restrict__ hpx, T* __restrict__ fine, const NfftNodes<T> nd, long npix, int npol) {
   __shared__ T swy[NFFT_CHUNK][W], swx[NFFT_CHUNK][W], sval[3][NFFT_CHUNK];
   __shared__ int sk0y[NFFT_CHUNK], sk0x[NFFT_CHUNK];
@@ -165,10 +170,20 @@ __global__ __launch_bounds__(NTP) void k_nfft_spread(const T* __restrict__ hpx, 
       if (ax) swx[q][d] = v; else swy[q][d] = v;
       if (d == 0) { if (ax) sk0x[q] = k0; else sk0y[q] = k0; }
     }
-    for (int e = t; e < cn * npol; e += NTP) {
-      const int k = e / cn, q = e - k * cn;
-      sval[k][q] = hb[(long)k * npix + nd.pix[slot_of(c0 + q)]];
-    }
+    if (ROT && npol >= 2) {
+      for (int q = t; q < cn; q += NTP) {
+        const int s = slot_of(c0 + q);
+        const long p = nd.pix[s];
+        if (npol == 3) sval[0][q] = hb[p];
+        const T Q = hb[(long)(npol - 2) * npix + p], U = hb[(long)(npol - 1) * npix + p], cc = nd.c2[s], ss = nd.s2[s];
+        sval[npol - 2][q] = fma(-U, ss, Q * cc);
+        sval[npol - 1][q] = fma(Q, ss, U * cc);
+      }
+    } else
+      for (int e = t; e < cn * npol; e += NTP) {
+        const int k = e / cn, q = e - k * cn;
+        sval[k][q] = hb[(long)k * npix + nd.pix[slot_of(c0 + q)]];
+      }
     __syncthreads();
     if (active)
       for (int q = 0; q < cn; ++q) {
@@ -207,15 +222,18 @@ __global__ __launch_bounds__(NTP) void k_nfft_extract(const cx<T>* __restrict__ 
   A[(long)blockIdx.y * plane + e] = (scale * (T)0.5) * (hm + hp);
 }
 
-// maps (Ny Nx, npol, nbatch) in place: Q' = Q cos 2 psi - U sin 2 psi, U' = U cos 2 psi + Q sin 2 psi (:243-244).  grid (ceil(Ny Nx / NTP), nbatch)
-template <typename T>
-__global__ __launch_bounds__(NTP) void k_nfft_rot_cart(T* __restrict__ m, const T* __restrict__ c2, const T* __restrict__ s2, long ncart, int npol) {
+// maps (Ny Nx, npol, nbatch), src -> dst (the same array: in place): Q' = Q cos 2 psi - U sin 2 psi, U' = U cos 2 psi + Q sin 2 psi (:243-244).
+// ADJ: the transpose, Q' = Q cos 2 psi + U sin 2 psi, U' = U cos 2 psi - Q sin 2 psi, into another array, the I plane of npol = 3 copied.
+// grid (ceil(Ny Nx / NTP), nbatch)
+template <typename T, bool ADJ = false>
+__global__ __launch_bounds__(NTP) void k_nfft_rot_cart(const T* src, T* dst, const T* __restrict__ c2, const T* __restrict__ s2, long ncart, int npol) {
   const long c = (long)blockIdx.x * NTP + threadIdx.x;
   if (c >= ncart) return;
-  T* q = m + ((long)blockIdx.y * npol + (npol - 2)) * ncart + c;
-  const T Q = q[0], U = q[ncart], cc = c2[c], ss = s2[c];
-  q[0] = fma(-U, ss, Q * cc);
-  q[ncart] = fma(Q, ss, U * cc);
+  const long o = ((long)blockIdx.y * npol + (npol - 2)) * ncart + c;
+  const T Q = src[o], U = src[o + ncart], cc = c2[c], ss = s2[c];
+  dst[o] = ADJ ? fma(U, ss, Q * cc) : fma(-U, ss, Q * cc);
+  dst[o + ncart] = ADJ ? fma(-Q, ss, U * cc) : fma(Q, ss, U * cc);
+  if (ADJ && npol == 3) dst[o - ncart] = src[o - ncart];
 }
 
 }  // namespace cmbl

@@ -1,5 +1,5 @@
 """HEALPix fields and the projection between the sphere and a flat patch (src/proj_healpix.jl) on top of the C ABI: `ProjHealpix`,
-`HealpixField` / `HealpixMap`, `Projector` and `project`.
+`HealpixField` / `HealpixMap`, `Projector`, `project` and its transpose `project_adjoint`.
 
 A HEALPix field is a tensor (B, P, npix) == Julia (npix, npol) plus the batch axis, RING ordering, P = 1 (I), 2 (QU) or 3 (IQU).  Pixel
 indices are 0-based here (the reference's k - 1).  `project` covers both directions of `method="bilinear"` and of `method="nfft"` for
@@ -11,7 +11,11 @@ of the band-limited patch at the HEALPix centres one way and its transpose the o
 `"fft"` itself still raises NotImplementedError, with its message unchanged: existing tests pin that, and making it an alias of "nfft" is
 left to a change that may touch them.
 
-NOT here (README "HEALPix projection", out of scope): NEST ordering, the AD rules, lensing of HEALPix fields."""
+The pullbacks: `project_adjoint` (and `Projector.to_cart_adjoint` / `to_healpix_adjoint`) is the exact transpose of `project`, on the device,
+for both methods; `project` on a field whose tensor has `requires_grad` goes through a `torch.autograd.Function` whose backward it is
+(the reference's `@adjoint` of :145-150).
+
+NOT here (README "HEALPix projection", out of scope): NEST ordering, lensing of HEALPix fields."""
 import ctypes
 
 import numpy as np
@@ -199,29 +203,135 @@ class Projector(_Handle):
     js = property(lambda s: s._get(_J, s.n_touched))
     psi_hpx = property(lambda s: s._get(_PSI_HPX, s.n_touched))
 
+    def _to_cart_raw(self, src, npol, B):
+        p = self.cart_proj
+        out = torch.empty((B, npol, p.Nx, p.Ny), dtype=p.T, device=p.device)
+        check(self.lib.cmbl_project_to_cart(self._h, _ptr(src), _ptr(out), npol, B))
+        return out
+
+    def _to_healpix_raw(self, arr, basis, P, B):
+        p = self.cart_proj
+        out = torch.empty((B, P, self.hpx_proj.npix), dtype=p.T, device=p.device)
+        check(self.lib.cmbl_project_to_healpix(self._h, basis, _ptr(arr), _ptr(out), P, B))
+        return out
+
+    def _to_cart_adjoint_raw(self, g, npol, B):
+        p = self.cart_proj
+        out = torch.empty((B, npol, self.hpx_proj.npix), dtype=p.T, device=p.device)
+        check(self.lib.cmbl_project_to_cart_adjoint(self._h, _ptr(g), _ptr(out), npol, B))
+        return out
+
+    def _to_healpix_adjoint_raw(self, g, npol, B):
+        p = self.cart_proj
+        out = torch.empty((B, npol, p.Nx, p.Ny), dtype=p.T, device=p.device)
+        check(self.lib.cmbl_project_to_healpix_adjoint(self._h, _ptr(g), _ptr(out), npol, B))
+        return out
+
+    def _cart_field(self, out):
+        # (EquiRectField is spin 0 or spin 2; an IQU result on a ProjEquiRect is a plain MAP Field, the reference's BaseField{IQUMap}, :251)
+        p = self.cart_proj
+        return EquiRectField(p, out, MAP) if isinstance(p, ProjEquiRect) and out.shape[1] < 3 else Field(p, out, MAP)
+
+    def _dev(self, t):
+        """a tensor that autograd follows -> contiguous, on the device, of the projection's precision (differentiable, unlike `tensor`)"""
+        p = self.cart_proj
+        return t.to(device=p.device, dtype=p.T).contiguous()
+
     def to_cart(self, f):
-        """project(projector, healpix_field => cart_proj) (:221-252)"""
+        """project(projector, healpix_field => cart_proj) (:221-252).  A field whose tensor has `requires_grad` is followed by autograd;
+        the pullback is `to_cart_adjoint`."""
         p = self.cart_proj
         if f.proj != self.hpx_proj:
             raise ValueError(f"Projector built for Nside {self.hpx_proj.Nside}, field has {f.proj.Nside}")
-        src = p.tensor(f.arr)
-        out = torch.empty((f.B, f.npol, p.Nx, p.Ny), dtype=p.T, device=p.device)
-        check(self.lib.cmbl_project_to_cart(self._h, _ptr(src), _ptr(out), f.npol, f.B))
-        # (EquiRectField is spin 0 or spin 2; an IQU result on a ProjEquiRect is a plain MAP Field, the reference's BaseField{IQUMap}, :251)
-        return EquiRectField(p, out, MAP) if isinstance(p, ProjEquiRect) and f.npol < 3 else Field(p, out, MAP)
+        if f.arr.requires_grad:
+            return self._cart_field(_ToCart.apply(self._dev(f.arr), self))
+        return self._cart_field(self._to_cart_raw(p.tensor(f.arr), f.npol, f.B))
 
     def to_healpix(self, f):
-        """project(projector, cart_field => hpx_proj) (:308-341): `f` a Field of the ProjLambert (any basis) or an EquiRectField"""
+        """project(projector, cart_field => hpx_proj) (:308-341): `f` a Field of the ProjLambert (any basis) or an EquiRectField.  A MAP
+        field whose tensor has `requires_grad` is followed by autograd; the pullback is `to_healpix_adjoint`."""
         p = self.cart_proj
         if f.proj is not p and f.proj != p:
             raise ValueError("Projector built for another Cartesian projection than the field's")
+        if torch.is_tensor(f.arr) and f.arr.requires_grad:
+            if f.basis != MAP:
+                raise ValueError("Projector.to_healpix: under autograd the field must be in the MAP basis")
+            out = _ToHealpix.apply(self._dev(f.arr), self)
+            return HealpixField(self.hpx_proj, out, {1: "I", 2: "QU", 3: "IQU"}[int(out.shape[1])])
         if isinstance(f, EquiRectField):
             f = f.to(MAP)
         arr, basis = f.arr, f.basis
         B, P = int(arr.shape[0]), int(arr.shape[1])
-        out = torch.empty((B, P, self.hpx_proj.npix), dtype=p.T, device=p.device)
-        check(self.lib.cmbl_project_to_healpix(self._h, basis, _ptr(arr), _ptr(out), P, B))
-        return HealpixField(self.hpx_proj, out, {1: "I", 2: "QU", 3: "IQU"}[P])
+        return HealpixField(self.hpx_proj, self._to_healpix_raw(arr, basis, P, B), {1: "I", 2: "QU", 3: "IQU"}[P])
+
+    def to_cart_adjoint(self, g):
+        """The transpose (pullback) of `to_cart`: `g` a MAP Field / EquiRectField on the Cartesian projection -> HealpixField.  Bilinear:
+        hbar[p] = sum over the (Cartesian pixel, corner) pairs that read p of weight * (the rotation's transpose applied to g there), exactly
+        0 where nothing reads; nfft: 1/Npatch sum_g K(x_g - x_p) (R^T g)_g on hpx_idxs_in_patch, exactly 0 elsewhere (include/cmblens.h)."""
+        p = self.cart_proj
+        if g.proj is not p and g.proj != p:
+            raise ValueError("Projector built for another Cartesian projection than the cotangent's")
+        if isinstance(g, EquiRectField):
+            g = g.to(MAP)
+        if g.basis != MAP:
+            raise ValueError("Projector.to_cart_adjoint: the cotangent must be in the MAP basis")
+        arr = p.tensor(g.arr.detach())
+        if arr.dim() != 4 or tuple(arr.shape[2:]) != (p.Nx, p.Ny) or not 1 <= arr.shape[1] <= 3:
+            raise ValueError(f"Projector.to_cart_adjoint: a MAP array (B, 1 ... 3, {p.Nx}, {p.Ny}) is needed, got {tuple(arr.shape)}")
+        B, P = int(arr.shape[0]), int(arr.shape[1])
+        return HealpixField(self.hpx_proj, self._to_cart_adjoint_raw(arr, P, B), {1: "I", 2: "QU", 3: "IQU"}[P])
+
+    def to_healpix_adjoint(self, g):
+        """The transpose (pullback) of `to_healpix` on MAP input: `g` a HealpixField -> MAP Field (an EquiRectField on a ProjEquiRect with
+        npol < 3, the rule of `to_cart`).  Values of `g` at pixels the projection does not touch are ignored."""
+        p = self.cart_proj
+        if not isinstance(g, HealpixField) or g.proj != self.hpx_proj:
+            raise ValueError(f"Projector built for Nside {self.hpx_proj.Nside}, the cotangent has {getattr(getattr(g, 'proj', None), 'Nside', None)}")
+        return self._cart_field(self._to_healpix_adjoint_raw(p.tensor(g.arr.detach()), g.npol, g.B))
+
+
+class _ToCart(torch.autograd.Function):
+    """`Projector.to_cart` for autograd: (B, P, npix) device tensor -> (B, P, Nx, Ny); backward is `cmbl_project_to_cart_adjoint`"""
+
+    @staticmethod
+    def forward(ctx, src, projector):
+        ctx.projector = projector
+        return projector._to_cart_raw(src, int(src.shape[1]), int(src.shape[0]))
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        return ctx.projector._to_cart_adjoint_raw(g, int(g.shape[1]), int(g.shape[0])), None
+
+
+class _ToHealpix(torch.autograd.Function):
+    """`Projector.to_healpix` for autograd, MAP input: (B, P, Nx, Ny) -> (B, P, npix); backward is `cmbl_project_to_healpix_adjoint`"""
+
+    @staticmethod
+    def forward(ctx, arr, projector):
+        ctx.projector = projector
+        return projector._to_healpix_raw(arr, MAP, int(arr.shape[1]), int(arr.shape[0]))
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        return ctx.projector._to_healpix_adjoint_raw(g, int(g.shape[1]), int(g.shape[0])), None
+
+
+def _pair(field, other_proj, method, projector):
+    """the checks `project` and `project_adjoint` share: (projector, is the field on the sphere)"""
+    _method(method)
+    on_sphere = isinstance(field, HealpixField)
+    if on_sphere == isinstance(other_proj, ProjHealpix):
+        raise TypeError("project: HealpixField => ProjLambert | ProjEquiRect, or Field | EquiRectField => ProjHealpix")
+    hpx, cart = (field.proj, other_proj) if on_sphere else (other_proj, field.proj)
+    if projector is None:
+        projector = Projector(hpx, cart, method)
+    elif projector.hpx_proj != hpx or (projector.cart_proj is not cart and projector.cart_proj != cart):
+        raise ValueError("project: the projector was built for another pair of projections")           # the @assert of :222, 309
+    elif projector.method != method:
+        raise ValueError(f"project: the projector was built for method {projector.method!r}, not {method!r}")   # Projector{method} (:221, 229)
+    return projector, on_sphere
 
 
 def project(field, target_proj, method="bilinear", projector=None):
@@ -229,15 +339,15 @@ def project(field, target_proj, method="bilinear", projector=None):
     HealpixField lands on `target_proj` (ProjLambert or ProjEquiRect) as a MAP Field / EquiRectField; a Field or EquiRectField lands on the
     sphere as a HealpixField, exactly 0 outside the patch.  QU and IQU fields have their polarisation rotated into the local basis.
     `method`: "bilinear" or "nfft" (module docstring).  `projector`: a cached `Projector` of the same pair and the same method."""
-    _method(method)
-    to_cart = isinstance(field, HealpixField)
-    if to_cart == isinstance(target_proj, ProjHealpix):
-        raise TypeError("project: HealpixField => ProjLambert | ProjEquiRect, or Field | EquiRectField => ProjHealpix")
-    hpx, cart = (field.proj, target_proj) if to_cart else (target_proj, field.proj)
-    if projector is None:
-        projector = Projector(hpx, cart, method)
-    elif projector.hpx_proj != hpx or (projector.cart_proj is not cart and projector.cart_proj != cart):
-        raise ValueError("project: the projector was built for another pair of projections")           # the @assert of :222, 309
-    elif projector.method != method:
-        raise ValueError(f"project: the projector was built for method {projector.method!r}, not {method!r}")   # Projector{method} (:221, 229)
+    projector, to_cart = _pair(field, target_proj, method, projector)
     return projector.to_cart(field) if to_cart else projector.to_healpix(field)
+
+
+def project_adjoint(g, source_proj, method="bilinear", projector=None):
+    """The transpose (pullback) of `project(., g's projection)` for an input that lived on `source_proj`: a cotangent on the sphere
+    (HealpixField) comes back to the Cartesian `source_proj` as a MAP Field / EquiRectField (`Projector.to_healpix_adjoint`), a cotangent on
+    a patch (MAP Field / EquiRectField) comes back to `source_proj = ProjHealpix(Nside)` as a HealpixField (`Projector.to_cart_adjoint`).
+    The same pair / method / projector checks as `project`.  This is what autograd runs when `project` is given a field whose tensor has
+    `requires_grad`."""
+    projector, on_sphere = _pair(g, source_proj, method, projector)
+    return projector.to_healpix_adjoint(g) if on_sphere else projector.to_cart_adjoint(g)

@@ -123,6 +123,8 @@ SIGNATURES = {
     "cmbl_projector_info_host": [_vp, _ci, _pd, _sz],
     "cmbl_project_to_cart": [_vp, _vp, _vp, _ci, _ci],
     "cmbl_project_to_healpix": [_vp, _ci, _vp, _vp, _ci, _ci],
+    "cmbl_project_to_cart_adjoint": [_vp, _vp, _vp, _ci, _ci],
+    "cmbl_project_to_healpix_adjoint": [_vp, _vp, _vp, _ci, _ci],
 }
 SYMBOLS = list(OTHER_RETURNS) + list(SIGNATURES)
 

@@ -590,7 +590,7 @@ int cmbl_quadratic_estimate(cmbl_dataset* ds, int which, const double* Cf_host, 
  *      arrays of the context's dtype, npix = 12 Nside^2 fastest: the reference's (npix, npol) plus the batch axis.  npol = 1 (I), 2 (QU),
  *      3 (IQU); QU are rotated by the angle psi between the two coordinate bases ("polarization flattening", :238-252, 327-341).
  *      ALL geometry is double on the device whatever the context's dtype (the reference computes it in T); values, weights and
- *      cos 2 psi / sin 2 psi are of the context's dtype.  NOT here: NEST ordering, the AD rules.
+ *      cos 2 psi / sin 2 psi are of the context's dtype.  NOT here: NEST ordering.
  *
  *      The METHOD belongs to the projector (the reference's Projector{method}); cmbl_project_to_cart / _to_healpix dispatch on it.
  *      CMBL_PROJECT_BILINEAR is described below.  CMBL_PROJECT_NFFT is method = :fft (:229-236, 314-325), a non-uniform FFT: with
@@ -616,7 +616,25 @@ int cmbl_quadratic_estimate(cmbl_dataset* ds, int which, const double* Cf_host, 
  *   their fractional (i, j) (1-based like the reference's) and psi.
  * project_to_cart: hpx (npix, npol, nbatch) -> map_out MAP (Ny, Nx, npol, nbatch): healpy.get_interp_val at the pixel centres.
  * project_to_healpix: `in` in basis_in (converted to MAP first; a ProjEquiRect context takes MAP only) -> hpx_out (npix, npol, nbatch):
- *   Images.bilinear_interpolation, a corner outside the map counts as zero.  Neither call synchronises. */
+ *   Images.bilinear_interpolation, a corner outside the map counts as zero.  Neither call synchronises.
+ *
+ * The transposes (pullbacks) of the two calls, for either method (the call dispatches on the projector's).  Maps are MAP basis,
+ * (Ny, Nx, npol, nbatch); HEALPix arrays (npix, npol, nbatch); both of the context's dtype.  With c, s = cos 2 psi, sin 2 psi at the pixel named,
+ * Rc: Q' = Q c - U s, U' = U c + Q s (:243-244) and Rh: Q' = Q c + U s, U' = U c - Q s (:332-333) acting on the last two planes when
+ * npol >= 2 (Rc^T has the form of Rh and Rh^T that of Rc, each at its own psi):
+ *   bilinear, project_to_cart (m[c] = Rc(psi_c) sum_k w[c][k] h[pix[c][k]]):
+ *     project_to_cart_adjoint     hbar[p] = sum_{(c, k): pix[c][k] = p} w[c][k] (Rc(psi_c)^T mbar[c]); exactly 0 at a pixel no Cartesian pixel
+ *                                 reads; duplicates in pix[c][.] (polar caps) are separate entries and are summed.
+ *   bilinear, project_to_healpix (h[p_t] = Rh(psi_t) sum_corners v[t][k] m[c_tk] over the touched pixels, corners outside the map dropped):
+ *     project_to_healpix_adjoint  mbar[c] = sum_{(t, k): c_tk = c} v[t][k] (Rh(psi_t)^T hbar[p_t]); every map pixel is written, one without
+ *                                 entries gets 0; cotangent values at untouched pixels are ignored (the forward is constant 0 there).
+ *   nfft:
+ *     project_to_healpix_adjoint  mbar_g = 1/(Ny Nx) sum_{p in patch} K(x_p - x_g) (Rh(psi_p)^T hbar)_p
+ *     project_to_cart_adjoint     hbar_p = 1/Npatch sum_g K(x_g - x_p) (Rc(psi_g)^T mbar)_g on hpx_idxs_in_patch, exactly 0 elsewhere.
+ * The bilinear rows are summed by ascending input pixel, then corner, in the context's dtype with one fma per entry and no atomics: results
+ * are bit-identical between runs.  The transposed tables are built on the first adjoint call of each direction (that call synchronises once)
+ * and cached in the projector; after that neither call synchronises.  The input is never modified.  npol outside 1 ... 3 or nbatch < 1 is
+ * CMBL_ERR_SHAPE, as for the forward calls. */
 typedef struct cmbl_projector cmbl_projector;
 enum { CMBL_PROJ_LAMBERT = 0, CMBL_PROJ_EQUIRECT = 1 };
 enum { CMBL_PROJECT_BILINEAR = 0, CMBL_PROJECT_NFFT = 1 };
@@ -630,6 +648,8 @@ int cmbl_projector_method(cmbl_projector* P, int* method, int* window_width);
 int cmbl_projector_info_host(cmbl_projector* P, int which, double* out_host, size_t n);
 int cmbl_project_to_cart(cmbl_projector* P, const void* hpx, void* map_out, int npol, int nbatch);
 int cmbl_project_to_healpix(cmbl_projector* P, int basis_in, const void* in, void* hpx_out, int npol, int nbatch);
+int cmbl_project_to_cart_adjoint(cmbl_projector* P, const void* map_cot, void* hpx_out, int npol, int nbatch);
+int cmbl_project_to_healpix_adjoint(cmbl_projector* P, const void* hpx_cot, void* map_out, int npol, int nbatch);
 
 #ifdef __cplusplus
 }
