@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include <stdexcept>
+#include "status.hpp"
 
 namespace cmbl {
 
@@ -31,7 +32,6 @@ __device__ __forceinline__ int brev(int i, int bits) { return bits == 0 ? 0 : (i
 
 // ---- error plumbing: never throw across the C ABI -------------------------------------------
 extern thread_local std::string g_last_error;
-enum Status { OK = 0, ERR_ARG = 1, ERR_SHAPE = 2, ERR_HIP = 3, ERR_NAN = 4, ERR_STATE = 5, ERR_ALLOC = 6 };
 
 struct Error { int code; std::string msg; };
 [[noreturn]] inline void fail(int code, const std::string& m) { throw Error{code, m}; }

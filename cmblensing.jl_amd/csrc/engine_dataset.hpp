@@ -2,36 +2,13 @@
 // with its gradients.  Included by api_decl.hpp and drivers.hpp.
 #pragma once
 #include "engine.hpp"
+#include "engine_cg.hpp"
 
 namespace cmbl {
 
 // =================================================================================================
 // Data model, Wiener filter, posterior   (src/dataset.jl, src/maximization.jl, src/numerical_algorithms.jl)
 enum OpId { OP_CF_INV = 0, OP_CN_INV, OP_B, OP_MF, OP_D, OP_D_INV, OP_PRECOND_INV, OP_CPHI_INV, OP_G_INV, OP_MPIX, OP_COUNT };
-
-// The host's view of a CG's device-resident flags, shared by every solver that keeps its scalars on the device (Dataset::wiener_cg, EqDataset::wiener_cg):
-// two pinned slots of up to 8 ints and an event each.  post: copy the flags after what has been enqueued and mark the point; wait: the flags as
-// they were at that point, without draining the stream -- the host reads the stop flag of iteration i - 1 while iteration i runs.
-struct CgFlagMirror {
-  int* host = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  CgFlagMirror() = default;
-  CgFlagMirror(const CgFlagMirror&) = delete; CgFlagMirror& operator=(const CgFlagMirror&) = delete;
-  ~CgFlagMirror() {
-    if (host) (void)hipHostFree(host);
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-  }
-  void ensure() {
-    if (host) return;
-    CMBL_HIP(hipHostMalloc((void**)&host, sizeof(int) * 16, hipHostMallocDefault));
-    for (auto& e : ev) CMBL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  void post(int slot, const int* flags_dev, int nflag, hipStream_t stream) {
-    CMBL_HIP(hipMemcpyAsync(host + 8 * slot, flags_dev, sizeof(int) * nflag, hipMemcpyDeviceToHost, stream));
-    CMBL_HIP(hipEventRecord(ev[slot], stream));
-  }
-  const int* wait(int slot) { CMBL_HIP(hipEventSynchronize(ev[slot])); return host + 8 * slot; }
-};
 
 struct DatasetApi {                        // what the C ABI (api.hip) holds of a dataset (see FlowApi)
   double logdet_sum = 0;
@@ -48,9 +25,9 @@ struct Dataset : DatasetApi {
   Op ops[OP_COUNT];
   DevBuf d_h; int Bd = 0;                  // data, F layout harmonic
   // scratch
-  DevBuf t1, t2, t3, mp, mp2, xs, rs, zs, ps, aps, best, bb, phiF, gphi, dphi1, dphi2, fh, fhat, ftil, cvt;
+  DevBuf t1, t2, t3, mp, mp2, phiF, gphi, dphi1, dphi2, fh, fhat, ftil, cvt;
 
-  Dataset(Ctx<T>* ctx, int npol) : c(ctx), P(npol) { CMBL_REQUIRE(npol >= 1 && npol <= 3, ERR_ARG, "npol must be 1, 2 or 3"); }
+  Dataset(Ctx<T>* ctx, int npol) : c(ctx), P(npol), cg(ctx) { CMBL_REQUIRE(npol >= 1 && npol <= 3, ERR_ARG, "npol must be 1, 2 or 3"); }
 
   void set_op(int which, const void* planes, int nplanes) override {
     CMBL_REQUIRE(which >= 0 && which < OP_COUNT, ERR_ARG, "bad operator id");
@@ -229,60 +206,26 @@ struct Dataset : DatasetApi {
 
   // conjugate_gradient (src/numerical_algorithms.jl:73-134) driving argmaxf_logpdf (src/maximization.jl:17-42).
   // a0 = gradientf(f=0,d=0) is identically zero for this linear model (all operators finite), so it is not evaluated.
-  // The scalars (res, alpha, beta, best residual, history, stop flag) live on the device (CgState): an iteration is enqueued
-  // without waiting for its reductions; the host reads the stop flag of iteration i-1 while iteration i runs.
-  DevBuf cg_scal, cg_hist, qdev, cg_rzfin;
-  CgFlagMirror cg_flags;                       // pinned: [slot][up to 8 flags]
-  // What the two forms of the iteration share.  cg_begin: the vectors, the scalar block (`sd`; its ints follow nd doubles per slot), the
-  // pinned flags and their events, b = -gradientf(f=0, d), the start iterate x and r = b - A x.  cg_end: the best iterate, the history and
-  // the NaN check.  The flag blocks differ (CgScal: 6 ints, `done` and `better` by parity; CgState: 4 ints), so they are given as `nflag`
-  // ints at `flags` with the NaN flag at index i_nan and the length of the history at i_nh.
-  struct CgVecs { long n, nr; cx<T>*x, *r, *z, *p, *Ap, *bx, *b; double* sd; int* si; double* hist; };
-  CgVecs cg_begin(LensOps<T>& L, const cx<T>* dd, const cx<T>* fstart, int maxit, int nd, int B) {
-    CgVecs v;
-    v.n = fsize(B); v.nr = 2 * v.n / B;
-    DevBuf* const bufs[7] = {&xs, &rs, &zs, &ps, &aps, &best, &bb};
-    for (DevBuf* d : bufs) d->ensure(sizeof(cx<T>) * v.n);
-    v.x = xs.template as<cx<T>>(); v.r = rs.template as<cx<T>>(); v.z = zs.template as<cx<T>>(); v.p = ps.template as<cx<T>>();
-    v.Ap = aps.template as<cx<T>>(); v.bx = best.template as<cx<T>>(); v.b = bb.template as<cx<T>>();
+  // The scalars (res, alpha, beta, best residual, history, stop flag) live on the device; the loop, its storage and its end are CgSolver's (engine_cg.hpp).
+  DevBuf qdev, cg_rzfin;
+  CgSolver<T> cg;
+  // What the two forms of the iteration share on top of the solver: b = -gradientf(f=0, d) = -L'B'M'Cn^-1 d, the start iterate x and r = b - A x
+  // with A = gradientf(., d = 0): both sides carry the sign of the gradient.  nd: doubles per slot of the scalar block (CgState 6, CgScal 7).
+  auto cg_A(LensOps<T>& L, int B) { return [this, &L, B](const cx<T>* p, cx<T>* Ap, double* pAp) { gradientf(L, p, nullptr, Ap, B); if (pAp) c->dot_F_dev(p, Ap, P, B, pAp); }; }
+  typename CgSolver<T>::Vecs cg_problem(LensOps<T>& L, const cx<T>* dd, const cx<T>* fstart, int maxit, int nd, int B) {
     CMBL_REQUIRE(B <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
-    cg_scal.ensure(sizeof(double) * nd * MAXBATCH + sizeof(int) * 8);
-    cg_hist.ensure(sizeof(double) * (size_t)maxit * B);
-    cg_flags.ensure();
-    v.sd = cg_scal.template as<double>(); v.si = reinterpret_cast<int*>(v.sd + nd * MAXBATCH); v.hist = cg_hist.template as<double>();
-    hipStream_t sm = c->stream;
-    std::vector<double> one(B, 1.0), mone(B, -1.0);
-    // b = -gradientf(f=0, d) = -L'B'M'Cn^-1 d
+    const auto v = cg.begin(fsize(B), B, maxit, nd);
+    std::vector<double> mone(B, -1.0);
     gradientf(L, nullptr, dd, v.b, B);
     c->lincomb((T*)v.b, (T*)v.b, nullptr, mone.data(), nullptr, v.nr, B);
-    if (fstart) {
-      CMBL_HIP(hipMemcpyAsync(v.x, fstart, sizeof(cx<T>) * v.n, hipMemcpyDeviceToDevice, sm));
-      gradientf(L, v.x, nullptr, v.Ap, B);                                          // A x
-      c->lincomb((T*)v.r, (T*)v.b, (T*)v.Ap, one.data(), mone.data(), v.nr, B);     // r = b - A x
-    } else {
-      CMBL_HIP(hipMemsetAsync(v.x, 0, sizeof(cx<T>) * v.n, sm));
-      CMBL_HIP(hipMemcpyAsync(v.r, v.b, sizeof(cx<T>) * v.n, hipMemcpyDeviceToDevice, sm));
-    }
+    cg.start(v, fstart, cg_A(L, B));
     return v;
-  }
-  void cg_post_flags(int slot, const int* flags, int nflag) { cg_flags.post(slot, flags, nflag, c->stream); }
-  const int* cg_wait_flags(int slot) { return cg_flags.wait(slot); }
-  int cg_end(const CgVecs& v, cx<T>* f_out, double* hist, const int* flags, int nflag, int i_nan, int i_nh, int B) {
-    hipStream_t sm = c->stream;
-    CMBL_HIP(hipMemcpyAsync(f_out, v.bx, sizeof(cx<T>) * v.n, hipMemcpyDeviceToDevice, sm));
-    int fl[8];
-    CMBL_HIP(hipMemcpyAsync(fl, flags, sizeof(int) * nflag, hipMemcpyDeviceToHost, sm));
-    CMBL_HIP(hipStreamSynchronize(sm));
-    const int nh = fl[i_nh];
-    CMBL_HIP(hipMemcpy(hist, v.hist, sizeof(double) * (size_t)nh * B, hipMemcpyDeviceToHost));
-    CMBL_REQUIRE(fl[i_nan] == 0, ERR_NAN, "NaN residual in conjugate gradient");
-    return nh;
   }
   // Fused form of the same iteration (a LenseFlow on a power-of-two map): per iteration the two flows, 7 launches between them (basis change + ifft_x,
   // c2r, beam, mask, Fourier mask / Cn^-1 / Fourier mask', mask', beam' + ifft_x) and 3 after them (A p and p'Ap -> alpha; x, r, r'z ->
   // beta and the stop test; p and the best iterate).  Every scalar is produced by the launch that produced its sum.
   int wiener_cg_fused(Flow<T>& L, const cx<T>* dd, const cx<T>* fstart, double tol, int maxit, cx<T>* f_out, double* hist, int B) {
-    const CgVecs v = cg_begin(L, dd, fstart, maxit, 7, B);
+    const auto v = cg_problem(L, dd, fstart, maxit, 7, B);
     cx<T>*x = v.x, *r = v.r, *p = v.p, *Y = v.z, *Ap = v.Ap, *bx = v.bx;
     cg_rzfin.ensure(sizeof(double) * MAXBATCH);
     CgScal st;
@@ -297,9 +240,9 @@ struct Dataset : DatasetApi {
       const DotOut o = c->pw_flat(PwCgStart<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, bx}, B, Ctx<T>::PART_CG_RZ);
       CMBL_LAUNCH(c, K_CG, (k_cg_init<T>), dim3(1), 0, sm, st, o, sc, B);
     });
-    cg_post_flags(0, st.done, 6);
+    cg.flags.post(0, st.done, 6, sm);
     int par = 0;
-    if (cg_wait_flags(0)[4] == 0) {                                         // a NaN start residual is reported below
+    if (cg.flags.wait(0)[4] == 0) {                                         // a NaN start residual is reported below
       for (int it = 2; it <= maxit; ++it) {
         model_adjoint(L, p, nullptr, B, Y, B);                              // Y = -L'B'M'Cn^-1 M B L p
         by_pol([&](auto pp) {
@@ -313,46 +256,17 @@ struct Dataset : DatasetApi {
           c->pw_flat(PwCgP<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, bx, st, par, tol, oR, sc, rzf}, B);
         });
         par ^= 1;
-        cg_post_flags(it & 1, st.done, 6);
-        if (it > 2 && cg_wait_flags((it - 1) & 1)[it & 1] != 0) break;      // previous iteration's flags: it left `done` at parity (it - 2) & 1
+        cg.flags.post(it & 1, st.done, 6, sm);
+        if (it > 2 && cg.flags.wait((it - 1) & 1)[it & 1] != 0) break;      // previous iteration's flags: it left `done` at parity (it - 2) & 1
       }
     }
-    return cg_end(v, f_out, hist, st.done, 6, 4, 5, B);
+    return cg.finish(v, f_out, hist, st.done, 6, 4, 5);
   }
   int wiener_cg(LensOps<T>& L, const cx<T>* dd, const cx<T>* fstart, double tol, int maxit, cx<T>* f_out, double* hist, int B) {
     if (Flow<T>* flow = fused() ? L.as_flow() : nullptr) return wiener_cg_fused(*flow, dd, fstart, tol, maxit, f_out, hist, B);
-    const CgVecs v = cg_begin(L, dd, fstart, maxit, 6, B);
-    const long n = v.n, nr = v.nr;
-    cx<T>*x = v.x, *r = v.r, *z = v.z, *p = v.p, *Ap = v.Ap, *bx = v.bx;
-    CgState st;
-    double* sd = v.sd;
-    st.res = sd; st.pAp = sd + MAXBATCH; st.res2 = sd + 2 * MAXBATCH; st.alpha = sd + 3 * MAXBATCH; st.beta = sd + 4 * MAXBATCH; st.best = sd + 5 * MAXBATCH;
-    st.hist = v.hist;
-    st.done = v.si; st.nan = v.si + 1; st.nh = v.si + 2; st.better = v.si + 3;
-    hipStream_t sm = c->stream;
-    const unsigned gx = (unsigned)std::min<long>((nr + NTP - 1) / NTP, 2048);
-    apply(OP_PRECOND_INV, r, z, B);
-    CMBL_HIP(hipMemcpyAsync(p, z, sizeof(cx<T>) * n, hipMemcpyDeviceToDevice, sm));
-    c->dot_F_dev(r, z, P, B, st.res);
-    CMBL_LAUNCH_NT(c, K_CG, 64, k_cg_start, dim3(1), 0, sm, st, B);
-    CMBL_HIP(hipMemcpyAsync(bx, x, sizeof(cx<T>) * n, hipMemcpyDeviceToDevice, sm));
-    cg_post_flags(0, st.done, 2);
-    if (cg_wait_flags(0)[1] == 0) {                                         // a NaN start residual is reported below
-      for (int it = 2; it <= maxit; ++it) {
-        gradientf(L, p, nullptr, Ap, B);
-        c->dot_F_dev(p, Ap, P, B, st.pAp);
-        CMBL_LAUNCH_NT(c, K_CG, 64, k_cg_alpha, dim3(1), 0, sm, st, B);
-        CMBL_LAUNCH(c, K_CG, (k_cg_xr<T>), dim3(gx, B), 0, sm, (T*)x, (T*)r, (const T*)p, (const T*)Ap, st, nr);
-        apply(OP_PRECOND_INV, r, z, B);
-        c->dot_F_dev(r, z, P, B, st.res2);
-        CMBL_LAUNCH_NT(c, K_CG, 64, k_cg_beta, dim3(1), 0, sm, st, B, tol);
-        CMBL_LAUNCH(c, K_CG, (k_cg_p<T>), dim3(gx, B), 0, sm, (T*)p, (const T*)z, st, nr);
-        CMBL_LAUNCH(c, K_CG, (k_cg_keep_best<T>), dim3(gx), 0, sm, (T*)bx, (const T*)x, st, 2 * n);
-        cg_post_flags(it & 1, st.done, 2);
-        if (it > 2 && cg_wait_flags((it - 1) & 1)[0] != 0) break;           // flags of the previous iteration
-      }
-    }
-    return cg_end(v, f_out, hist, st.done, 4, 1, 2, B);
+    const auto v = cg_problem(L, dd, fstart, maxit, 6, B);
+    cg.solve(v, cg_A(L, B), [&](const cx<T>* r, cx<T>* z, double* rz) { apply(OP_PRECOND_INV, r, z, B); c->dot_F_dev(r, z, P, B, rz); }, tol);
+    return cg.finish(v, f_out, hist, v.si, 4, 1, 2);
   }
 
   // What grad_logpdf and the composed logpdf_mixed share, for nphi planes of phi (1, or one per slot):  z = M B L f - d with f~ = L f left in

@@ -18,8 +18,8 @@
 //   z = P^-1 r, partials of r'z              k_eqds_apply2                    |P^-1|
 //   r'z ; beta, history, stop and best flags k_eqds_dot_fin, k_cg_beta
 //   p = z + beta p ; bestx = x if better     k_cg_p, k_cg_keep_best
-// Cn block-diagonal: the middle line becomes  -> map, *= M, -> Az, Cn^-1 (k_eqds_apply2, |Cn^-1|), -> map, *= M, -> Az.  The scalars, the history
-// and the flags live on the device (CgState); the host reads the stop flag of iteration i - 1 while iteration i runs.
+// Cn block-diagonal: the middle line becomes  -> map, *= M, -> Az, Cn^-1 (k_eqds_apply2, |Cn^-1|), -> map, *= M, -> Az.  The loop, with its scalars, history and
+// flags on the device, is CgSolver<T>::solve (engine_cg.hpp, shared with the flat-sky solver): this file forms b and supplies A p (hess) and z = P^-1 r (apply1) with their dots.
 #pragma once
 #include "engine.hpp"
 #include "engine_equirect.hpp"
@@ -28,8 +28,6 @@
 #include "kernels_equirect_ds.hpp"
 
 namespace cmbl {
-
-static_assert(EQDS_ERR_ARG == ERR_ARG && EQDS_ERR_SHAPE == ERR_SHAPE && EQDS_ERR_NAN == ERR_NAN && EQDS_ERR_STATE == ERR_STATE && EQDS_MAXBATCH == MAXBATCH, "eqds_host.hpp restates cmbl::Status");
 
 struct EqDatasetApi {                      // what the C ABI (api.hip) holds of such a data set: precision-free, pointers untyped
   double logdet_sum = 0;
@@ -67,10 +65,10 @@ struct EqDataset : EqDatasetApi {
   Ctx<T>* c;
   EqdsBook bk;
   DevBuf pix[EQDS_NPIXOP], Wb, MCb;        // owned copies of the map-diagonal planes; W = M Cn^-1 M and M Cn^-1 (pixel form of Cn)
-  DevBuf xs, rs, zs, ps, aps, best, bb, t1, t2, mp, parts, scal, histb, q2;   // scratch, grown on demand
-  CgFlagMirror flags;                      // the host's view of the solver's flags (engine_dataset.hpp)
+  DevBuf t1, t2, mp, parts, q2;            // scratch, grown on demand
+  CgSolver<T> cg;                          // the CG vectors, scalars, flags and loop (engine_cg.hpp)
 
-  EqDataset(Ctx<T>* ctx, int npol) : c(ctx) { std::string m; const int rc = bk.init(ctx->Ny, ctx->Nx, npol, m); if (rc) fail(rc, m); }
+  EqDataset(Ctx<T>* ctx, int npol) : c(ctx), cg(ctx) { std::string m; const int rc = bk.init(ctx->Ny, ctx->Nx, npol, m); if (rc) fail(rc, m); }
   int P() const { return bk.P; }
   int n() const { return bk.n(); }
   int Mh() const { return c->Nx / 2 + 1; }
@@ -213,68 +211,19 @@ struct EqDataset : EqDatasetApi {
     for (int b = 0; b < B; ++b) lp[b] = -0.5 * (h[b] + h[B + b] + logdet_sum);
   }
 
-  // conjugate_gradient (src/numerical_algorithms.jl:73-134) on A = Cf^-1 + B'M'Cn^-1 M B, b = B'M'Cn^-1 d, with the semantics of cmbl_wiener_cg:
+  // conjugate_gradient (CgSolver, engine_cg.hpp) on A = Cf^-1 + B'M'Cn^-1 M B, b = B'M'Cn^-1 d, with the semantics of cmbl_wiener_cg:
   // res = dot(r, z), stop when all(res < tol), the best-res iterate is returned, a NaN residual is ERR_NAN.  Returns the length of the history.
   int wiener_cg(const void* dv, const void* fstart, double tol, int maxit, void* f_out, double* hist, int B) override {
     require(B, true, true); scratch(B); weights();
-    const long na = azsize(B), nr = 2 * na / B;
-    DevBuf* const bufs[7] = {&xs, &rs, &zs, &ps, &aps, &best, &bb};
-    for (DevBuf* d : bufs) d->ensure(sizeof(cx<T>) * na);
-    cx<T>*x = xs.template as<cx<T>>(), *r = rs.template as<cx<T>>(), *z = zs.template as<cx<T>>(), *p = ps.template as<cx<T>>(), *Ap = aps.template as<cx<T>>(),
-         *bx = best.template as<cx<T>>(), *b = bb.template as<cx<T>>();
-    scal.ensure(sizeof(double) * 6 * MAXBATCH + sizeof(int) * 4);
-    histb.ensure(sizeof(double) * (size_t)maxit * B);
-    flags.ensure();
-    double* sd = scal.template as<double>();
-    int* si = reinterpret_cast<int*>(sd + 6 * MAXBATCH);
-    CgState st;
-    st.res = sd; st.pAp = sd + MAXBATCH; st.res2 = sd + 2 * MAXBATCH; st.alpha = sd + 3 * MAXBATCH; st.beta = sd + 4 * MAXBATCH; st.best = sd + 5 * MAXBATCH;
-    st.hist = histb.template as<double>();
-    st.done = si; st.nan = si + 1; st.nh = si + 2; st.better = si + 3;
-    hipStream_t sm = c->stream;
-    const unsigned gx = (unsigned)std::min<long>((nr + NTP - 1) / NTP, 2048);
-    // b = B' M' Cn^-1 d
-    T* map = mp.template as<T>();
-    CMBL_HIP(hipMemcpyAsync(map, dv, sizeof(T) * mapsize(B), hipMemcpyDeviceToDevice, sm));
+    const auto v = cg.begin(azsize(B), B, maxit, 6);
+    T* map = mp.template as<T>();                                            // b = B' M' Cn^-1 d
+    CMBL_HIP(hipMemcpyAsync(map, dv, sizeof(T) * mapsize(B), hipMemcpyDeviceToDevice, c->stream));
     weigh_back(map, t1.template as<cx<T>>(), B);
-    beam_adj(t1.template as<cx<T>>(), b, B);
-    if (fstart) {
-      copy_az(x, (const cx<T>*)fstart, B);
-      hess(x, Ap, nullptr, B);
-      std::vector<double> one(B, 1.0), mone(B, -1.0);
-      c->lincomb((T*)r, (const T*)b, (const T*)Ap, one.data(), mone.data(), nr, B);      // r = b - A x
-    } else {
-      CMBL_HIP(hipMemsetAsync(x, 0, sizeof(cx<T>) * na, sm));
-      copy_az(r, b, B);
-    }
-    apply1(EQDS_PRECOND_INV, false, T(1), r, z, r, st.res, B);
-    copy_az(p, z, B);
-    CMBL_LAUNCH_NT(c, K_CG, 64, k_cg_start, dim3(1), 0, sm, st, B);
-    copy_az(bx, x, B);
-    flags.post(0, st.done, 4, sm);
-    if (flags.wait(0)[1] == 0) {                                             // a NaN start residual is reported below
-      for (int it = 2; it <= maxit; ++it) {
-        hess(p, Ap, st.pAp, B);
-        CMBL_LAUNCH_NT(c, K_CG, 64, k_cg_alpha, dim3(1), 0, sm, st, B);
-        CMBL_LAUNCH(c, K_CG, (k_cg_xr<T>), dim3(gx, (unsigned)B), 0, sm, (T*)x, (T*)r, (const T*)p, (const T*)Ap, st, nr);
-        apply1(EQDS_PRECOND_INV, false, T(1), r, z, r, st.res2, B);
-        CMBL_LAUNCH_NT(c, K_CG, 64, k_cg_beta, dim3(1), 0, sm, st, B, tol);
-        CMBL_LAUNCH(c, K_CG, (k_cg_p<T>), dim3(gx, (unsigned)B), 0, sm, (T*)p, (const T*)z, st, nr);
-        CMBL_LAUNCH(c, K_CG, (k_cg_keep_best<T>), dim3(gx), 0, sm, (T*)bx, (const T*)x, st, 2 * na);
-        flags.post(it & 1, st.done, 4, sm);
-        if (it > 2 && flags.wait((it - 1) & 1)[0] != 0) break;               // flags of the previous iteration
-      }
-    }
-    CMBL_HIP(hipMemcpyAsync(f_out, bx, sizeof(cx<T>) * na, hipMemcpyDeviceToDevice, sm));
-    int fl[4];
-    std::vector<double> hh((size_t)maxit * B);
-    CMBL_HIP(hipMemcpyAsync(fl, st.done, sizeof(int) * 4, hipMemcpyDeviceToHost, sm));
-    CMBL_HIP(hipMemcpyAsync(hh.data(), st.hist, sizeof(double) * hh.size(), hipMemcpyDeviceToHost, sm));
-    CMBL_HIP(hipStreamSynchronize(sm));
-    int nit = 0; std::string m;
-    const int rc = eqds_cg_finish(fl, hh.data(), maxit, B, hist, &nit, m);
-    if (rc) fail(rc, m);
-    return nit;
+    beam_adj(t1.template as<cx<T>>(), v.b, B);
+    auto A = [&](const cx<T>* p, cx<T>* Ap, double* pAp) { hess(p, Ap, pAp, B); };
+    cg.start(v, (const cx<T>*)fstart, A);
+    cg.solve(v, A, [&](const cx<T>* r, cx<T>* z, double* rz) { apply1(EQDS_PRECOND_INV, false, T(1), r, z, r, rz, B); }, tol);
+    return cg.finish(v, (cx<T>*)f_out, hist, v.si, 4, 1, 2);
   }
 };
 

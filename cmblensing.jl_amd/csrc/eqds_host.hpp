@@ -1,15 +1,14 @@
-// Host-side bookkeeping of EqDataset<T> (engine_equirect_ds.hpp) that touches no device: which operators are set, the shape and state checks of
-// the entry points, and the end of a CG solve (flags and history).  Plain C++, no HIP header, so that a stand-alone program can exercise it under
-// the host sanitizers (tests/c_abi/eqds_host.cpp).  The codes are those of cmbl::Status / CMBL_ERR_*.
+// Host-side bookkeeping of EqDataset<T> (engine_equirect_ds.hpp) that touches no device: which operators are set, and the shape and state checks
+// of the entry points.  Plain C++, no HIP header, so that a stand-alone program can exercise it under the host sanitizers
+// (tests/c_abi/eqds_host.cpp, which also covers the end of a solve, cg_host.hpp).  The codes are cmbl::Status (status.hpp).
 #pragma once
 #include <string>
+#include "status.hpp"
 
 namespace cmbl {
 
-enum { EQDS_OK = 0, EQDS_ERR_ARG = 1, EQDS_ERR_SHAPE = 2, EQDS_ERR_NAN = 4, EQDS_ERR_STATE = 5 };
 enum { EQDS_CF_INV = 0, EQDS_B = 1, EQDS_PRECOND_INV = 2, EQDS_CN_INV = 3, EQDS_NBLOCK = 4 };   // CMBL_EQDS_* block operators
 enum { EQDS_MASK = 0, EQDS_CN_INV_PIX = 1, EQDS_NPIXOP = 2 };                                    // CMBL_EQDS_* map-diagonal operators
-constexpr int EQDS_MAXBATCH = 256;
 
 struct EqdsBook {
   int Ny = 0, Nx = 0, P = 0;
@@ -19,51 +18,40 @@ struct EqdsBook {
 
   int n() const { return P * Ny; }
   int init(int Ny_, int Nx_, int npol, std::string& msg) {
-    if (npol != 1 && npol != 2) { msg = "eqds_create: npol must be 1 (spin 0) or 2 (spin 2); IQUAzFourier has no transform in the reference"; return EQDS_ERR_ARG; }
-    if (npol == 2 && Nx_ % 2) { msg = "eqds_create: QUAzFourier needs an even Nx (src/proj_equirect.jl:166)"; return EQDS_ERR_SHAPE; }
+    if (npol != 1 && npol != 2) { msg = "eqds_create: npol must be 1 (spin 0) or 2 (spin 2); IQUAzFourier has no transform in the reference"; return ERR_ARG; }
+    if (npol == 2 && Nx_ % 2) { msg = "eqds_create: QUAzFourier needs an even Nx (src/proj_equirect.jl:166)"; return ERR_SHAPE; }
     Ny = Ny_; Nx = Nx_; P = npol;
-    return EQDS_OK;
+    return OK;
   }
   int set_block(int which, const void* p, bool cplx, int n_, std::string& msg) {
-    if (which < 0 || which >= EQDS_NBLOCK) { msg = "eqds_set_block_op: bad operator id"; return EQDS_ERR_ARG; }
+    if (which < 0 || which >= EQDS_NBLOCK) { msg = "eqds_set_block_op: bad operator id"; return ERR_ARG; }
     if (!p) {
-      if (which != EQDS_B && which != EQDS_CN_INV) { msg = "eqds_set_block_op: only B and CN_INV can be unset"; return EQDS_ERR_ARG; }
+      if (which != EQDS_B && which != EQDS_CN_INV) { msg = "eqds_set_block_op: only B and CN_INV can be unset"; return ERR_ARG; }
       blk[which] = Block{};
-      return EQDS_OK;
+      return OK;
     }
-    if (n_ != n()) { msg = "eqds_set_block_op: n must be Ny for a spin-0 and 2 Ny for a spin-2 data set"; return EQDS_ERR_SHAPE; }
+    if (n_ != n()) { msg = "eqds_set_block_op: n must be Ny for a spin-0 and 2 Ny for a spin-2 data set"; return ERR_SHAPE; }
     blk[which].p = p; blk[which].cplx = cplx;
-    return EQDS_OK;
+    return OK;
   }
   int set_pixel(int which, bool unset, int nplanes, std::string& msg) {
-    if (which < 0 || which >= EQDS_NPIXOP) { msg = "eqds_set_pixel_op: bad operator id"; return EQDS_ERR_ARG; }
-    if (!unset && nplanes != 1 && nplanes != P) { msg = "eqds_set_pixel_op: one plane, or one per polarisation"; return EQDS_ERR_SHAPE; }
+    if (which < 0 || which >= EQDS_NPIXOP) { msg = "eqds_set_pixel_op: bad operator id"; return ERR_ARG; }
+    if (!unset && nplanes != 1 && nplanes != P) { msg = "eqds_set_pixel_op: one plane, or one per polarisation"; return ERR_SHAPE; }
     pix_planes[which] = unset ? 0 : nplanes;
     dirty = true;
-    return EQDS_OK;
+    return OK;
   }
   bool has(int which) const { return blk[which].p != nullptr; }
   bool cn_pix() const { return pix_planes[EQDS_CN_INV_PIX] > 0; }
   // what an evaluation needs: Cf^-1 and exactly one form of Cn^-1 (the solver: the preconditioner as well); nbatch in [1, 256]
   int check(int nbatch, bool need_cn, bool need_precond, std::string& msg) const {
-    if (nbatch < 1 || nbatch > EQDS_MAXBATCH) { msg = "eqds: nbatch must lie in [1, 256]"; return EQDS_ERR_SHAPE; }
-    if (!has(EQDS_CF_INV)) { msg = "eqds: the operator CF_INV has not been set"; return EQDS_ERR_STATE; }
-    if (need_cn && has(EQDS_CN_INV) && cn_pix()) { msg = "eqds: both forms of Cn^-1 are set (CN_INV and CN_INV_PIX): unset one"; return EQDS_ERR_STATE; }
-    if (need_cn && !has(EQDS_CN_INV) && !cn_pix()) { msg = "eqds: no form of Cn^-1 has been set (CN_INV or CN_INV_PIX)"; return EQDS_ERR_STATE; }
-    if (need_precond && !has(EQDS_PRECOND_INV)) { msg = "eqds: the operator PRECOND_INV has not been set"; return EQDS_ERR_STATE; }
-    return EQDS_OK;
+    if (nbatch < 1 || nbatch > MAXBATCH) { msg = "eqds: nbatch must lie in [1, 256]"; return ERR_SHAPE; }
+    if (!has(EQDS_CF_INV)) { msg = "eqds: the operator CF_INV has not been set"; return ERR_STATE; }
+    if (need_cn && has(EQDS_CN_INV) && cn_pix()) { msg = "eqds: both forms of Cn^-1 are set (CN_INV and CN_INV_PIX): unset one"; return ERR_STATE; }
+    if (need_cn && !has(EQDS_CN_INV) && !cn_pix()) { msg = "eqds: no form of Cn^-1 has been set (CN_INV or CN_INV_PIX)"; return ERR_STATE; }
+    if (need_precond && !has(EQDS_PRECOND_INV)) { msg = "eqds: the operator PRECOND_INV has not been set"; return ERR_STATE; }
+    return OK;
   }
 };
-
-// End of a solve.  flags = (done, nan, nh, better) as the device left them; hist_dev_copy: maxit * B doubles read back from the device.  Copies the
-// nh recorded residual vectors to hist_out, sets *nit and reports a NaN residual (src/numerical_algorithms.jl:94).
-inline int eqds_cg_finish(const int* flags, const double* hist_dev_copy, int maxit, int B, double* hist_out, int* nit, std::string& msg) {
-  const int nh = flags[2];
-  if (nh < 0 || nh > maxit) { msg = "eqds_wiener_cg: corrupt history length"; return EQDS_ERR_STATE; }
-  for (long i = 0; i < (long)nh * B; ++i) hist_out[i] = hist_dev_copy[i];
-  *nit = nh;
-  if (flags[1] != 0) { msg = "NaN residual in conjugate gradient"; return EQDS_ERR_NAN; }
-  return EQDS_OK;
-}
 
 }  // namespace cmbl

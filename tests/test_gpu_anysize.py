@@ -52,6 +52,56 @@ def test_dataset_gradientf_and_wiener(prec, pol, Nside):
     TP.test_dataset_gradientf_and_wiener(prec, pol, Nside, True)
 
 
+@pytest.mark.parametrize("prec,Nside,nsteps", [("f64", (36, 60), 13), ("f32", (45, 27), 11)])
+def test_wiener_returns_the_iterate_of_the_lowest_residual(prec, Nside, nsteps):
+    """the best-iterate rule of the CG (src/numerical_algorithms.jl:111-114; k_cg_beta / k_cg_keep_best, driven by CgSolver::solve) on the plain
+    any-size path: I maps with a pixel mask, theta = 3', 3' beam, B = 1, tol = 0.  In the float64 oracle the residual of the 36 x 60 case first rises at
+    index 12 (1028.34 after 1026.62), so 13 steps return the 12-step iterate, bit for bit, 8 % away from the 14-step one.  That rise of 0.17 % is too
+    close to the single-precision residual tolerance (1e-3) to fix the branch there, so single precision runs the 45 x 27 case, whose first rise is
+    14.4 % at index 10 (CPU search of the oracle over eight shapes up to 72 x 48, I and P, beams 0 / 3' / 6', 40 steps; the oracle run in float32 rises
+    by the same 14.4 % and its iterate is 1.4e-6 from the float64 one)."""
+    C, so, sd = TP._dataset_pair(prec, "I", Nside, theta=3.0, mask=True, beam=3.0, B=1)
+    ods, ds, p = so["ds"], sd["ds"], sd["proj"]
+    F = lambda a, b: C.Field(p, p.tensor(a), b)
+    ds.set_data(F(so["d"], C.HARMONIC))
+    fw_o, h_o = ods.argmaxf_logpdf(so["phi"], tol=0.0, nsteps=nsteps)
+    res_o = np.array([float(np.ravel(r)[0]) for _, r in h_o])
+    assert len(res_o) == nsteps and int(np.argmin(res_o)) == nsteps - 2, res_o                       # the case has not gone stale: the last step is a rise
+    assert prec == "f64" or res_o[-1] > 1.01 * res_o[-2], res_o                                         # fp32: ten times the residual tolerance
+    fw_g, h_g = ds.argmaxf_logpdf(F(so["phi"], C.FOURIER), tol=0.0, nsteps=nsteps)
+    fw_p, h_p = ds.argmaxf_logpdf(F(so["phi"], C.FOURIER), tol=0.0, nsteps=nsteps - 1)
+    print("oracle residuals", res_o[-3:], "device", [float(r[0]) for _, r in h_g[-3:]])
+    assert len(h_g) == nsteps and len(h_p) == nsteps - 1
+    assert torch.equal(fw_g.arr, fw_p.arr)
+    close("cg best iterate", fw_g.arr.cpu().numpy(), fw_o, 4e-6 if prec == "f32" else 1e-9)          # cgtol["x"] of TP.test_dataset_gradientf_and_wiener
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+@pytest.mark.parametrize("solver", ["flat", "equirect"])
+def test_wiener_reports_a_nan_residual(prec, solver):
+    """data that are NaN in batch slot 1 give a NaN start residual: the solve ends with CMBL_ERR_NAN (4) from cmbl_wiener_cg_op (the 36 x 60 I case
+    above with B = 2) and from cmbl_eqds_wiener_cg (case (17, 30), spin 0, B = 3 of tests/_equirect_ds_ref.py).  The kernels run to completion on
+    NaN values; this is an error return, not a fault."""
+    from cmblensing_jl_amd.lib import CmblError
+    if solver == "flat":
+        C, so, sd = TP._dataset_pair(prec, "I", (36, 60), theta=3.0, mask=True, beam=3.0, B=2)
+        p = sd["proj"]
+        d = np.array(so["d"])
+        d[1] = np.nan
+        run = lambda: sd["ds"].argmaxf_logpdf(C.Field(p, p.tensor(so["phi"]), C.FOURIER), d=C.Field(p, p.tensor(d), C.HARMONIC), tol=0.0, nsteps=4)
+    else:
+        import test_gpu_equirect_ds as TE
+        import _equirect_ds_ref as D
+        C = _pkg()
+        ds, p, o = TE.dataset(C, D.CASES[0], DT[prec][0])
+        d = np.array(o["d"])
+        d[1] = np.nan
+        run = lambda: ds.argmaxf_logpdf(TE.mp(C, p, d, DT[prec][0]), tol=0.0, nsteps=4)
+    with pytest.raises(CmblError) as e:
+        run()
+    assert e.value.code == 4 and "NaN residual" in str(e.value), str(e.value)
+
+
 @pytest.mark.parametrize("prec", ["f32", "f64"])
 @pytest.mark.parametrize("pol,Nside", [("P", (96, 160)), ("IP", (75, 45))])
 def test_logpdf_mixed_and_gradient(prec, pol, Nside):

@@ -11,8 +11,9 @@ block-diagonal and with neither beam nor mask; (33, 45) B = 1: odd Nx (no Nyquis
 several row and summation tiles; (32, 64) B = 9: the 8-slot form with a remainder.
 
 The best-iterate rule (the iterate of the lowest residual is returned) has no case here: a CPU search over seeds 0-5 of every case, from zero and
-from fstart, found no residual that rises within the 8 compared steps, so every run returns its last iterate; the rule itself is the flat-sky
-solver's kernel (k_cg_beta / k_cg_keep_best), tested there."""
+from fstart, found no residual that rises within the 8 compared steps, so every run returns its last iterate; the rule itself is the shared solver's
+(CgSolver::solve with k_cg_beta / k_cg_keep_best), tested on the flat-sky path by
+tests/test_gpu_anysize.py::test_wiener_returns_the_iterate_of_the_lowest_residual."""
 import ctypes
 import json
 import os
