@@ -12,7 +12,7 @@ from .engine import (ProjLambert, LenseFlow, BilinearLens, PowerLens, Taylens, a
 from .equirect import (ProjEquiRect, EquiRectField, BlockDiagEquiRect, AZFOURIER, Cl_to_Beam, Cl_to_Cov, simulate, equirect_geometry,   # noqa: F401
                        blocks_from_ref, blocks_to_ref, EquiRectDataSet)
 from .healpix import (ProjHealpix, HealpixField, HealpixMap, Projector, project, project_adjoint, pix2ang_ring, npix2nside)   # noqa: F401
-from .sim import (Cls, load_sim, noise_cls, beam_cls, lowpass, cl_to_2d, HarmOp, border_mask)   # noqa: F401
+from .sim import (Cls, load_sim, noise_from_white, noise_cls, beam_cls, lowpass, cl_to_2d, HarmOp, border_mask)   # noqa: F401
 from .chains import partition_chains, chain_seed, gather_chain_values, allreduce_sum   # noqa: F401
 from .drivers import (quadratic_estimate, MAP_joint, MAP_joint_step, hmc_step, sample_f, gibbs_step, symplectic_integrate,   # noqa: F401
                       mass_matrix_phi, brent_minimize, sample_joint, MAP_marg, simulate_data, hmc_step_native, MAP_joint_step_native, quadratic_estimate_native)

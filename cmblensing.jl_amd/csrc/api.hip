@@ -297,7 +297,17 @@ int cmbl_dataset_create(cmbl_ctx* ctx, int npol, cmbl_dataset** out) {
 }
 int cmbl_dataset_destroy(cmbl_dataset* ds) { return guard([&] { if (ds) registry_remove(ds); delete ds; }); }
 int cmbl_dataset_set_op(cmbl_dataset* ds, int which, const void* planes, int nplanes) {
-  return guard([&] { NOTNULL(ds); NOTNULL(planes); ds->p->set_op(which, planes, nplanes); });
+  return guard([&] {
+    NOTNULL(ds);
+    if (!(which == CMBL_OP_CN_INV_PIX && nplanes == 0)) NOTNULL(planes);      // clearing the map-diagonal noise operator takes no planes
+    ds->p->set_op(which, planes, nplanes);
+  });
+}
+int cmbl_dataset_noise_inv(cmbl_dataset* ds, const void* in, void* out, int B) {
+  return guard([&] {
+    NOTNULL(ds); NOTNULL(in); NOTNULL(out); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1");
+    BY_DTYPE(ds->ctx, do_noise_inv, ds, in, out, B);
+  });
 }
 int cmbl_dataset_set_data(cmbl_dataset* ds, const void* d, int B) {
   return guard([&] { NOTNULL(ds); NOTNULL(d); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1"); ds->p->set_data(d, B); });

@@ -70,6 +70,19 @@ template <typename T> const cx<T>* data_of(Dataset<T>& ds, const void* d, cx<T>*
   CMBL_REQUIRE(ds.Bd == B, ERR_SHAPE, "dataset data batch size differs from nbatch");
   return ds.d_h.template as<cx<T>>();
 }
+// pinv(Cn) * z with whichever form of the noise operator the data set holds (reference layout in and out, in place allowed)
+template <typename T>
+void do_noise_inv(cmbl_dataset* dsh, const void* in, void* out, int B) {
+  Dataset<T>& ds = typed<Dataset<T>>(dsh);
+  Ctx<T>* c = ds.c;
+  CMBL_REQUIRE(ds.has_noise(), ERR_STATE, "dataset_noise_inv: neither CMBL_OP_CN_INV nor CMBL_OP_CN_INV_PIX has been set");
+  const long n = ds.fsize(B);
+  ds.cvt.ensure(sizeof(cx<T>) * n);
+  cx<T>* zF = ds.cvt.template as<cx<T>>();
+  c->ref2F((const cx<T>*)in, zF, (long)ds.P * B);
+  ds.apply_cn_inv(zF, zF, B);
+  c->F2ref(zF, (cx<T>*)out, (long)ds.P * B);
+}
 // (cmbl_gradientf_logpdf and cmbl_wiener_cg come here too, with a view of their LenseFlow)
 template <typename T>
 void do_gradf_op(cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void* d, int zero_d, void* out, int B) {

@@ -66,6 +66,7 @@ namespace cmbl {
   X(T, do_dataset_create, (cmbl_dataset* h, int npol)) \
   X(T, do_bl_create, (cmbl_bilinear* h)) \
   X(T, do_pl_create, (cmbl_powerlens* h, int order, int kind)) \
+  X(T, do_noise_inv, (cmbl_dataset* dsh, const void* in, void* out, int B)) \
   X(T, do_gradf_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void* d, int zero_d, void* out, int B)) \
   X(T, do_cg_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* d, const void* fstart, double tol, int maxit, void* f_out, double* hist, int* nit, int B)) \
   X(T, do_grad_lp_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void* phi, const void* d, double* lp, void* gf, void* gphi, int B, int quirk)) \

@@ -657,6 +657,17 @@ struct Ctx : CtxBase {
                      (T)(1.0 / Ny));
     });
   }
+  // mixed -> (map x scale x weight plane of the slice) -> mixed, for the map-diagonal noise sandwich (in place allowed); slices = B * P,
+  // weight: nplanes (1 or P) maps
+  void y_weight(const cx<T>* in, cx<T>* out, const T* weight, int nplanes, int P, T scale, long slices) {
+    CMBL_REQUIRE(!generic, ERR_STATE, "fused column pass called on the any-size path");
+    const TileY t = tileY(slices, false);
+    dispatch_col(t, [&](auto lgm, auto r, auto nt) {
+      constexpr int LGM = decltype(lgm)::value, R = decltype(r)::value, NT = decltype(nt)::value;
+      CMBL_LAUNCH_NT(this, K_MASK, NT, (k_y_weight<T, R, NT, LGM>), dim3(Nx / t.C, (unsigned)slices), ldsY(t.C, false), stream, in, out, weight, nplanes, P,
+                     twY.as<cx<T>>(), Nx, (T)(scale / Ny));
+    });
+  }
   // all_slices: the slices of the whole operation when this call is one launch chain of several (the row-group height follows it)
   template <int MODE> void x_pass(const cx<T>* in, cx<T>* out, long slices, hipStream_t st = nullptr, long all_slices = 0) {
     if (!st) st = stream;
@@ -713,6 +724,11 @@ struct Ctx : CtxBase {
   void mask_mul(T* out, const T* in, const T* m, long slices) {
     const unsigned gx = (unsigned)std::min<long>((npix() + NTP - 1) / NTP, 2048);
     CMBL_LAUNCH(this, K_MASK, (k_mask_mul<T>), dim3(gx, (unsigned)slices), 0, stream, out, in, m, npix());
+  }
+  // out = scale * (weight plane of the slice) * in on maps: mask_mul with nplanes (1 or P) planes, slices = B * P
+  void weight_mul(T* out, const T* in, const T* w, int nplanes, int P, T scale, long slices) {
+    const unsigned gx = (unsigned)std::min<long>((npix() + NTP - 1) / NTP, 2048);
+    CMBL_LAUNCH(this, K_MASK, (k_weight_mul<T>), dim3(gx, (unsigned)slices), 0, stream, out, in, w, nplanes, P, scale, npix());
   }
 
   // ---- fused harmonic work (kernels_harm.hpp) -----------------------------------------------------------------------------

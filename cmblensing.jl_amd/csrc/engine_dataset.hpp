@@ -8,7 +8,7 @@ namespace cmbl {
 
 // =================================================================================================
 // Data model, Wiener filter, posterior   (src/dataset.jl, src/maximization.jl, src/numerical_algorithms.jl)
-enum OpId { OP_CF_INV = 0, OP_CN_INV, OP_B, OP_MF, OP_D, OP_D_INV, OP_PRECOND_INV, OP_CPHI_INV, OP_G_INV, OP_MPIX, OP_COUNT };
+enum OpId { OP_CF_INV = 0, OP_CN_INV, OP_B, OP_MF, OP_D, OP_D_INV, OP_PRECOND_INV, OP_CPHI_INV, OP_G_INV, OP_MPIX, OP_CN_INV_PIX, OP_COUNT };
 
 struct DatasetApi {                        // what the C ABI (api.hip) holds of a dataset (see FlowApi)
   double logdet_sum = 0;
@@ -37,6 +37,16 @@ struct Dataset : DatasetApi {
       o.buf.ensure(sizeof(T) * c->npix());
       CMBL_HIP(hipMemcpyAsync(o.buf.p, planes, sizeof(T) * c->npix(), hipMemcpyDeviceToDevice, c->stream));
       o.nplanes = 1; o.d[0] = o.buf.template as<T>(); o.kind = 1;
+      return;
+    }
+    if (which == OP_CN_INV_PIX) {            // pinv of the variance maps of Cn = Diagonal(V): one plane for all pol slices or one each; 0 planes clears it
+      CMBL_REQUIRE(nplanes == 0 || nplanes == 1 || nplanes == P, ERR_SHAPE, "the map-diagonal noise operator takes 1 or npol planes (0 clears it)");
+      CMBL_REQUIRE(nplanes == 0 || planes != nullptr, ERR_ARG, "planes is NULL");
+      o.nplanes = nplanes; o.kind = 1; o.d[0] = nullptr;
+      if (nplanes == 0) return;
+      o.buf.ensure(sizeof(T) * nplanes * c->npix());
+      CMBL_HIP(hipMemcpyAsync(o.buf.p, planes, sizeof(T) * nplanes * c->npix(), hipMemcpyDeviceToDevice, c->stream));
+      o.d[0] = o.buf.template as<T>();
       return;
     }
     const bool s0 = (which == OP_CPHI_INV || which == OP_G_INV);
@@ -73,6 +83,33 @@ struct Dataset : DatasetApi {
     cx<T>* m = c->mixed_scratch(sl);
     c->template x_pass<1>(x, m, sl); c->y_mask(m, m, ops[OP_MPIX].d[0], sl); c->template x_pass<0>(m, x, sl);
   }
+  // out = beta * pinv(Cn) in, harmonic F in and out (in place allowed), with whichever form of the noise operator is set.  Fourier form
+  // (OP_CN_INV): one launch.  Map-diagonal form (OP_CN_INV_PIX; Cn = Diagonal(V) in the I/QU map basis, src/dataset.jl:37-47): the sandwich
+  // rfft2(w .* irfft2(.)) between the two basis changes.  Power-of-two maps: three launches -- EB -> QU with ifft_x (row carrier), the column
+  // kernel (c2r, weight, r2c in LDS), fft_x with QU -> EB (row carrier).  Any size: five (basis change, irfft2, weight, rfft2, basis change).
+  void apply_cn_inv(const cx<T>* in, cx<T>* out, int B, T beta = 1) {
+    if (!has(OP_CN_INV_PIX)) { apply(OP_CN_INV, in, out, B, false, false, false, nullptr, 0, beta); return; }
+    const Op& o = ops[OP_CN_INV_PIX];
+    const long sl = (long)P * B;
+    if (c->generic) {
+      mp.ensure(sizeof(T) * sl * c->npix());
+      c->harm(in, out, P, B, 0, nullptr, false, false, true);
+      c->F_to_map(out, mp.template as<T>(), sl); c->weight_mul(mp.template as<T>(), mp.template as<T>(), o.d[0], o.nplanes, P, beta, sl); c->rfft2_F(mp.template as<T>(), out, sl);
+      c->harm(out, out, P, B, 0, nullptr, false, true, false);
+      return;
+    }
+    cx<T>* m = c->mixed_scratch(sl);
+    by_pol([&](auto pp) {
+      constexpr int PP = decltype(pp)::value;
+      PwChain<T, PP> to_qu{c->geom(), {}, 0, 1, nullptr, T(0), nullptr, T(1)};
+      c->template x_pw<PP, true>(in, m, to_qu, B);                                      // EB -> QU, ifft_x
+      c->y_weight(m, m, o.d[0], o.nplanes, P, beta, sl);                                // x pinv(V) on the map
+      PwChain<T, PP> to_eb{c->geom(), {}, 1, 0, nullptr, T(0), out, T(1)};
+      c->template x_pw<PP, false>(m, nullptr, to_eb, B);                                // fft_x, QU -> EB, stored
+    });
+  }
+  bool has_noise() const { return has(OP_CN_INV_PIX) || has(OP_CN_INV); }
+
   // x (harmonic F) -> M x = Mf * (Mpix * x) ; transpose: Mpix' * (Mf' * x)   (src/dataset.jl:279-285)
   // qu: the pixel side of M is exchanged in QU Fourier (x comes in QU Fourier for M, goes out in QU Fourier for M'), so that the beam
   // next to it does the basis change in its own launch instead of a launch of its own
@@ -91,7 +128,7 @@ struct Dataset : DatasetApi {
   }
 
   // ---- fused path (kernels_harm.hpp; power-of-two maps) ----------------------------------------------------------------------------
-  bool fused() const { return !c->generic && c->opts.fused_harm; }
+  bool fused() const { return !c->generic && c->opts.fused_harm && !has(OP_CN_INV_PIX); }
   OpRef<T> opref(int which, bool transpose = false) const {
     const Op& o = op(which);
     OpRef<T> r{};
@@ -190,8 +227,8 @@ struct Dataset : DatasetApi {
         CMBL_REQUIRE(dd != nullptr, ERR_ARG, "gradientf with f = 0 and d = 0 is identically zero");
         CMBL_HIP(hipMemcpyAsync(r, dd, sizeof(cx<T>) * n, hipMemcpyDeviceToDevice, c->stream));
       }
-      if (f_h && !dd) apply(OP_CN_INV, r, r, B, false, false, false, nullptr, 0, (T)-1);       // d = 0: the sign of -(M B L f) rides along
-      else apply(OP_CN_INV, r, r, B);
+      if (f_h && !dd) apply_cn_inv(r, r, B, (T)-1);                        // d = 0: the sign of -(M B L f) rides along
+      else apply_cn_inv(r, r, B);
       apply_M(r, B, true, true);
       apply(OP_B, r, r, B, true, true, true);                              // QU Fourier -> (EB) x beam' -> QU Fourier
       L.op_adj_F(r, r, P, B);
@@ -282,7 +319,7 @@ struct Dataset : DatasetApi {
     double* qd = qdev.template as<double>();
     mean(L, f_h, z, B, ftil.template as<T>());                              // leaves f~ = L f in ftil
     c->lincomb1((T*)z, (const T*)z, (const T*)dd, 1.0, -1.0, 2 * n / B, B);
-    apply(OP_CN_INV, z, w, B);                c->dot_F_dev(z, w, P, B, qd + 2 * MAXBATCH);
+    apply_cn_inv(z, w, B);                    c->dot_F_dev(z, w, P, B, qd + 2 * MAXBATCH);
     apply(OP_CF_INV, f_h, cfif, B);           c->dot_F_dev(f_h, cfif, P, B, qd);
     apply(OP_CPHI_INV, phi_F, cpip, nphi, false, false, false, nullptr, 0, 1, 1);
     c->dot_F_dev(phi_F, cpip, 1, nphi, qd + MAXBATCH);

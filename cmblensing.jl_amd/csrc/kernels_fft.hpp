@@ -672,6 +672,39 @@ __global__ __launch_bounds__(NT) void k_y_mask(const cx<T>* __restrict__ in, cx<
   half_store<T, NT, LD, LGM, G::LGC>(s, out + sl * (size_t)mixed_rows(G::Nyh) * Nx, tw, x0);
 }
 
+// y pass of the map-diagonal noise sandwich  rfft2( w .* irfft2(x) )  with w = pinv(V) of Cn = Diagonal(V) in the I/QU map basis
+// (src/dataset.jl:37-47, 76-80): k_y_mask with the weight plane chosen per slice (slice sl = b * P + p reads plane p, or plane 0 when one
+// plane serves all pol slices) and `scale` carrying 1/Ny and the sign.  mixed -> map (LDS / registers only) -> x w -> mixed.
+template <typename T, int R, int NT, int LGM>
+__global__ __launch_bounds__(NT) void k_y_weight(const cx<T>* __restrict__ in, cx<T>* __restrict__ out, const T* __restrict__ weight, int nplanes, int P,
+                                                 const cx<T>* __restrict__ twY, int Nx, T scale) {
+  using G = ColTile<R, NT, LGM>;
+  constexpr int M = G::M, LD = G::LDM, C = G::C;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  cx<T>* tw = reinterpret_cast<cx<T>*>(smem);
+  cx<T>* s = tw + M;                            // half of the twiddle circle (see row_tw)
+  const int x0 = xcd_tile(blockIdx.x, gridDim.x) * C;
+  const size_t sl = blockIdx.y;
+  using PM = PairMap<R, NT, LGM>;
+  TwStage<T, NT, M> twr;
+  HalfStage<T, NT, LGM, G::LGC> tl;
+  twr.issue(twY);
+  tl.issue(in + sl * (size_t)mixed_rows(G::Nyh) * Nx, twY, x0);
+  const size_t plane = nplanes == 1 ? 0 : sl % (size_t)P;
+  const cx<T>* wk2 = reinterpret_cast<const cx<T>*>(weight) + (plane * Nx + (size_t)x0) * M;     // planes are (Nx, Ny) maps without a batch axis
+  cx<T> wv[R];
+#pragma unroll
+  for (int i = 0; i < R; ++i) wv[i] = at32(wk2, (unsigned)PM::e(i));
+  twr.commit(tw);
+  tl.template commit<LD>(s);
+  __syncthreads();
+  cx<T> z[R];
+  mpt_inverse_read<T, R, NT, LGM, LD>(s, tw, scale, z);
+  __syncthreads();
+  mpt_write_forward<T, R, NT, LGM, LD>(s, tw, [&](int i) { return mk<T>(wv[i].x * z[i].x, wv[i].y * z[i].y); });
+  half_store<T, NT, LD, LGM, G::LGC>(s, out + sl * (size_t)mixed_rows(G::Nyh) * Nx, tw, x0);
+}
+
 // ---------------------------------------------------------------------------------------------
 // x pass.  grid = slices * ceil(Nyh / RPW) row groups, 128 * RPW threads.  LDS: twX[Nx] + RPW * row_ld(Nx) cplx
 //   MODE 0: forward  (mixed -> F)

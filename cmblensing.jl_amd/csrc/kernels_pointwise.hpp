@@ -96,6 +96,15 @@ __global__ __launch_bounds__(NTP) void k_mask_mul(T* __restrict__ out, const T* 
   for (long i = (long)blockIdx.x * NTP + threadIdx.x; i < n; i += (long)gridDim.x * NTP) out[off + i] = m[i] * in[off + i];
 }
 
+// out[b][p][i] = scale * w[nplanes == 1 ? 0 : p][i] * in[b][p][i]  (map-diagonal pinv(Cn), one plane per pol slice or one for all; slice
+// sl = b * P + p)   grid (blocks, slices); in place allowed
+template <typename T>
+__global__ __launch_bounds__(NTP) void k_weight_mul(T* out, const T* in, const T* __restrict__ w, int nplanes, int P, T scale, long n) {
+  const long off = (long)blockIdx.y * n;
+  const T* wp = w + (nplanes == 1 ? 0 : (long)(blockIdx.y % P) * n);
+  for (long i = (long)blockIdx.x * NTP + threadIdx.x; i < n; i += (long)gridDim.x * NTP) out[off + i] = scale * wp[i] * in[off + i];
+}
+
 // ---------------------------------------------------------------------------------------------
 // Reductions: per-batch-slot sums, deterministic two-pass (fixed partition, fixed tree).
 //

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from .engine import Field, MAP, FOURIER, HARMONIC
+from .sim import noise_from_white
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -293,7 +294,7 @@ def simulate_data(ds, phi, white_f, white_n):
     white_*: (B,P,Nx,Ny) unit white-noise maps (device tensors from ProjLambert.randn, or host arrays).  Returns d (HARMONIC)."""
     proj, h = ds.proj, ds.host
     raw = lambda w, op: Field(proj, proj.diag_apply(op.sqrt().p, proj.rfft(proj.tensor(w)), HARMONIC, HARMONIC), HARMONIC)
-    return ds.mean(raw(white_f, h["Cf"]), phi) + raw(white_n, h["Cn"])
+    return ds.mean(raw(white_f, h["Cf"]), phi) + noise_from_white(ds, white_n)
 
 
 def MAP_marg(ds, nsteps=10, nsteps_with_meanfield_update=4, alpha=0.2, Nsims=50, sims_per_batch=1, phi_start=None, cg_tol=1e-1,
@@ -448,7 +449,7 @@ def sample_f(ds, phi, white_f, white_n, fstart=None, tol=1e-1, nsteps=500):
     """`sample_f` (src/maximization.jl:56-62)"""
     proj, h = ds.proj, ds.host
     raw = lambda w, op: Field(proj, proj.diag_apply(op.sqrt().p, proj.rfft(proj.tensor(w)), HARMONIC, HARMONIC), HARMONIC)
-    fs, ns = raw(white_f, h["Cf"]), raw(white_n, h["Cn"])
+    fs, ns = raw(white_f, h["Cf"]), noise_from_white(ds, white_n)
     dsim = ds.mean(fs, phi) + ns
     df, hist = ds.argmaxf_logpdf(phi, d=ds.d - dsim, fstart=fstart, tol=tol, nsteps=nsteps)
     return fs + df, hist

@@ -18,7 +18,7 @@ MAP, FOURIER, HARMONIC = 0, 1, 2
 FLOW_FWD, FLOW_INV, FLOW_ADJ, FLOW_INVADJ = 0, 1, 2, 3
 DIAG_MUL, DIAG_DIV_NAN2ZERO = 1, 3
 UD_MAP, UD_FOURIER = 0, 1
-(OP_CF_INV, OP_CN_INV, OP_B, OP_MF, OP_D, OP_D_INV, OP_PRECOND_INV, OP_CPHI_INV, OP_G_INV, OP_MPIX) = range(10)
+(OP_CF_INV, OP_CN_INV, OP_B, OP_MF, OP_D, OP_D_INV, OP_PRECOND_INV, OP_CPHI_INV, OP_G_INV, OP_MPIX, OP_CN_INV_PIX) = range(11)
 
 
 def _ptr(t):
@@ -819,11 +819,13 @@ class BaseDataSet(_Handle):
     ops: dict name -> real planes (numpy/torch, reference layout):
         'Cf_inv','Cn_inv','B','Mf','D','D_inv','precond_inv' : (P or 5, Nx, Nyh)   harmonic basis
         'Cphi_inv','G_inv' : (1, Nx, Nyh) ;  'Mpix' : (Nx, Ny) optional
+        'Cn_inv_pix' : (P or 1, Nx, Ny) optional -- pinv(V) of a noise covariance Cn = Diagonal(V) in the I/QU map basis (0 where V is 0 or
+        infinite).  While set it IS the noise operator (`CMBL_OP_CN_INV_PIX`) and 'Cn_inv' is not read; `set_op("Cn_inv_pix", None)` clears it.
     d: harmonic-basis data (B,P,Nx,Nyh); logdet_sum: logdet Cf + logdet Cϕ + logdet Cn.
     """
     _destroy = "cmbl_dataset_destroy"
     _ids = dict(Cf_inv=OP_CF_INV, Cn_inv=OP_CN_INV, B=OP_B, Mf=OP_MF, D=OP_D, D_inv=OP_D_INV,
-                precond_inv=OP_PRECOND_INV, Cphi_inv=OP_CPHI_INV, G_inv=OP_G_INV, Mpix=OP_MPIX)
+                precond_inv=OP_PRECOND_INV, Cphi_inv=OP_CPHI_INV, G_inv=OP_G_INV, Mpix=OP_MPIX, Cn_inv_pix=OP_CN_INV_PIX)
 
     def __init__(self, proj, P, ops, d=None, logdet_sum=0.0, nsteps=7, L=None):
         self.proj, self.P = proj, int(P)
@@ -876,10 +878,16 @@ class BaseDataSet(_Handle):
         check(self.lib.cmbl_dataset_set_logdet(self._h, self.logdet_sum))
 
     def set_op(self, name, planes):
+        if name == "Cn_inv_pix" and planes is None:  # clear it: back to the Fourier form 'Cn_inv'; drops what setting it drops
+            self.ops.pop(name, None)
+            self._mask_full = (None, None)
+            self.__dict__.pop("_qe_planes", None)
+            check(self.lib.cmbl_dataset_set_op(self._h, self._ids[name], None, 0))
+            return
         t = self.proj.tensor(planes)
         t = t.reshape(1, *t.shape) if t.dim() == 2 else t
         self.ops[name] = t
-        if name == "Mpix":
+        if name in ("Mpix", "Cn_inv_pix"):
             self._mask_full = (None, None)          # expanded copy of the pixel mask is stale
         self.__dict__.pop("_qe_planes", None)       # device copies of the estimator's planes (drivers.quadratic_estimate_native) are stale too
         check(self.lib.cmbl_dataset_set_op(self._h, self._ids[name], _ptr(t), t.shape[0]))
@@ -887,6 +895,15 @@ class BaseDataSet(_Handle):
     def _apply(self, name, f, basis_out=HARMONIC):
         """harmonic-basis operator `name` applied to Field f"""
         return Field(self.proj, self.proj.diag_apply(self.ops[name], f.arr, HARMONIC, f.basis, basis_out), basis_out)
+
+    def noise_inv(self, f):
+        """pinv(Cn) * f (HARMONIC) with whichever form of the noise operator is set: the Fourier-diagonal 'Cn_inv' or the map-diagonal
+        'Cn_inv_pix' (`cmbl_dataset_noise_inv`)"""
+        f = f.to(HARMONIC)
+        B = f.arr.shape[0]
+        out = self.proj.empty(HARMONIC, self.P, B)
+        check(self.lib.cmbl_dataset_noise_inv(self._h, _ptr(f.arr), _ptr(out), B))
+        return Field(self.proj, out, HARMONIC)
 
     def _applyT(self, name, f, basis_out=HARMONIC):
         """transpose of the (real) harmonic-basis operator `name`: for BlockDiagIEB planes (TT,TE,ET,EE,BB) swap TE <-> ET"""
@@ -916,7 +933,7 @@ class BaseDataSet(_Handle):
             return self.grad_logpdf(f, phi, d, want_f=False, alias_quirk=alias_quirk)[2]
         ft = self.L(phi) * f.to(MAP)
         z = d.to(HARMONIC) - self._mask(self._apply("B", ft))
-        w = self._applyT("B", self._maskT(self._apply("Cn_inv", z)), basis_out=FOURIER)
+        w = self._applyT("B", self._maskT(self.noise_inv(z)), basis_out=FOURIER)
         dphi, _, _ = self.L(phi).gradient(FLOW_FWD, ft, w, alias_quirk=alias_quirk)
         prior = self.proj.diag_apply(self.ops["Cphi_inv"], phi.to(FOURIER).arr, FOURIER, FOURIER)
         if prior.shape[0] != dphi.arr.shape[0]:
@@ -963,7 +980,7 @@ class BaseDataSet(_Handle):
         d = self.d if d is None else d
         z = self.mean(f, phi) - d
         q1 = f.dot(self._apply("Cf_inv", f))
-        q3 = z.dot(self._apply("Cn_inv", z))
+        q3 = z.dot(self.noise_inv(z))
         cp = Field(self.proj, self.proj.diag_apply(self.ops["Cphi_inv"], phi.arr, FOURIER, FOURIER), FOURIER)
         q2 = phi.dot(cp)
         return -0.5 * (q1 + q2 + q3 + self.logdet_sum)

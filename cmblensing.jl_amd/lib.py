@@ -50,6 +50,7 @@ SIGNATURES = {
     "cmbl_dataset_create": [_vp, _ci, _pvp],
     "cmbl_dataset_destroy": [_vp],
     "cmbl_dataset_set_op": [_vp, _ci, _vp, _ci],
+    "cmbl_dataset_noise_inv": [_vp, _vp, _vp, _ci],
     "cmbl_dataset_set_data": [_vp, _vp, _ci],
     "cmbl_dataset_set_logdet": [_vp, _cd],
     "cmbl_gradientf_logpdf": [_vp, _vp, _vp, _vp, _ci, _vp, _ci],

@@ -14,6 +14,7 @@ mirrors, method for method:
 import numpy as np
 
 from .engine import Field, FOURIER, HARMONIC
+from .sim import noise_from_white
 from . import theta as TH
 
 
@@ -63,7 +64,7 @@ class CMBLensingMuseProblem:
         col = lambda w, planes, basis: Field(proj, proj.diag_apply(planes, proj.rfft(w), basis, basis), basis)
         f = col(draw(R.STREAM_F, ds.P), h["Cf"].sqrt().p, HARMONIC)
         phi = col(draw(R.STREAM_P, 1), np.sqrt(np.asarray(h["Cphi"], float))[None], FOURIER)
-        n = col(draw(R.STREAM_N, ds.P), h["Cn"].sqrt().p, HARMONIC)
+        n = noise_from_white(ds, draw(R.STREAM_N, ds.P))
         return ds.mean(f, phi) + n, dict(f=f, phi=phi)
 
     def zhat_at_theta(self, d, zguess, theta):

@@ -140,9 +140,23 @@ def white_noise(seed, shape):
     return np.random.Generator(np.random.PCG64(seed)).standard_normal(shape)
 
 
+def noise_from_white(ds, white):
+    """n ~ 𝒩(0, Cn) from unit white-noise maps (B,P,Nx,Ny), HARMONIC: sqrt(Cn)·rfft(white) with the Fourier-diagonal `ds.host["Cn"]`
+    (src/specialops.jl:6), or sqrt(V) ⊙ white in map space when the data set has the map-diagonal Cn = Diagonal(V) (`ds.host["Cn_pix"]`,
+    load_sim(noise_var_map=...))."""
+    proj, h = ds.proj, ds.host
+    w = proj.tensor(white)
+    if h.get("Cn_pix") is None:
+        return Field(proj, proj.diag_apply(h["Cn"].sqrt().p, proj.rfft(w), HARMONIC, HARMONIC), HARMONIC)
+    with np.errstate(invalid="ignore"):
+        s = np.sqrt(h["Cn_pix"])
+    s = proj.tensor(np.where(np.isfinite(s), s, 0.0))          # pixels of infinite variance carry no weight: no draw is made there
+    return Field(proj, proj.map_fma(w, s.unsqueeze(0).expand(*w.shape).contiguous()), MAP).to(HARMONIC)
+
+
 def load_sim(theta_pix, Nside, pol, cls, T=torch.float32, device=0, muK_arcmin_T=3.0, lknee=100.0, alphaknee=3.0,
              beam_fwhm=0.0, pixel_mask=None, bandpass_lmax=3000, nsteps=7, Nbatch=1, seeds=(1, 2, 3),
-             Nphi=None, Nphi_fac=2, G=None, rng="host", pixel_mask_kwargs=None, L=None):
+             Nphi=None, Nphi_fac=2, G=None, rng="host", pixel_mask_kwargs=None, L=None, noise_var_map=None, Cnhat=None):
     # Nphi: None / "qe" -> N⁰ of the quadratic estimator like the reference; "flat" -> cheap flat level; or an [x,ky] plane
     """`load_sim` (src/dataset.jl:186-338).  `cls`: dict group -> dict {TT,EE,BB,TE,pp} of Cls for the groups
     'unlensed_scalar', 'tensor', 'total' (e.g. decoded from the reference's dat/default_camb_Cls.jld2).
@@ -151,6 +165,15 @@ def load_sim(theta_pix, Nside, pol, cls, T=torch.float32, device=0, muK_arcmin_T
     keywords of the deterministic `border_mask` instead; giving both is a ValueError.
     `L`: the lensing operator of the data set (`load_sim(L = BilinearLens)`, :223): None = `LenseFlow(proj, nsteps)`, or a callable
     `proj -> operator` such as `BilinearLens` or `lambda p: PowerLens(p, 4)` (`BaseDataSet` has what each operator covers).
+    `noise_var_map`: a noise variance map V in μK² per pixel, shape (P or 1, Nx, Ny) (host array or device tensor; one plane is shared by all
+    pol slices): the noise covariance is then Cn = Diagonal(V) in the I/QU map basis, the inhomogeneous noise of a hit-count map (`BaseDataSet.Cn`
+    is any operator, src/dataset.jl:37-47).  logdet Cn = Σ log V (`logdet(Diagonal(::Map))`, src/proj_lambert.jl:337-342; a shared plane counts P
+    times; pixels of zero or infinite variance, whose weight pinv(V) is 0, are left out of the sum and get no noise draw), the noise realisation is
+    sqrt(V) ⊙ white from the same white draws and seeds, and `muK_arcmin_T`, `lknee`, `alphaknee` are NOT read.
+    `Cnhat`: the approximate, Fourier-diagonal Cn̂ (a `HarmOp`) that the preconditioner, the mixing matrix D, `quadratic_estimate` and
+    `ds.host["Cn"]` read (:41, 129-132, 316-328); None = white noise at the harmonic-mean level 1 / mean(1/V) per plane, over the pixels with finite
+    positive V.  (The reference defaults to Cn̂ = Cn, which is not diagonal in Cf's basis and so cannot be inverted mode by mode inside the
+    preconditioner: the harmonic-mean default is this port's choice.)  V is kept as `ds.host["Cn_pix"]`, Σ log V as `ds.host["logdet_Cn"]`.
     Returns dict(f, phi, ftilde, d, ds, proj) with Fields on the device."""
     if pixel_mask is not None and pixel_mask_kwargs is not None:
         raise ValueError("load_sim: give pixel_mask (border_mask) or pixel_mask_kwargs (make_mask), not both")
@@ -165,6 +188,26 @@ def load_sim(theta_pix, Nside, pol, cls, T=torch.float32, device=0, muK_arcmin_T
     Cfs, Cten = mk(cls["unlensed_scalar"]), mk(cls["tensor"])                  # :268-269
     Cf = Cfs + Cten                                                             # :273 at r = r₀
     Cn = mk(ncl)                                                                # :271-272
+    Cn_pix = Cn_inv_pix = logdet_Cn = None
+    if noise_var_map is not None:                                               # Cn = Diagonal(V) in the map basis; `Cn` below is Cn̂
+        V = noise_var_map.detach().cpu().numpy() if torch.is_tensor(noise_var_map) else np.asarray(noise_var_map)
+        Cn_pix = np.array(V, dtype=np.float64).reshape(-1, Nx, Ny)
+        if Cn_pix.shape[0] not in (1, P):
+            raise ValueError(f"load_sim: noise_var_map has {Cn_pix.shape[0]} planes, expected 1 or {P}")
+        Cn_inv_pix = _pinv(Cn_pix)
+        seen = np.isfinite(Cn_pix) & (Cn_pix > 0)                                 # pixels of zero or infinite variance carry no weight and no logdet term
+        # summed here in double like the logdets of the Fourier-diagonal operators next to it (HarmOp.logdet): `proj.logdet_diag(V, MAP)` of a
+        # float32 context rounds V and takes float32 logarithms, -1.5e-7 per pixel on average -- -9e-4 of 26793 at 32 x 64 T+QU, a third of the
+        # float32 error of logpdf there
+        logdet_Cn = float(np.sum(np.log(Cn_pix[seen]))) * (P // Cn_pix.shape[0])
+        if Cnhat is None:
+            good = [v[np.isfinite(v) & (v > 0)] for v in np.broadcast_to(Cn_pix, (P, Nx, Ny))]
+            lv = [1.0 / np.mean(1.0 / g) for g in good]
+            one = np.ones_like(Cphi)
+            Cnhat = HarmOp([lv[0] * one, 0 * one, 0 * one, lv[1] * one, lv[2] * one] if P == 3 else [l * one for l in lv])
+        Cn = Cnhat
+    elif Cnhat is not None:
+        raise ValueError("load_sim: Cnhat is the approximation of a map-diagonal noise covariance; it needs noise_var_map")
     Mf = mk(lowpass(bandpass_lmax), units=1, te_zero=True)                      # :279
     bcl = beam_cls(beam_fwhm, lmax)
     Bop = mk(Cls(bcl.ell, np.sqrt(bcl.cl)), units=1, te_zero=True)              # :300
@@ -181,13 +224,13 @@ def load_sim(theta_pix, Nside, pol, cls, T=torch.float32, device=0, muK_arcmin_T
     s2len = np.deg2rad(5 / 60) ** 2
     D = ((Cf + (Cn.scale(2) + s2len)) @ Cf.pinv()).sqrt()                       # :322-328
     precond = Cf.pinv() + (Bop.T() @ Mf.T() @ Cn.pinv() @ Mf @ Bop)             # src/dataset.jl:129-132
-    logdet_sum = Cf.logdet(proj) + Cn.logdet(proj) + HarmOp([Cphi]).logdet(proj)
+    logdet_sum = Cf.logdet(proj) + (Cn.logdet(proj) if logdet_Cn is None else logdet_Cn) + HarmOp([Cphi]).logdet(proj)
     ops = dict(Cf_inv=Cf.pinv().p, Cn_inv=Cn.pinv().p, B=Bop.p, Mf=Mf.p, D=D.p, D_inv=D.pinv().p,
-               precond_inv=precond.pinv().p, Cphi_inv=_pinv(Cphi)[None], G_inv=_pinv(Gp)[None], Mpix=Mpix)
+               precond_inv=precond.pinv().p, Cphi_inv=_pinv(Cphi)[None], G_inv=_pinv(Gp)[None], Mpix=Mpix, Cn_inv_pix=Cn_inv_pix)
     ds = BaseDataSet(proj, P, ops, logdet_sum=logdet_sum, nsteps=nsteps, L=L)
     Cft = mk(cls["total"])                                                     # Cf̃ (:270)
     ds.host = dict(Cf=Cf, Cn=Cn, Cphi=Cphi, Mf=Mf, B=Bop, D=D, Nphi=Nphi, G=Gp, Mpix=Mpix, precond=precond, Cftilde=Cft,
-                   Cfs=Cfs, Cten=Cten, r0=0.2, Aphi0=1.0, s2len=s2len)
+                   Cfs=Cfs, Cten=Cten, r0=0.2, Aphi0=1.0, s2len=s2len, Cn_pix=Cn_pix, logdet_Cn=logdet_Cn)
     if G is not None:
         ds.host["G_user"] = Gp.copy()                                           # theta.set_theta keeps a user-supplied G at fiducial Aϕ           # θ layer (theta.py): r₀ = Cℓ.params.r, Aϕ₀ = 1 (:239,250)
 
@@ -202,7 +245,11 @@ def load_sim(theta_pix, Nside, pol, cls, T=torch.float32, device=0, muK_arcmin_T
     f = sim(Cf.sqrt().p, seeds[0], P)
     phi = sim(np.sqrt(Cphi)[None], seeds[1], 1)
     phi = Field(proj, phi.arr, FOURIER)
-    n = sim(Cn.sqrt().p, seeds[2], P)
+    if Cn_pix is None:
+        n = sim(Cn.sqrt().p, seeds[2], P)
+    else:                                                                        # sqrt(V) ⊙ white, the same white draw
+        n = noise_from_white(ds, proj.randn([seeds[2] + 1000003 * b for b in range(Nbatch)], 0, P) if rng == "device"
+                             else white_noise(seeds[2], (Nbatch, P, Nx, Ny)))
     ftilde = ds.L(phi) * f                                                       # map
     d = ds.mean(f, phi) + n                                                      # M·B·L(ϕ)·f + n  (src/dataset.jl:59-66)
     ds.set_data(d)

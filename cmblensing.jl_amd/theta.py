@@ -79,7 +79,8 @@ def _ops(ds, r, Aphi, bands=None):
         logdet_mix += HarmOp([G]).logdet(proj)
     precond = Cf.pinv() + (h["B"].T() @ h["Mf"].T() @ h["Cn"].pinv() @ h["Mf"] @ h["B"])
     out = dict(Cf_inv=Cf.pinv().p, D=D.p, D_inv=D.pinv().p, precond_inv=precond.pinv().p, Cphi_inv=_pinv(Cphi)[None], G_inv=_pinv(G)[None])
-    logdet_sum = Cf.logdet(proj) + h["Cn"].logdet(proj) + HarmOp([Cphi]).logdet(proj)
+    logdet_Cn = h["logdet_Cn"] if h.get("logdet_Cn") is not None else h["Cn"].logdet(proj)     # Σ log V of a map-diagonal Cn (load_sim(noise_var_map=...))
+    logdet_sum = Cf.logdet(proj) + logdet_Cn + HarmOp([Cphi]).logdet(proj)
     return out, logdet_sum, logdet_mix, dict(Cf=Cf, Cphi=Cphi, D=D, G=G, precond=precond)
 
 

@@ -503,10 +503,24 @@ enum { CMBL_OP_CF_INV = 0,     /* pinv(Cf)                                   har
        CMBL_OP_CPHI_INV = 7,   /* pinv(Cphi), 1 plane                                                           */
        CMBL_OP_G_INV = 8,      /* pinv(G), 1 plane                                                              */
        CMBL_OP_MPIX = 9,       /* pixel mask, real (Ny,Nx) map; optional                                        */
-       CMBL_OP_COUNT = 10 };
+       CMBL_OP_CN_INV_PIX = 10,/* pinv(V) of Cn = Diagonal(V), real (Ny,Nx) maps; optional (see below)          */
+       CMBL_OP_COUNT = 11 };
+/* CMBL_OP_CN_INV_PIX: a noise covariance that is diagonal in the I/QU MAP basis, Cn = Diagonal(V) with V the variance per pixel -- the
+ * inhomogeneous noise of a survey's hit-count map.  BaseDataSet.Cn is "any operator" (src/dataset.jl:37-47), pinv(Cn(theta)) is all that
+ * gradientf_logpdf asks of it (:76-80), and logdet(Diagonal(::Map)) exists for it (src/proj_lambert.jl:337-342).  planes: device maps
+ * (nplanes, Ny, Nx) in the layout of CMBL_OP_MPIX and of MAP fields, nplanes = 1 (one map for all pol slices) or npol (I | Q,U | I,Q,U);
+ * anything else is CMBL_ERR_SHAPE.  They are the caller's pinv of the variance: 0 where the variance is 0 or infinite.  No batch axis.
+ * While set, this IS the data set's noise operator and CMBL_OP_CN_INV is read by no entry point; nplanes = 0 (planes may be NULL) clears it.
+ * pinv(Cn) z is then rfft2(w .* irfft2(z)) between the EB <-> QU basis changes; z' pinv(Cn) z stays a Fourier-domain dot (the default `dot`,
+ * src/proj_lambert.jl:328), so the sum-accuracy modes keep their meaning.  The fused forms of the posterior and of the Wiener CG (option
+ * fused_harm) are not used while it is set: every entry point below runs its composed form.  The approximate, Fourier-diagonal Cn^ (what the
+ * preconditioner, D and the quadratic estimator read, :41, 129-132, 316-328) stays with the caller, inside CMBL_OP_PRECOND_INV / CMBL_OP_D.
+ * cmbl_dataset_noise_inv: out = pinv(Cn) * in with whichever form is set (HARMONIC in and out, nbatch slots, in place allowed);
+ * CMBL_ERR_STATE if neither is. */
 int cmbl_dataset_create(cmbl_ctx* ctx, int npol, cmbl_dataset** out);
 int cmbl_dataset_destroy(cmbl_dataset* ds);
 int cmbl_dataset_set_op(cmbl_dataset* ds, int which, const void* planes, int nplanes);
+int cmbl_dataset_noise_inv(cmbl_dataset* ds, const void* in_harmonic, void* out_harmonic, int nbatch);
 int cmbl_dataset_set_data(cmbl_dataset* ds, const void* d_harmonic, int nbatch);
 /* sum of the three logdet terms of logpdf (logdet Cf + logdet Cphi + logdet Cn), per batch identical */
 int cmbl_dataset_set_logdet(cmbl_dataset* ds, double logdet_sum);
