@@ -382,6 +382,33 @@ int cmbl_grad_logpdf_mixed(cmbl_dataset* ds, cmbl_flow* L, const void* fo, const
   });
 }
 
+// ---- θ layer: the parameter-dependent operators and logpdf(Mixed; θ) over a grid, on the device ----
+int cmbl_dataset_theta_model(cmbl_dataset* ds, const double* Cfs_host, int nplanes, const double* C0_host, int nbands, const int* band_planes_host,
+                             const int32_t* band_idx_host, const int* band_nbins_host, const double* Cten_host, const double* Cn_host, double s2len,
+                             double r0, const double* Cphi0_host, double Aphi0, const double* Nphi_host, const double* G_host, double logdet_Cn) {
+  return guard([&] {
+    NOTNULL(ds); NOTNULL(Cfs_host); NOTNULL(Cten_host); NOTNULL(Cn_host); NOTNULL(Cphi0_host); NOTNULL(Nphi_host);
+    const ThetaModelArgs a{Cfs_host, nplanes, C0_host, nbands, band_planes_host, band_idx_host, band_nbins_host, Cten_host, Cn_host, s2len, r0,
+                           Cphi0_host, Aphi0, Nphi_host, G_host, logdet_Cn};
+    BY_DTYPE(ds->ctx, do_theta_model, ds, a);
+  });
+}
+int cmbl_logpdf_mixed_theta(cmbl_dataset* ds, cmbl_flow* L, const void* fo, const void* phio, int B, int ntheta, const double* r_host,
+                            const double* Aphi_host, const double* amps_host, int namps, double* lp_host) {
+  return guard([&] {
+    NOTNULL(ds); NOTNULL(L); NOTNULL(fo); NOTNULL(phio); NOTNULL(r_host); NOTNULL(Aphi_host); NOTNULL(lp_host);
+    CMBL_REQUIRE(B >= 1 && ntheta >= 1, ERR_SHAPE, "nbatch >= 1 and ntheta >= 1");
+    SAME_CTX(ds, L);
+    BY_DTYPE(ds->ctx, do_lpm_theta, ds, L, fo, phio, B, ntheta, r_host, Aphi_host, amps_host, namps, lp_host);
+  });
+}
+int cmbl_dataset_theta_ops(cmbl_dataset* ds, double r, double Aphi, const double* amps_host, int namps, int which, void* out_dev, double* sums_host) {
+  return guard([&] {
+    NOTNULL(ds);
+    BY_DTYPE(ds->ctx, do_theta_ops, ds, r, Aphi, amps_host, namps, which, out_dev, sums_host);
+  });
+}
+
 int cmbl_hmc_step(cmbl_dataset* ds, cmbl_flow* L, const void* fo, const void* phio, const void* mass, const void* white_p, const double* log_u_host,
                   const uint64_t* seeds_host, uint64_t step, int nleap, double eps, int always_accept, int alias_quirk, int B,
                   void* phio_out, double* dH_host, int* accept_host) {

@@ -142,6 +142,25 @@ void do_lpm(cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, 
   if (gfo) c->F2ref(gF, (cx<T>*)gphio, B);
   CMBL_HIP(hipStreamSynchronize(c->stream));
 }
+// the θ layer on the device (Dataset<T>::theta_*, kernels_theta.hpp)
+template <typename T> void do_theta_model(cmbl_dataset* dsh, const ThetaModelArgs& a) {
+  typed<Dataset<T>>(dsh).theta_install(a.cfs, a.nplanes, a.c0, a.nbands, a.band_planes, a.band_idx, a.band_nbins, a.cten, a.cn, a.s2len, a.r0, a.cphi0, a.aphi0,
+                                       a.nphi, a.g, a.logdet_cn);
+}
+template <typename T>
+void do_lpm_theta(cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, int B, int ntheta, const double* r, const double* aphi, const double* amps,
+                  int namps, double* lp) {
+  Dataset<T>& ds = typed<Dataset<T>>(dsh); Flow<T>& L = typed<Flow<T>>(Lh);
+  Ctx<T>* c = ds.c;
+  ds.cvt.ensure(sizeof(cx<T>) * 2 * B * c->plane());
+  cx<T>* pF = ds.cvt.template as<cx<T>>();
+  c->ref2F((const cx<T>*)phio, pF, B);
+  ds.logpdf_mixed_theta(L, (const T*)fo, pF, B, ntheta, r, aphi, amps, namps, lp);
+  CMBL_HIP(hipStreamSynchronize(c->stream));
+}
+template <typename T> void do_theta_ops(cmbl_dataset* dsh, double r, double aphi, const double* amps, int namps, int which, void* out, double* sums) {
+  typed<Dataset<T>>(dsh).theta_readback(r, aphi, amps, namps, which, (T*)out, sums);
+}
 
 template <typename T> Drivers<T>& drivers_of(cmbl_dataset* dsh, cmbl_flow* Lh) {
   auto& p = dsh->drv[Lh->p.get()];

@@ -71,7 +71,10 @@ namespace cmbl {
   X(T, do_cg_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* d, const void* fstart, double tol, int maxit, void* f_out, double* hist, int* nit, int B)) \
   X(T, do_grad_lp_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void* phi, const void* d, double* lp, void* gf, void* gphi, int B, int quirk)) \
   X(T, do_lpm, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, double* lp, void* gfo, void* gphio, int B, int quirk)) \
-  X(T, do_hmc, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, const void* mass, const void* white_p, const double* log_u, const uint64_t* seeds, uint64_t step, int nleap, double eps, int always, int quirk, int B, void* phio_out, double* dH, int* accept)) \
+  X(T, do_theta_model, (cmbl_dataset* dsh, const ThetaModelArgs& a)) \
+  X(T, do_lpm_theta, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, int B, int ntheta, const double* r, const double* aphi, const double* amps, int namps, double* lp)) \
+  X(T, do_theta_ops, (cmbl_dataset* dsh, double r, double aphi, const double* amps, int namps, int which, void* out, double* sums)) \
+  X(T, do_hmc,(cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, const void* mass, const void* white_p, const double* log_u, const uint64_t* seeds, uint64_t step, int nleap, double eps, int always, int quirk, int B, void* phio_out, double* dH, int* accept)) \
   X(T, do_map_step, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* phi, const void* fstart, const void* hinv, double amax, double atol, double cg_tol, int cg_maxit, int quirk, int B, void* f_out, void* phi_out, double* logpdf, double* alpha, int* ncg, int* nls)) \
   X(T, do_qe, (cmbl_dataset* dsh, int which, const double* Cf, const double* Cft, const double* Cn, const double* TF, const double* Cphi, int wiener, const double* AL_in, void* phiqe_out, double* AL_out, int B)) \
   X(T, do_ud_grade, (cmbl_ctx* src, cmbl_ctx* dst, int mode, int deconv, int aa, int bi, const void* in, int bo, void* out, int P, int B)) \

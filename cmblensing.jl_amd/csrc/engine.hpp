@@ -631,6 +631,10 @@ struct Ctx : CtxBase {
     if (generic) return transpose(in, out, Nx, Nyh, slices);
     CMBL_LAUNCH(this, K_LAYOUT, (k_ref2F<T>), dim3(Nx / 32, (Nyh + 31) / 32, (unsigned)slices), 0, stream, in, out, Nx, lgNx, Nyh);
   }
+  void F2ref_real(const T* in, T* out, long slices) {
+    if (generic) return transpose(in, out, Nyh, Nx, slices);
+    CMBL_LAUNCH(this, K_LAYOUT, (k_F2ref<T>), dim3(Nx / 32, (Nyh + 31) / 32, (unsigned)slices), 0, stream, in, out, Nx, lgNx, Nyh);
+  }
   void y_r2c(const T* map, cx<T>* mixed, long slices) {
     CMBL_REQUIRE(!generic, ERR_STATE, "fused column pass called on the any-size path");
     const TileY t = tileY(slices, false);

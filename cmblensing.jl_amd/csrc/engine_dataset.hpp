@@ -3,6 +3,7 @@
 #pragma once
 #include "engine.hpp"
 #include "engine_cg.hpp"
+#include "kernels_theta.hpp"
 
 namespace cmbl {
 
@@ -445,6 +446,158 @@ struct Dataset : DatasetApi {
     c->lincomb1((T*)g, (const T*)g, (const T*)cpip, 1.0, -1.0, 2 * pl, B);
     apply(OP_G_INV, g, gphio_F, B, true, false, false, nullptr, 0, 1, 1);
     read_logpdf(lp, B, 1);
+  }
+
+  // ---- θ layer on the device (kernels_theta.hpp): the model installed once per data set, the operators of one θ, the grid of logpdf(Mixed; θ) ----
+  struct ThetaModel {
+    bool set = false, has_c0 = false, has_g = false;
+    int np = 0, nbands = 0, namps = 0;
+    int bmask[TH_MAXBANDS] = {0, 0, 0}, bnb[TH_MAXBANDS] = {0, 0, 0}, boff[TH_MAXBANDS] = {0, 0, 0};
+    double s2len = 0, r0 = 1, aphi0 = 1, logdet_cn = 0;
+    DevBuf planes;                           // double, F layout: cfs, c0, cten, cn, d0inv (np planes each), cphi0, nphi, g0inv, guser
+    DevBuf bidx;                             // int32, F layout: one bin-index plane per band
+    DevBuf ops;                              // T, F layout: the scratch operator sets pinv(Cf) (np), pinv(D) (np), pinv(Cphi), pinv(G)
+    DevBuf part, sums, amps;                 // partial sums [3][nblk], their totals [3], the amplitude vectors of a grid call
+  } th;
+  T* th_op(int which) {
+    T* o = th.ops.template as<T>(); const long pl = c->plane();
+    return which == OP_CF_INV ? o : which == OP_D_INV ? o + th.np * pl : which == OP_CPHI_INV ? o + 2 * th.np * pl : o + (2 * th.np + 1) * pl;
+  }
+  // a reference-layout plane ([x][ky]) in the F layout ([ky][x slot]; the slot order of Ctx::build_geometry)
+  template <typename V> void th_toF(const V* ref, V* out, int nplanes) const {
+    const int Nx = c->Nx, Nyh = c->Nyh;
+    std::vector<int> xf(Nx);
+    for (int i = 0; i < Nx; ++i) { unsigned r = i; if (!c->generic) { r = 0; for (int b = 0; b < c->lgNx; ++b) r |= ((i >> b) & 1u) << (c->lgNx - 1 - b); } xf[i] = (int)r; }
+    for (int p = 0; p < nplanes; ++p)
+      for (int k = 0; k < Nyh; ++k)
+        for (int i = 0; i < Nx; ++i) out[((size_t)p * Nyh + k) * Nx + i] = ref[((size_t)p * Nx + xf[i]) * Nyh + k];
+  }
+  // everything theta._ops reads, copied; D0 = D(r0) and g0 = G-numerator at Aphi0 do not depend on θ and are derived here, on the host, with
+  // the very functions the kernel uses
+  void theta_install(const double* cfs, int nplanes, const double* c0, int nbands, const int* band_planes, const int32_t* band_idx, const int* band_nbins,
+                     const double* cten, const double* cn, double s2len, double r0, const double* cphi0, double aphi0, const double* nphi,
+                     const double* g, double logdet_cn) {
+    CMBL_REQUIRE(nplanes == (P == 3 ? 5 : P), ERR_SHAPE, "theta_model: the covariances take npol planes (5 for IQU)");
+    CMBL_REQUIRE(nbands >= 0 && nbands <= TH_MAXBANDS, ERR_ARG, "theta_model: at most three bandpower bands (TT, TE, EE)");
+    CMBL_REQUIRE(nbands == 0 || (c0 && band_planes && band_idx && band_nbins), ERR_ARG, "theta_model: bands need the base covariance, their planes, bin indices and bin counts");
+    CMBL_REQUIRE(r0 != 0 && aphi0 != 0 && std::isfinite(r0) && std::isfinite(aphi0), ERR_ARG, "theta_model: r0 and Aphi0 must be finite and non-zero");
+    const long pl = c->plane();
+    const int np = nplanes;
+    int namps = 0;
+    for (int k = 0; k < nbands; ++k) {
+      CMBL_REQUIRE(band_nbins[k] >= 1 && band_nbins[k] <= 65535, ERR_ARG, "theta_model: a band needs 1 ... 65535 bins");
+      CMBL_REQUIRE(band_planes[k] > 0 && band_planes[k] < (1 << np) && (np != 5 || !(band_planes[k] & 16)), ERR_ARG, "theta_model: a band rescales planes of the covariance, never BB of the block form");
+      for (long j = 0; j < pl; ++j) CMBL_REQUIRE(band_idx[(size_t)k * pl + j] >= 0 && band_idx[(size_t)k * pl + j] <= band_nbins[k], ERR_ARG, "theta_model: a bin index outside [0, nbins]");
+      namps += band_nbins[k];
+    }
+    std::vector<double> h((size_t)(5 * np + 4) * pl, 0.0);
+    double *hcfs = h.data(), *hc0 = hcfs + np * pl, *hcten = hc0 + np * pl, *hcn = hcten + np * pl, *hd0 = hcn + np * pl;
+    double *hcphi = hd0 + np * pl, *hnphi = hcphi + pl, *hg0 = hnphi + pl, *hgu = hg0 + pl;
+    th_toF(cfs, hcfs, np); th_toF(cten, hcten, np); th_toF(cn, hcn, np); th_toF(cphi0, hcphi, 1); th_toF(nphi, hnphi, 1);
+    if (c0) th_toF(c0, hc0, np);
+    if (g) th_toF(g, hgu, 1);
+    for (long j = 0; j < pl; ++j) {
+      if (np == 5) {
+        auto at = [&](const double* a) { return ThBlk{a[j], a[pl + j], a[2 * pl + j], a[3 * pl + j], a[4 * pl + j]}; };
+        const ThBlk d0i = th_pinv(th_mix(th_add(at(hcfs), at(hcten)), th_noise2(at(hcn), s2len)));
+        hd0[j] = d0i.a; hd0[pl + j] = d0i.b; hd0[2 * pl + j] = d0i.c; hd0[3 * pl + j] = d0i.d; hd0[4 * pl + j] = d0i.e;
+      } else {
+        for (int p = 0; p < np; ++p) hd0[p * pl + j] = th_pinv(th_mix(hcfs[p * pl + j] + hcten[p * pl + j], hcn[p * pl + j], s2len));
+      }
+      hg0[j] = th_pinv(th_g(hnphi[j], hcphi[j]));
+    }
+    th.set = false;                            // a second install replaces the first; a failed one leaves none
+    th.planes.ensure(sizeof(double) * h.size());
+    CMBL_HIP(hipMemcpyAsync(th.planes.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
+    if (nbands) {
+      std::vector<int32_t> hb((size_t)nbands * pl);
+      th_toF(band_idx, hb.data(), nbands);
+      th.bidx.ensure(sizeof(int32_t) * hb.size());
+      CMBL_HIP(hipMemcpyAsync(th.bidx.p, hb.data(), sizeof(int32_t) * hb.size(), hipMemcpyHostToDevice, c->stream));
+      CMBL_HIP(hipStreamSynchronize(c->stream));   // hb goes away
+    }
+    CMBL_HIP(hipStreamSynchronize(c->stream));     // ... and h
+    th.ops.ensure(sizeof(T) * (2 * np + 2) * pl);
+    th.part.ensure(sizeof(double) * 3 * TH_MAXBLK); th.sums.ensure(sizeof(double) * 3);
+    th.np = np; th.nbands = nbands; th.namps = namps; th.has_c0 = c0 != nullptr; th.has_g = g != nullptr;
+    for (int k = 0, off = 0; k < TH_MAXBANDS; ++k) {
+      th.bmask[k] = k < nbands ? band_planes[k] : 0; th.bnb[k] = k < nbands ? band_nbins[k] : 0; th.boff[k] = off;
+      off += th.bnb[k];
+    }
+    th.s2len = s2len; th.r0 = r0; th.aphi0 = aphi0; th.logdet_cn = logdet_cn;
+    th.set = true;
+  }
+  // the operators of one θ into the scratch sets and the three sums into th.sums (device).  r / aphi NaN: not named.  amps_dev: this θ's
+  // amplitude vectors on the device, or nullptr (ones)
+  void theta_eval(double r, double aphi, const double* amps_dev) {
+    CMBL_REQUIRE(th.set, ERR_STATE, "no θ model has been installed on this data set (cmbl_dataset_theta_model)");
+    const long pl = c->plane();
+    const double* d = th.planes.template as<double>();
+    ThetaDev m{};
+    m.cfs = d; m.c0 = th.has_c0 ? d + th.np * pl : nullptr; m.cten = d + 2 * th.np * pl; m.cn = d + 3 * th.np * pl; m.d0inv = d + 4 * th.np * pl;
+    m.cphi0 = d + 5 * th.np * pl; m.nphi = m.cphi0 + pl; m.g0inv = m.nphi + pl; m.guser = th.has_g ? m.g0inv + pl : nullptr;
+    for (int k = 0; k < TH_MAXBANDS; ++k) { m.bidx[k] = k < th.nbands ? th.bidx.template as<int>() + (size_t)k * pl : nullptr; m.bmask[k] = th.bmask[k]; m.bnb[k] = th.bnb[k]; m.boff[k] = th.boff[k]; }
+    m.nbands = th.nbands; m.np = th.np; m.Nx = c->Nx; m.Ny = c->Ny; m.Nyh = c->Nyh; m.pl = pl; m.s2len = th.s2len; m.aphi0 = th.aphi0;
+    ThetaPoint t{};
+    t.r_named = !std::isnan(r); t.s = (t.r_named ? r : th.r0) / th.r0;
+    t.g_theta = !std::isnan(aphi) && !th.has_g; t.aphi = std::isnan(aphi) ? th.aphi0 : aphi;
+    t.amps = amps_dev;
+    const int nblk = (int)std::min<long>(TH_MAXBLK, (pl + NTP - 1) / NTP);
+    double* part = th.part.template as<double>();
+    if (th.np == 5) CMBL_LAUNCH(c, K_PWFLAT, (k_theta_ops<T, true>), dim3((unsigned)nblk), 0, c->stream, m, t, th_op(OP_CF_INV), th_op(OP_D_INV), th_op(OP_CPHI_INV), th_op(OP_G_INV), part);
+    else CMBL_LAUNCH(c, K_PWFLAT, (k_theta_ops<T, false>), dim3((unsigned)nblk), 0, c->stream, m, t, th_op(OP_CF_INV), th_op(OP_D_INV), th_op(OP_CPHI_INV), th_op(OP_G_INV), part);
+    CMBL_LAUNCH(c, K_REDUCE, k_theta_sum, dim3(1), 0, c->stream, (const double*)part, nblk, th.sums.template as<double>());
+  }
+  void theta_sums(double* s3) {
+    CMBL_HIP(hipMemcpyAsync(s3, th.sums.p, sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
+    CMBL_HIP(hipStreamSynchronize(c->stream));
+  }
+  const double* theta_amps(const double* amps_host, int namps, int ntheta) {
+    CMBL_REQUIRE(th.set, ERR_STATE, "no θ model has been installed on this data set (cmbl_dataset_theta_model)");
+    CMBL_REQUIRE(amps_host ? namps == th.namps : namps == 0, ERR_SHAPE, "the amplitude vectors of a θ hold one value per bin of every band of the installed model (or none at all)");
+    if (!amps_host || namps == 0) return nullptr;
+    th.amps.ensure(sizeof(double) * (size_t)namps * ntheta);
+    CMBL_HIP(hipMemcpyAsync(th.amps.p, amps_host, sizeof(double) * (size_t)namps * ntheta, hipMemcpyHostToDevice, c->stream));
+    CMBL_HIP(hipStreamSynchronize(c->stream));     // the caller's array may go away
+    return th.amps.template as<double>();
+  }
+  // lp[i * B + b] = logpdf(Mixed(ds); f°_b, phi°_b, θ_i) (src/dataset.jl:84-87).  The four θ-dependent operator sets and logdet_sum of the data set
+  // point at the scratch sets while the grid runs and are put back on every way out.
+  void logpdf_mixed_theta(Flow<T>& L, const T* fo, const cx<T>* phio_F, int B, int ntheta, const double* r, const double* aphi, const double* amps_host,
+                          int namps, double* lp) {
+    const double* ad = theta_amps(amps_host, namps, ntheta);
+    static constexpr int ids[4] = {OP_CF_INV, OP_D_INV, OP_CPHI_INV, OP_G_INV};
+    struct Saved { int nplanes, kind; const T* d[5]; };
+    struct Restore {
+      Dataset* ds; Saved s[4]; double logdet;
+      ~Restore() { for (int i = 0; i < 4; ++i) { Op& o = ds->ops[ids[i]]; o.nplanes = s[i].nplanes; o.kind = s[i].kind; for (int k = 0; k < 5; ++k) o.d[k] = s[i].d[k]; } ds->logdet_sum = logdet; }
+    } keep{this, {}, logdet_sum};
+    for (int i = 0; i < 4; ++i) { const Op& o = ops[ids[i]]; keep.s[i].nplanes = o.nplanes; keep.s[i].kind = o.kind; for (int k = 0; k < 5; ++k) keep.s[i].d[k] = o.d[k]; }
+    const long pl = c->plane();
+    for (int i = 0; i < 4; ++i) {
+      Op& o = ops[ids[i]];
+      const int n = i < 2 ? th.np : 1;
+      o.nplanes = n; o.kind = n == 5 ? 2 : 1;
+      for (int k = 0; k < 5; ++k) o.d[k] = k < n ? th_op(ids[i]) + (size_t)k * pl : nullptr;
+    }
+    for (int i = 0; i < ntheta; ++i) {
+      theta_eval(r[i], aphi[i], ad ? ad + (size_t)i * namps : nullptr);
+      double s[3];
+      theta_sums(s);
+      logdet_sum = s[0] + th.logdet_cn;
+      logpdf_mixed(L, fo, phio_F, lp + (size_t)i * B, nullptr, nullptr, B, false);
+      for (int b = 0; b < B; ++b) lp[(size_t)i * B + b] -= s[1] + s[2];
+    }
+  }
+  // testing aid: the scratch operator set `which` of one θ in the reference layout, and the three sums
+  void theta_readback(double r, double aphi, const double* amps_host, int namps, int which, T* out_ref, double* sums_host) {
+    CMBL_REQUIRE(which == OP_CF_INV || which == OP_D_INV || which == OP_CPHI_INV || which == OP_G_INV, ERR_ARG, "theta_ops: which is CMBL_OP_CF_INV, _D_INV, _CPHI_INV or _G_INV");
+    const double* ad = theta_amps(amps_host, namps, 1);
+    theta_eval(r, aphi, ad);
+    if (out_ref) c->F2ref_real(th_op(which), out_ref, (which == OP_CF_INV || which == OP_D_INV) ? th.np : 1);
+    double s[3];
+    theta_sums(s);
+    if (sums_host) for (int k = 0; k < 3; ++k) sums_host[k] = s[k];
   }
 };
 

@@ -472,7 +472,7 @@ def gibbs_step(ds, phi, white_f, white_n, white_p, log_u, N=25, eps=0.01, always
 # ---------------------------------------------------------------------------------------------------------------------
 def sample_joint(ds, nsamps_per_chain, chain_ids=(0,), base_seed=0, phi_start="prior", N=25, eps=0.01, nburnin_always_accept=10,
                  dist=None, nchains_total=None, progress=None, rng="host", first_step=0, filename=None, nfilewrite=5, nsavemaps=1,
-                 resume=None, theta_ranges=None, theta_start="prior", alias_quirk=None):
+                 resume=None, theta_ranges=None, theta_start="prior", alias_quirk=None, theta_on="host"):
     """`sample_joint` at fixed θ (src/sampling.jl:180-335): Gibbs loop  f | ϕ  ->  mix  ->  HMC ϕ° | f°  ->  unmix  ->  logpdf.
     The chains owned by this process are the batch slots of `ds` (`ds.d` must have len(chain_ids) slots; the reference runs
     chains under pmap, one worker per GPU, src/sampling.jl:266,292).  Chain c draws from its own generator keyed by
@@ -487,7 +487,8 @@ def sample_joint(ds, nsamps_per_chain, chain_ids=(0,), base_seed=0, phi_start="p
     `theta_ranges` = {"Aphi": grid, "r": grid} adds the Gibbs θ passes (`gibbs_sample_slice_θ!`, :427-437) after the HMC pass; the
     dataset's ParamDependentOps are then re-evaluated at the sampled θ for the following passes (single chain per dataset).  The
     sampled θ is part of every saved sample (`theta_<key>`, like `filter_for_saving` keeps θ, :226-228) and a resumed run continues
-    from the file's last θ (:247-256).
+    from the file's last θ (:247-256).  `theta_on` = "host" | "device": where the grid of a θ pass is evaluated (`theta.gibbs_sample_theta(on=...)`);
+    the one `set_theta` at the end of a pass, which the HMC step, the mass matrix and the saved state read, is on the host either way.
     Defaults follow the reference (:190-214): `phi_start="prior"` draws ϕ ~ 𝒩(0, Cϕ) (0 / None = zero, or a Field), `theta_start=
     "prior"` draws θ uniformly inside its range (or a dict), `nburnin_always_accept=10`.  Step numbering: the reference stores the
     initial state as step 1 and its first Gibbs pass is step 2 (:268,277); here the first Gibbs pass is saved as step 1, so
@@ -501,6 +502,7 @@ def sample_joint(ds, nsamps_per_chain, chain_ids=(0,), base_seed=0, phi_start="p
     B = len(chain_ids)
     assert ds.d.arr.shape[0] == B, "dataset batch size must equal the number of local chains"
     assert rng in ("host", "device")
+    assert theta_on in ("host", "device"), theta_on
     multi = dist is not None and dist.is_initialized() and dist.get_world_size() > 1
     rank = dist.get_rank() if multi else 0
     assert not multi or nchains_total is not None, "nchains_total (chains over all ranks) is required when running on more than one rank"
@@ -593,7 +595,7 @@ def sample_joint(ds, nsamps_per_chain, chain_ids=(0,), base_seed=0, phi_start="p
             def tpass(fo_, po_, step=step):
                 for j, (key, xs) in enumerate(theta_ranges.items()):
                     uu = R.uniform(seeds[0], R.stream_id(R.STREAM_U + 1 + j, step)) if rng == "device" else [rngs[0].random()]
-                    val, _ = TH.gibbs_sample_theta(ds, fo_, po_, theta, key, xs, uu)
+                    val, _ = TH.gibbs_sample_theta(ds, fo_, po_, theta, key, xs, uu, on=theta_on)
                     theta[key] = float(val[0])
                 TH.set_theta(ds, **theta)
         st = gibbs_step(ds, phi, wf, wn, wp, logu, N=N, eps=eps, always_accept=(step + 2 < nburnin_always_accept), theta_pass=tpass,

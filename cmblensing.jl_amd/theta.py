@@ -7,11 +7,18 @@
     src/sampling.jl:80-135,427-437   grid_and_sample, gibbs_sample_slice_θ!
 Like the reference's ParamDependentOp (src/specialops.jl:314-330: recompute on the host side of the storage, then adapt) the ℓ-space
 planes are recomputed on the host for each θ and uploaded (a handful of (Nx, Ny/2+1) planes); every field operation stays on the
-device.  The smoothing / quadrature inside grid_and_sample are Loess.jl / QuadGK / Roots in the reference -- third-party numerics
+device.  The grid of a Gibbs θ pass need not go that way: `logpdf_mixed_theta_grid` (`gibbs_sample_theta(on="device")`) installs what `_ops`
+reads on the device once and has a kernel make the four operator sets and the log-determinants of every grid point there (csrc/kernels_theta.hpp;
+`_ops` stays the definition of every formula).  The smoothing / quadrature inside grid_and_sample are Loess.jl / QuadGK / Roots in the reference -- third-party numerics
 whose outputs are not pinned; here: local-quadratic LOESS with tricube weights and a trapezoid CDF on a fine grid.
 """
-import numpy as np
+import ctypes
 
+import numpy as np
+import torch
+
+from .engine import LenseFlow, MAP, FOURIER, _ptr
+from .lib import check
 from .sim import HarmOp, _pinv
 
 
@@ -116,6 +123,98 @@ def logpdf_mixed_theta(ds, fo, po, r=None, Aphi=None, **bands):
     return ds.logpdf_mixed(fo, po)
 
 
+# ---- the θ layer on the device (cmbl_dataset_theta_model / cmbl_logpdf_mixed_theta, include/cmblens.h) ---------------------------------
+_pd = ctypes.POINTER(ctypes.c_double)
+_pi = ctypes.POINTER(ctypes.c_int)
+_MODEL_KEYS = ("Cfs", "Cten", "Cn", "Cphi0", "Nphi", "Cfs_bands", "G_user", "logdet_Cn")
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _dp(a):
+    return None if a is None else a.ctypes.data_as(_pd)
+
+
+def _install_theta_model(ds):
+    """install on the device what `_ops` reads (once; again when one of the host entries it was built from is another object)"""
+    h = ds.host
+    h.setdefault("Cphi0", np.asarray(h["Cphi"], float).copy())
+    key = tuple(h.get(k) for k in _MODEL_KEYS)
+    scal = (float(h["s2len"]), float(h["r0"]), float(h["Aphi0"]))
+    old = getattr(ds, "_theta_model", None)
+    if old is not None and all(a is b for a, b in zip(old[0], key)) and old[1] == scal:
+        return
+    Cfs, Cten, Cn = (_f64(h[k].p) for k in ("Cfs", "Cten", "Cn"))
+    cb = h.get("Cfs_bands")
+    C0 = planes = idx = nbins = None
+    nbands = 0
+    if cb is not None:
+        C0 = _f64(cb.C0.p)
+        nbands = len(cb.bands)
+        planes = np.array([sum(1 << k for k in pl) for pl, _, _ in cb.bands.values()], dtype=np.int32)
+        idx = np.ascontiguousarray(np.stack([i for _, i, _ in cb.bands.values()]) if nbands else np.zeros(0), dtype=np.int32)
+        nbins = np.array([nb for _, _, nb in cb.bands.values()], dtype=np.int32)
+    Cphi0, Nphi = _f64(h["Cphi0"]), _f64(h["Nphi"])
+    G = _f64(h["G_user"]) if "G_user" in h else None
+    logdet_Cn = h["logdet_Cn"] if h.get("logdet_Cn") is not None else h["Cn"].logdet(ds.proj)
+    check(ds.lib.cmbl_dataset_theta_model(ds._h, _dp(Cfs), Cfs.shape[0], _dp(C0), nbands, None if planes is None else planes.ctypes.data_as(_pi),
+                                          None if idx is None else ctypes.c_void_p(idx.ctypes.data), None if nbins is None else nbins.ctypes.data_as(_pi),
+                                          _dp(Cten), _dp(Cn), scal[0], scal[1], _dp(Cphi0), scal[2], _dp(Nphi), _dp(G), float(logdet_Cn)))
+    ds._theta_model = (key, scal)
+
+
+def _theta_rows(ds, thetas):
+    """(r, Aϕ, amplitude rows or None) of a list of θ dicts; a parameter that is None or absent is 'not named': NaN / ones"""
+    cb = ds.host.get("Cfs_bands")
+    names = list(cb.bands) if cb is not None else []
+    nan = float("nan")
+    r = np.array([nan if th.get("r") is None else float(th["r"]) for th in thetas], dtype=np.float64)
+    A = np.array([nan if th.get("Aphi") is None else float(th["Aphi"]) for th in thetas], dtype=np.float64)
+    for th in thetas:
+        extra = [k for k in th if k not in ("r", "Aphi") and k not in names]
+        if extra:
+            raise ValueError(f"bandpower amplitudes {extra} given but the dataset has no such bandpower covariance (theta.use_bandpowers)")
+    if not names or all(th.get(n) is None for th in thetas for n in names):
+        return r, A, None
+    rows = [np.concatenate([np.ones(cb.bands[n][2]) if th.get(n) is None else np.asarray(th[n], float).ravel() for n in names]) for th in thetas]
+    if len({len(x) for x in rows}) != 1:
+        raise ValueError("the θ of one grid call must give each amplitude vector with the same length")
+    return r, A, _f64(np.stack(rows))
+
+
+def logpdf_mixed_theta_grid(ds, fo, po, thetas):
+    """logpdf(Mixed(ds); f°, ϕ°, θ) for every θ of `thetas` (dicts as `set_theta` takes them) -> (len(thetas), B), in ONE library call: per θ a
+    pointwise kernel makes pinv(Cf), pinv(D), pinv(Cϕ), pinv(G) and the log-determinants on the device from the resident model and the value is
+    the library's `logpdf_mixed`; only scalars cross to the host.  `ds.ops`, `ds.host`, `ds.theta`, `ds.logdet_sum` and `ds.logdet_mix` are not
+    touched: the data set stays at the θ it had.  The model is installed on first use and kept while the host entries it was built from
+    (`Cfs`, `Cten`, `Cn`, `Cphi0`, `Nphi`, `Cfs_bands`, `G_user`, `logdet_Cn`) are the same objects."""
+    if not isinstance(ds.L, LenseFlow):
+        raise ValueError(f"logpdf_mixed_theta_grid: the library's logpdf_mixed is defined for a LenseFlow in ds.L, not {type(ds.L).__name__}")
+    thetas = list(thetas)
+    fo, po = fo.to(MAP), po.to(FOURIER)
+    _install_theta_model(ds)
+    r, A, amps = _theta_rows(ds, thetas)
+    B, n = fo.arr.shape[0], len(thetas)
+    lp = np.empty((n, B), dtype=np.float64)
+    ds.L.invalidate()
+    check(ds.lib.cmbl_logpdf_mixed_theta(ds._h, ds.L._h, _ptr(fo.arr), _ptr(po.arr), B, n, _dp(r), _dp(A), _dp(amps), 0 if amps is None else amps.shape[1], _dp(lp)))
+    return lp
+
+
+def theta_ops_device(ds, which, r=None, Aphi=None, **bands):
+    """TESTING AID (`cmbl_dataset_theta_ops`): the operator set `which` ("Cf_inv", "D_inv", "Cphi_inv", "G_inv") that the θ kernel makes at one θ,
+    as a device tensor in the reference layout, and the three sums (logdet Cf + logdet Cϕ, logdet(D0⁻¹ D), logdet G)"""
+    _install_theta_model(ds)
+    rr, A, amps = _theta_rows(ds, [dict(r=r, Aphi=Aphi, **bands)])
+    npl = ds.host["Cfs"].p.shape[0] if which in ("Cf_inv", "D_inv") else 1
+    out = torch.empty((npl, ds.proj.Nx, ds.proj.Nyh), dtype=ds.proj.T, device=ds.proj.device)
+    sums = np.empty(3)
+    check(ds.lib.cmbl_dataset_theta_ops(ds._h, float(rr[0]), float(A[0]), _dp(amps), 0 if amps is None else amps.shape[1], ds._ids[which], _ptr(out), _dp(sums)))
+    return out, sums
+
+
 def loess(xs, ys, x, span=0.25, degree=2):
     """local polynomial regression, tricube weights over the ceil(span·n) nearest points, evaluated at x"""
     xs, ys, x = np.asarray(xs, float), np.asarray(ys, float), np.atleast_1d(np.asarray(x, float))
@@ -147,13 +246,17 @@ def grid_and_sample(logpdfs, xs, u, span=0.25, nfine=2001):
     return float(np.interp(u, cdf / cdf[-1], xf)), (xf, sm - logA), loess(xs, lp, xs, span) - logA
 
 
-def gibbs_sample_theta(ds, fo, po, theta, key, xs, u, span=0.25):
+def gibbs_sample_theta(ds, fo, po, theta, key, xs, u, span=0.25, on="host"):
     """`gibbs_sample_slice_θ!(k)` (src/sampling.jl:427-437): conditional of θ[key] given (f°, ϕ°) and the other parameters, on the grid
-    `xs`, one draw per batch slot with uniforms `u`.  Returns (new value per slot, log pdf grid (nslots, len(xs)))."""
-    lps = []
-    for x in xs:
-        th = dict(theta, **{key: float(x)})
-        lps.append(logpdf_mixed_theta(ds, fo, po, **th))
-    lps = np.array(lps).T                                       # (B, nx)
+    `xs`, one draw per batch slot with uniforms `u`.  Returns (new value per slot, log pdf grid (nslots, len(xs))).
+    on="host": every grid point through `set_theta` (the data set is left at the last one); on="device": the whole grid from one
+    `logpdf_mixed_theta_grid` call, the data set stays where it was."""
+    if on not in ("host", "device"):
+        raise ValueError(f'on must be "host" or "device", got {on!r}')
+    grid = [dict(theta, **{key: float(x)}) for x in xs]
+    if on == "device":
+        lps = logpdf_mixed_theta_grid(ds, fo, po, grid).T       # (B, nx)
+    else:
+        lps = np.array([logpdf_mixed_theta(ds, fo, po, **th) for th in grid]).T
     out = [grid_and_sample(lps[b], xs, u[b], span) for b in range(lps.shape[0])]
     return np.array([o[0] for o in out]), np.array([o[2] for o in out])

@@ -562,6 +562,42 @@ int cmbl_logpdf_mixed(cmbl_dataset* ds, cmbl_flow* L, const void* fo, const void
 int cmbl_grad_logpdf_mixed(cmbl_dataset* ds, cmbl_flow* L, const void* fo, const void* phio, double* lp_host,
                            void* gfo, void* gphio, int nbatch, int alias_quirk);
 
+/* ---- the θ layer on the device: the ParamDependentOps of load_sim (src/dataset.jl:272-274, 316-328) and logpdf(Mixed(ds); f°, phi°, θ) (:84-87,
+ *      src/generic.jl:264-271) over a grid of θ -- the inner loop of gibbs_sample_slice_θ! (src/sampling.jl:427-437).  θ = (r, Aphi, bandpower amplitudes):
+ *        Cf(θ) = Cfs(amplitudes) + (r / r0) Cten,   Cphi(Aphi) = Cphi0 Aphi / Aphi0,   D(r) = sqrt((C + 2 Cn^ + σ²len) pinv(C)) with C = Cfs + (r / r0) Cten
+ *        (the amplitudes enter Cf, not D),   G(Aphi) = pinv(g0) sqrt(1 + 2 Nphi pinv(Cphi(Aphi))),  g0 the same root at Aphi0.
+ *      The definition of every formula is the host algebra of the Python layer (theta._ops, sim.HarmOp): the 2 x 2 TE block of an IQU data set reads its ET
+ *      plane for both off-diagonals, `+ scalar` touches TT, EE and BB, pinv is 1 / x with every non-finite result replaced by 0, logdet is
+ *      Σ λ log|x| over the half plane with non-finite terms skipped.  All arithmetic is double in either precision, no product is fused into a sum or
+ *      difference (pinv is discontinuous at a determinant that is exactly 0), and only the store of an operator plane rounds.
+ *   cmbl_dataset_theta_model: installs, once per data set, what the operators are made of.  Every pointer is a HOST pointer to doubles in the reference
+ *      layout, real (Ny/2+1, Nx) planes, and is copied (as cmbl_clbins_create copies its weights); a second call replaces the first.
+ *      Cfs_host, Cten_host, Cn_host: scalar and tensor signal covariance and the Fourier-diagonal noise Cn^, `nplanes` = npol planes each (5 for IQU: TT, TE,
+ *      ET, EE, BB); another count is CMBL_ERR_SHAPE.  C0_host (NULL without bands): the base covariance the bandpower amplitudes rescale (it replaces Cfs
+ *      inside Cf, not inside D).  nbands in [0, 3]; per band k: band_planes_host[k] a bit mask of the planes of C0 it rescales (bit p = plane p; BB of the
+ *      block form is never rescaled), band_idx_host + k * plane the bin index of every mode (int32, decided by the caller; the value band_nbins_host[k]
+ *      names the constant amplitude 1 of modes outside the edges; anything outside [0, nbins] is CMBL_ERR_ARG), band_nbins_host[k] its number of bins.
+ *      Cphi0_host, Nphi_host: one plane each; G_host: a fixed G plane or NULL -- with it G is that plane at every θ and logdet G is 0 (`if G == nothing`, :317).
+ *      logdet_Cn: the constant third term of logdet_sum (also what a data set with CMBL_OP_CN_INV_PIX uses: Σ log V).  D(r0) and g0 are derived here.
+ *   cmbl_logpdf_mixed_theta: lp_host[i * nbatch + b] = logpdf(Mixed(ds); f°_b, phi°_b, θ_i), i < ntheta; fo, phio as for cmbl_logpdf_mixed.  r_host[i] / Aphi_host[i]:
+ *      NaN means "not named in θ_i": the operators stay fiducial and the parameter's term of the mixing log-determinant is exactly 0; with Aphi not named,
+ *      or with a fixed G, G is 1 (or the fixed plane).  amps_host: ntheta rows of namps doubles, the amplitude vectors of the bands concatenated in
+ *      the order of the install, or NULL with namps = 0 (all ones); another namps than the model's Σ nbins is CMBL_ERR_SHAPE.  Per θ: one pointwise pass
+ *      writes pinv(Cf), pinv(D), pinv(Cphi), pinv(G) into scratch sets owned by the data set and reduces logdet Cf + logdet Cphi, logdet(D(r0)^-1 D) and
+ *      logdet G in double (two stages, fixed order, no atomics: bit-identical between runs); CMBL_OP_CF_INV, _D_INV, _CPHI_INV, _G_INV and logdet_sum of
+ *      the data set point at them while cmbl_logpdf_mixed's own code runs (whichever path the context takes), and the two mixing log-determinants are
+ *      subtracted.  The data set is put back as it was on every way out, an error included.  Only scalars cross to the host per θ; nothing is allocated
+ *      after the first call.  A NaN logpdf is a value, not an error.  Before any cmbl_dataset_theta_model: CMBL_ERR_STATE.  L's phi is overwritten.
+ *   cmbl_dataset_theta_ops: a TESTING AID.  Evaluates the pass at one θ and copies the scratch set `which` (CMBL_OP_CF_INV, _D_INV: npol or 5 planes;
+ *      CMBL_OP_CPHI_INV, _G_INV: 1 plane; else CMBL_ERR_ARG) to out_dev (device, the context's precision, reference layout; may be NULL) and the three sums,
+ *      in the order above, to sums_host (may be NULL).  The data set's own operators are not touched.  Synchronises. */
+int cmbl_dataset_theta_model(cmbl_dataset* ds, const double* Cfs_host, int nplanes, const double* C0_host, int nbands, const int* band_planes_host,
+                             const int32_t* band_idx_host, const int* band_nbins_host, const double* Cten_host, const double* Cn_host, double s2len,
+                             double r0, const double* Cphi0_host, double Aphi0, const double* Nphi_host, const double* G_host, double logdet_Cn);
+int cmbl_logpdf_mixed_theta(cmbl_dataset* ds, cmbl_flow* L, const void* fo, const void* phio, int nbatch, int ntheta, const double* r_host,
+                            const double* Aphi_host, const double* amps_host, int namps, double* lp_host);
+int cmbl_dataset_theta_ops(cmbl_dataset* ds, double r, double Aphi, const double* amps_host, int namps, int which, void* out_dev, double* sums_host);
+
 /* ---- loop bodies of the reference's drivers, for hosts that are neither Julia (which keeps src/maximization.jl:116-233 and
  *      src/sampling.jl:388-464 itself on top of the entry points above) nor Python (cmblensing.jl_amd/drivers.py).  Control flow on the
  *      host inside the library, every field operation one of the launches above; both return when their host outputs are final.

@@ -486,6 +486,42 @@ function logpdf(mds::Mixed{<:HIPDataSet}; f°, ϕ°, θ=(;), Ω...)
     depends_on_θ(mds.ds, θ) ? lp - logdet(mds.ds.ds.D, θ) - logdet(mds.ds.ds.G, θ) : lp      # src/dataset.jl:86, on the θ-dependent originals
 end
 
+# ---- the θ layer on the device (include/cmblens.h): the grid of logpdf(Mixed(ds); f°, ϕ°, θ) of gibbs_sample_slice_θ! (src/sampling.jl:427-437) in
+# one call.  Thin wrappers over host arrays: planes are Float64 (Ny÷2+1, Nx[, nplanes]) arrays as `diag(op)` of the reference's operators gives
+# them, `bands` a vector of (planes = bit mask, idx::Matrix{Int32}, nbins) of a bandpower-rescaled Cf (src/proj_lambert.jl:374-411) or empty.
+function hip_theta_model!(hd::HIPDataSet, Cfs::Array{Float64}, Cten::Array{Float64}, Cn̂::Array{Float64}, σ²len, r₀, Cϕ₀::Matrix{Float64}, Aϕ₀,
+                          Nϕ::Matrix{Float64}, logdetCn; C₀=nothing, bands=(), G=nothing)
+    nb = length(bands)
+    masks = Cint[b.planes for b in bands]
+    idx = nb == 0 ? Int32[] : reduce(vcat, [vec(Int32.(b.idx)) for b in bands])
+    nbins = Cint[b.nbins for b in bands]
+    GC.@preserve Cfs Cten Cn̂ Cϕ₀ Nϕ C₀ G masks idx nbins chk(ccall((:cmbl_dataset_theta_model, lib), Cint,
+              (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cint}, Ptr{Int32}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble,
+               Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble),
+              hd.h, Cfs, size(Cfs, 3), isnothing(C₀) ? C_NULL : C₀, nb, nb == 0 ? C_NULL : masks, nb == 0 ? C_NULL : idx, nb == 0 ? C_NULL : nbins,
+              Cten, Cn̂, σ²len, r₀, Cϕ₀, Aϕ₀, Nϕ, isnothing(G) ? C_NULL : G, logdetCn))
+    hd
+end
+# rs, Aϕs: one value per θ, NaN = "not named in θ"; amps: (Σ nbins, nθ) matrix of amplitude vectors or nothing.  -> (nbatch, nθ) matrix
+function hip_logpdf_mixed_theta(hd::HIPDataSet, f°::Field, ϕ°::Field, rs::Vector{Float64}, Aϕs::Vector{Float64}, amps::Union{Nothing,Matrix{Float64}}=nothing)
+    fo, po = Ł(f°), Fourier(ϕ°)
+    B, nθ = nbatch(fo), length(rs)
+    lp = Matrix{Cdouble}(undef, B, nθ)
+    a, b = fo.arr, po.arr
+    GC.@preserve a b lp rs Aϕs amps chk(ccall((:cmbl_logpdf_mixed_theta, lib), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+              hd.h, hd.L.h, devptr(a), devptr(b), B, nθ, rs, Aϕs, isnothing(amps) ? C_NULL : amps, isnothing(amps) ? 0 : size(amps, 1), lp))
+    hd.L.cached = nothing
+    lp
+end
+# testing aid: the operator set `which` (0 Cf⁻¹, 5 D⁻¹, 7 Cϕ⁻¹, 8 G⁻¹) the θ kernel makes at one θ into the device array `out`, and the three sums
+function hip_theta_ops!(out, hd::HIPDataSet, which::Integer, r::Float64, Aϕ::Float64, amps::Union{Nothing,Vector{Float64}}=nothing)
+    sums = Vector{Cdouble}(undef, 3)
+    GC.@preserve out sums amps chk(ccall((:cmbl_dataset_theta_ops, lib), Cint, (Ptr{Cvoid}, Cdouble, Cdouble, Ptr{Cdouble}, Cint, Cint, Ptr{Cvoid}, Ptr{Cdouble}),
+              hd.h, r, Aϕ, isnothing(amps) ? C_NULL : amps, isnothing(amps) ? 0 : length(amps), which, devptr(out), sums))
+    sums
+end
+
 # ---- reductions and random fields (optional: the generic Julia broadcasts on ROCArrays work too) ------------------------------
 # restricted to device-backed flat-sky fields: CPU fields and other projections keep the reference's own `dot`
 function LinearAlgebra.dot(a::BaseField{B,<:ProjLambert,<:Any,<:ROCArray}, b::BaseField{B,<:ProjLambert,<:Any,<:ROCArray}) where {B}
