@@ -594,6 +594,7 @@ struct Ctx : CtxBase {
     while (rpw > 1 && row_groups(slices, rpw) < row_fill_target()) rpw >>= 1;
     return rpw;
   }
+  template <int V> using IC = std::integral_constant<int, V>;
   template <int RPWMAX, int LGNX, typename Fn> void dispatch_rpw(long slices, Fn&& fn) const {
     if constexpr (row_rpw_variants(LGNX)) {
       const int rpw = pick_rpw(RPWMAX, LGNX, slices);
@@ -603,13 +604,6 @@ struct Ctx : CtxBase {
     } else fn(std::integral_constant<int, RPWMAX>{});
   }
 
-  template <typename Fn> void dispatch_col(const TileY& t, Fn&& fn) const {
-    bool done = false;
-#define CMBL_X(lgm, r, nt) if (!done && lgM == lgm && t.R == r && t.NT == nt) { fn(std::integral_constant<int, lgm>{}, std::integral_constant<int, r>{}, std::integral_constant<int, nt>{}); done = true; }
-    CMBL_COL_LIST(CMBL_X)
-#undef CMBL_X
-    if (!done) fail(ERR_SHAPE, "unsupported column tile");
-  }
   template <typename Fn> void dispatch_row(Fn&& fn) const {
     bool done = false;
 #define CMBL_X(lgnx) if (!done && lgNx == lgnx) { fn(std::integral_constant<int, lgnx>{}); done = true; }
@@ -635,60 +629,70 @@ struct Ctx : CtxBase {
     if (generic) return transpose(in, out, Nyh, Nx, slices);
     CMBL_LAUNCH(this, K_LAYOUT, (k_F2ref<T>), dim3(Nx / 32, (Nyh + 31) / 32, (unsigned)slices), 0, stream, in, out, Nx, lgNx, Nyh);
   }
-  void y_r2c(const T* map, cx<T>* mixed, long slices) {
+  // ---- the two launchers of the fused kernels: every column / row launch of this path goes through them ------------------------------
+  // Column launch: the kernel sel(R, NT, LGM) -- compile-time constants of the tile's entry in CMBL_COL_LIST -- over (Nx / C tiles, the slices of
+  // THIS launch) on `st`, with the LDS of a pair or packed tile (ldsY)
+  template <typename Sel, typename... Args>
+  void launch_col(int kid, const TileY& t, bool pair, long slices, hipStream_t st, Sel sel, const Args&... args) {
     CMBL_REQUIRE(!generic, ERR_STATE, "fused column pass called on the any-size path");
-    const TileY t = tileY(slices, false);
-    dispatch_col(t, [&](auto lgm, auto r, auto nt) {
-      constexpr int LGM = decltype(lgm)::value, R = decltype(r)::value, NT = decltype(nt)::value;
-      CMBL_LAUNCH_NT(this, K_Y_R2C, NT, (k_y_r2c<T, R, NT, LGM>), dim3(Nx / t.C, (unsigned)slices), ldsY(t.C, false), stream, map, mixed, twY.as<cx<T>>(), Nx);
+    bool done = false;
+#define CMBL_X(lgm, r, nt)                                                                                                   \
+    if (!done && lgM == lgm && t.R == r && t.NT == nt) {                                                                       \
+      const auto kern = sel(IC<r>{}, IC<nt>{}, IC<lgm>{});                                                                     \
+      CMBL_LAUNCH_NT(this, kid, nt, kern, dim3(Nx / t.C, (unsigned)slices), ldsY(t.C, pair), st, args...);                     \
+      done = true;                                                                                                             \
+    }
+    CMBL_COL_LIST(CMBL_X)
+#undef CMBL_X
+    if (!done) fail(ERR_SHAPE, "unsupported column tile");
+  }
+  // Row launch: the kernel sel(LGNX, RPW) over the row groups of the `slices` slices of this launch, NBUF row sets in LDS.  op_slices: the slices of
+  // the whole operation when this launch is one launch chain of several -- the group height follows it (pick_rpw), not the chain's share.
+  // parts: the grid holds the row groups `parts` times (k_delta_rows: the d/dx part behind the adjoint part); apart: groups of full height ask for
+  // the LDS that keeps two of them off one CU (lds_apart; shorter groups are meant to share).  The argument ROW_GROUPS stands for the row groups.
+  struct RowGroups {};
+  static constexpr RowGroups ROW_GROUPS{};
+  template <typename A> static const A& row_arg(const A& a, int) { return a; }
+  static int row_arg(RowGroups, int nb) { return nb; }
+  template <int NBUF, typename Sel, typename... Args>
+  void launch_row(int kid, long op_slices, long slices, hipStream_t st, int parts, bool apart, Sel sel, const Args&... args) {
+    CMBL_REQUIRE(!generic, ERR_STATE, "fused row pass called on the any-size path");
+    dispatch_row([&](auto lgnx) {
+      constexpr int LGNX = decltype(lgnx)::value, RPWMAX = row_rpw<T>(LGNX, NBUF);
+      if constexpr (RPWMAX > 0) {
+        dispatch_rpw<RPWMAX, LGNX>(op_slices, [&](auto rpw_) {
+          constexpr int RPW = decltype(rpw_)::value;
+          const int nb = (int)row_groups(slices, RPW);
+          const size_t lds = apart && RPW == RPWMAX ? lds_apart(ldsX(RPW, NBUF), nb) : ldsX(RPW, NBUF);
+          const auto kern = sel(lgnx, rpw_);
+          CMBL_LAUNCH_NT(this, kid, row_nt(RPW), kern, dim3((unsigned)(parts * nb)), lds, st, row_arg(args, nb)...);
+        });
+      } else fail(ERR_SHAPE, "row tile does not fit LDS (Nx too large for this precision)");
     });
   }
+  void y_r2c(const T* map, cx<T>* mixed, long slices) {
+    launch_col(K_Y_R2C, tileY(slices, false), false, slices, stream, [](auto r, auto nt, auto lgm) { return k_y_r2c<T, r(), nt(), lgm()>; }, map, mixed, twY.as<cx<T>>(), Nx);
+  }
   void y_c2r(const cx<T>* mixed, T* map, long slices) {
-    CMBL_REQUIRE(!generic, ERR_STATE, "fused column pass called on the any-size path");
-    const TileY t = tileY(slices, false);
-    dispatch_col(t, [&](auto lgm, auto r, auto nt) {
-      constexpr int LGM = decltype(lgm)::value, R = decltype(r)::value, NT = decltype(nt)::value;
-      CMBL_LAUNCH_NT(this, K_Y_C2R, NT, (k_y_c2r<T, R, NT, LGM>), dim3(Nx / t.C, (unsigned)slices), ldsY(t.C, false), stream, mixed, map, twY.as<cx<T>>(), Nx, (T)(1.0 / Ny));
-    });
+    launch_col(K_Y_C2R, tileY(slices, false), false, slices, stream, [](auto r, auto nt, auto lgm) { return k_y_c2r<T, r(), nt(), lgm()>; }, mixed, map, twY.as<cx<T>>(), Nx,
+               (T)(1.0 / Ny));
   }
   // mixed -> (map x mask) -> mixed, for the pixel-mask sandwich (in place allowed)
   void y_mask(const cx<T>* in, cx<T>* out, const T* mask, long slices) {
-    CMBL_REQUIRE(!generic, ERR_STATE, "fused column pass called on the any-size path");
-    const TileY t = tileY(slices, false);
-    dispatch_col(t, [&](auto lgm, auto r, auto nt) {
-      constexpr int LGM = decltype(lgm)::value, R = decltype(r)::value, NT = decltype(nt)::value;
-      CMBL_LAUNCH_NT(this, K_MASK, NT, (k_y_mask<T, R, NT, LGM>), dim3(Nx / t.C, (unsigned)slices), ldsY(t.C, false), stream, in, out, mask, twY.as<cx<T>>(), Nx,
-                     (T)(1.0 / Ny));
-    });
+    launch_col(K_MASK, tileY(slices, false), false, slices, stream, [](auto r, auto nt, auto lgm) { return k_y_mask<T, r(), nt(), lgm()>; }, in, out, mask, twY.as<cx<T>>(), Nx,
+               (T)(1.0 / Ny));
   }
   // mixed -> (map x scale x weight plane of the slice) -> mixed, for the map-diagonal noise sandwich (in place allowed); slices = B * P,
   // weight: nplanes (1 or P) maps
   void y_weight(const cx<T>* in, cx<T>* out, const T* weight, int nplanes, int P, T scale, long slices) {
-    CMBL_REQUIRE(!generic, ERR_STATE, "fused column pass called on the any-size path");
-    const TileY t = tileY(slices, false);
-    dispatch_col(t, [&](auto lgm, auto r, auto nt) {
-      constexpr int LGM = decltype(lgm)::value, R = decltype(r)::value, NT = decltype(nt)::value;
-      CMBL_LAUNCH_NT(this, K_MASK, NT, (k_y_weight<T, R, NT, LGM>), dim3(Nx / t.C, (unsigned)slices), ldsY(t.C, false), stream, in, out, weight, nplanes, P,
-                     twY.as<cx<T>>(), Nx, (T)(scale / Ny));
-    });
+    launch_col(K_MASK, tileY(slices, false), false, slices, stream, [](auto r, auto nt, auto lgm) { return k_y_weight<T, r(), nt(), lgm()>; }, in, out, weight, nplanes, P,
+               twY.as<cx<T>>(), Nx, (T)(scale / Ny));
   }
   // all_slices: the slices of the whole operation when this call is one launch chain of several (the row-group height follows it)
   template <int MODE> void x_pass(const cx<T>* in, cx<T>* out, long slices, hipStream_t st = nullptr, long all_slices = 0) {
-    if (!st) st = stream;
-    if (all_slices <= 0) all_slices = slices;
     CMBL_REQUIRE(in != out, ERR_ARG, "x pass cannot run in place (tiled mixed layout on one side)");
-    CMBL_REQUIRE(!generic, ERR_STATE, "fused row pass called on the any-size path");
-    dispatch_row([&](auto lgnx) {
-      constexpr int LGNX = decltype(lgnx)::value, RPWMAX = row_rpw<T>(LGNX, 1);
-      if constexpr (RPWMAX > 0) {
-        dispatch_rpw<RPWMAX, LGNX>(all_slices, [&](auto rpw_) {
-          constexpr int RPW = decltype(rpw_)::value;
-          CMBL_LAUNCH_NT(this, (MODE == 2 ? K_X_GRAD : K_X_FFT), row_nt(RPW), (k_x_fft<T, MODE, LGNX, RPW>), dim3((unsigned)row_groups(slices, RPW)),
-                         ldsX(RPW, 1), st,
-                         in, out, twX.as<cx<T>>(), dlx_over_Nx, Nyh);
-        });
-      } else fail(ERR_SHAPE, "row tile does not fit LDS (Nx too large for this precision)");
-    });
+    launch_row<1>(MODE == 2 ? K_X_GRAD : K_X_FFT, all_slices > 0 ? all_slices : slices, slices, st ? st : stream, 1, false,
+                  [](auto lgnx, auto rpw) { return k_x_fft<T, MODE, lgnx(), rpw()>; }, in, out, twX.as<cx<T>>(), dlx_over_Nx, Nyh);
   }
   // map -> F  (m_rfft, src/util_fft.jl:20)
   // (the x pass reads the tiled mixed layout and writes F rows, or the reverse: it cannot run in place -- `xtmp` holds the mixed side)
@@ -1125,6 +1129,32 @@ struct Flow : FlowApi, LensOps<T> {
     r.stage = stage; r.last = last ? 1 : 0;
     return r;
   }
+  // The 4n RK stages of a flow from (t0, h), in order: stage index, coefficients (coef) and RK4 quadrature weight (src/numerical_algorithms.jl:20)
+  struct Stage { int it; RKCoef<T> rk; T w; };
+  template <typename F> void stages(double t0, double h, F&& body) const {
+    int it = 0;
+    for (int step = 0; step < n; ++step)
+      for (int stage = 1; stage <= 4; ++stage, ++it)
+        body(Stage{it, coef(step, stage, t0, h, step == n - 1 && stage == 4), (T)((stage == 1 || stage == 4 ? 1.0 : 2.0) * h / 6)});
+  }
+  // the (t_s, c_s) table of the delta-phi quadrature over the stored stages (dphi_finish)
+  void fill_tc(double t0, double h) {
+    tc_host.resize(2 * (size_t)(4 * n));
+    stages(t0, h, [&](const Stage& s) { tc_host[2 * s.it] = s.rk.t; tc_host[2 * s.it + 1] = s.w; });
+  }
+  // One launch chain of a flow (groups() / gen_groups()): its stream, first slice, slice count and the batch-slot offset of its phi maps (phi_off).
+  // run_chains: fork, every stage in turn and within it body(stage, chain) for the chains 0 .. K-1, then staged() once per stage; join.  Stage-major and
+  // chain-minor: the order in which the host feeds the streams is part of the measured behaviour.
+  struct Chain { hipStream_t st; long s0, ns, phi; };
+  template <typename Body, typename Staged> void run_chains(int K, long slices, int B, double t0, double h, Body&& body, Staged&& staged) {
+    const long gs = slices / K;
+    fork(K);
+    stages(t0, h, [&](const Stage& s) {
+      for (int g = 0; g < K; ++g) body(s, Chain{gstream(g), g * gs, gs, phi_off(g, K, B)});
+      staged();
+    });
+    join(K);
+  }
 
   // Small maps: the whole flow in one launch, one workgroup per slice with the half plane resident in LDS (kernels_small.hpp; defined in
   // engine_small.hpp, compiled by tu_small_*.hip).  small_ok: the shape has such a kernel in this precision and p(t) is cached.
@@ -1172,12 +1202,9 @@ struct Flow : FlowApi, LensOps<T> {
   // The RK stages of a flow: chain g of K runs stage(its run -- stream, slice window, the form's layout; K = 1: all slices on the main stream --, RK coefficients, stage index) for every stage in turn
   template <typename F> void gen_stages(const GenForm& fm, long slices, double t0, double h, F stage) {
     const int K = gen_groups(slices, fm);
-    fork(K);
-    for (int it = 0; it < 4 * n; ++it) {
-      const RKCoef<T> rk = coef(it / 4, it % 4 + 1, t0, h, it == 4 * n - 1);
-      for (int g = 0; g < K; ++g) stage(K <= 1 ? GenRun{c->stream, 0, -1, 0, fm.tile} : GenRun{gstream(g), g * (slices / K), slices / K, slices, fm.tile}, rk, it);
-    }
-    join(K);
+    run_chains(K, slices, 1 /* the any-size stages take phi of all slots */, t0, h, [&](const Stage& s, const Chain& ch) {
+      stage(K <= 1 ? GenRun{c->stream, 0, -1, 0, fm.tile} : GenRun{ch.st, ch.s0, ch.ns, slices, fm.tile}, s.rk, s.it);
+    }, [] {});
   }
   // Every buffer the chosen form of a flow can touch is sized here BEFORE the chains fork, and by nothing after it: a growth (hipFree / hipMalloc) inside
   // the multi-stream region would pull a buffer from under a launch of another chain.  gA, gGx, gT, gW2 and the mixed scratch are hand-off arrays.
@@ -1361,10 +1388,8 @@ struct Flow : FlowApi, LensOps<T> {
     CMBL_HIP(hipMemcpyAsync(gYs.p, df, sizeof(cx<T>) * slices * pl, hipMemcpyDeviceToDevice, c->stream));
     const double t0 = forward_primal ? 1.0 : 0.0, h = (forward_primal ? -1.0 : 1.0) / n;
     if (fm.stage != GenForm::REFERENCE) c->gen_y_r2c(GenRun{c->stream, 0, -1, 0, fm.tile}, gms.as<T>(), gA.as<cx<T>>(), slices);
-    tc_host.resize(2 * (size_t)nst);
+    fill_tc(t0, h);
     gen_stages(fm, slices, t0, h, [&](const GenRun& r, const RKCoef<T>& rk, int it) {
-      tc_host[2 * it] = rk.t;                                                // (time and quadrature weight of the stage, for dphi_finish; every chain writes the same)
-      tc_host[2 * it + 1] = (T)((it % 4 == 0 || it % 4 == 3 ? 1.0 : 2.0) * h / 6);
       const GenDelta d{rk, f, df, Wst.as<T>() + (size_t)(2 * it) * slices * np, P, it == 0, t3};
       switch (fm.stage) {
         case GenForm::FUSED: return gen_delta_fused(r, fm, d, slices);
@@ -1426,32 +1451,35 @@ struct Flow : FlowApi, LensOps<T> {
     cx<T>* a_cur = Ab.template as<cx<T>>(); cx<T>* a_nxt = A2.as<cx<T>>();
     if (!a_ready) c->y_r2c(in, a_cur, slices);                             // the first RK step reads the state from `in` (y0r), the rest from `out`
     const int K = groups(P, B);
-    const long gs = slices / K;                                            // slices per group
     const auto tile = c->tileY(slices, true);
     const double t0 = inverse ? 1.0 : 0.0, h = (inverse ? -1.0 : 1.0) / n;
-    fork(K);
-    for (int step = 0; step < n; ++step)
-      for (int stage = 1; stage <= 4; ++stage) {
-        for (int g = 0; g < K; ++g) {
-          hipStream_t st = gstream(g);
-          const long so = g * gs;
-          c->template x_pass<2>(a_cur + so * pl, Gx.as<cx<T>>() + so * pl, gs, st, slices);
-          FlowYArgs<T> a{};
-          a.A = a_cur + so * pl; a.Gx = Gx.as<cx<T>>() + so * pl; a.Anext = a_nxt + so * pl; a.y0 = y + so * np; a.acc = acc.as<T>() + so * np;
-          a.y0r = (step == 0 ? in : y) + so * np;
-          a.twY = c->twY.template as<cx<T>>(); a.ly = c->ly.template as<T>();
-          a.Nx = c->Nx; a.P = P; a.emit_last = emit_last ? 1 : 0;
-          a.rk = coef(step, stage, t0, h, step == n - 1 && stage == 4);
-          a.ph = ph(a.rk.t, phi_off(g, K, B));
-          a.pf = c->col_prefetch(c->Nx / tile.C, gs, K);
-          c->dispatch_col(tile, [&](auto lgm, auto r, auto nt) {
-            constexpr int LGM = decltype(lgm)::value, R = decltype(r)::value, NT = decltype(nt)::value;
-            CMBL_LAUNCH_NT(c, K_FLOW_Y, NT, (k_flow_y_fwd<T, R, NT, LGM>), dim3(c->Nx / tile.C, (unsigned)gs), c->ldsY(tile.C), st, a);
-          });
-        }
-        std::swap(a_cur, a_nxt);
-      }
-    join(K);
+    run_chains(K, slices, B, t0, h, [&](const Stage& s, const Chain& ch) {
+      c->template x_pass<2>(a_cur + ch.s0 * pl, Gx.as<cx<T>>() + ch.s0 * pl, ch.ns, ch.st, slices);
+      FlowYArgs<T> a = flow_y_args(s, ch, a_cur, a_nxt, y, P);
+      a.y0r = (s.it < 4 ? in : y) + ch.s0 * np;                            // (the first RK step)
+      a.emit_last = emit_last ? 1 : 0;
+      a.pf = c->col_prefetch(c->Nx / tile.C, ch.ns, K);
+      c->launch_col(K_FLOW_Y, tile, true, ch.ns, ch.st, [](auto r, auto nt, auto lgm) { return k_flow_y_fwd<T, r(), nt(), lgm()>; }, a);
+    }, [&] { std::swap(a_cur, a_nxt); });
+  }
+  // The argument blocks both kinds of fused stage fill alike, for one chain.  Column pass of a forward-type stage: a_cur -> a_nxt is the ping-pong pair of
+  // y-transform buffers, the state is read and updated at y (the touch-prefetch distance is the caller's: FlowYArgs::pf or DeltaYArgs::pf)
+  FlowYArgs<T> flow_y_args(const Stage& s, const Chain& ch, const cx<T>* a_cur, cx<T>* a_nxt, T* y, int P) const {
+    const long som = ch.s0 * c->mplane(), so = ch.s0 * c->npix();
+    FlowYArgs<T> a{};
+    a.A = a_cur + som; a.Gx = Gx.as<cx<T>>() + som; a.Anext = a_nxt + som; a.y0 = y + so; a.y0r = a.y0; a.acc = acc.as<T>() + so;
+    a.ph = ph(s.rk.t, ch.phi);
+    a.twY = c->twY.template as<cx<T>>(); a.ly = c->ly.template as<T>();
+    a.Nx = c->Nx; a.P = P; a.rk = s.rk;
+    return a;
+  }
+  // row pass of an adjoint-type stage: RK update of the Fourier state Y from (Wx, Wy), ifft_x of the next stage's state -> H
+  AdjXArgs<T> adj_x_args(const Stage& s, const Chain& ch, cx<T>* Y) const {
+    const long so = ch.s0 * c->plane(), som = ch.s0 * c->mplane();
+    AdjXArgs<T> x{};
+    x.Wx = Wx.as<cx<T>>() + som; x.Wy = Wy.as<cx<T>>() + som; x.Y0 = Y + so; x.acc = Yacc.as<cx<T>>() + so; x.Hnext = H.as<cx<T>>() + som;
+    x.twX = c->twX.template as<cx<T>>(); x.lx_r = c->lx_r.template as<T>(); x.Nyh = c->Nyh; x.rk = s.rk;
+    return x;
   }
 
   // L'*g (inverse=false, t 1->0) or L'\g (inverse=true, t 0->1); F layout, QU-Fourier basis; out may alias in
@@ -1467,42 +1495,18 @@ struct Flow : FlowApi, LensOps<T> {
     if (in != out) CMBL_HIP(hipMemcpyAsync(out, in, sizeof(cx<T>) * slices * pl, hipMemcpyDeviceToDevice, c->stream));
     if (!h_ready) c->template x_pass<1>(out, H.as<cx<T>>(), slices);
     const int K = groups(P, B);
-    const long gs = slices / K;
     const auto tile = c->tileY(slices, true);
     const double t0 = inverse ? 0.0 : 1.0, h = (inverse ? 1.0 : -1.0) / n;
-    fork(K);
-    for (int step = 0; step < n; ++step)
-      for (int stage = 1; stage <= 4; ++stage) {
-        const RKCoef<T> rk = coef(step, stage, t0, h, step == n - 1 && stage == 4);
-        for (int g = 0; g < K; ++g) {
-          hipStream_t st = gstream(g);
-          const long so = g * gs * pl, som = g * gs * mpl;
-          AdjYArgs<T> a{};
-          a.H = H.as<cx<T>>() + som; a.Wx = Wx.as<cx<T>>() + som; a.Wy = Wy.as<cx<T>>() + som; a.ph = ph(rk.t, phi_off(g, K, B));
-          a.twY = c->twY.template as<cx<T>>(); a.ly = c->ly.template as<T>();
-          a.Nx = c->Nx; a.P = P; a.t = rk.t;
-          a.pf = c->col_prefetch(c->Nx / tile.C, gs, K);
-          c->dispatch_col(tile, [&](auto lgm, auto r, auto nt) {
-            constexpr int LGM = decltype(lgm)::value, R = decltype(r)::value, NT = decltype(nt)::value;
-            CMBL_LAUNCH_NT(c, K_ADJ_Y, NT, (k_adj_y<T, R, NT, LGM>), dim3(c->Nx / tile.C, (unsigned)gs), c->ldsY(tile.C), st, a);
-          });
-          AdjXArgs<T> x{};
-          x.Wx = a.Wx; x.Wy = a.Wy; x.Y0 = out + so; x.acc = Yacc.as<cx<T>>() + so; x.Hnext = H.as<cx<T>>() + som;
-          x.twX = c->twX.template as<cx<T>>(); x.lx_r = c->lx_r.template as<T>(); x.Nyh = c->Nyh; x.rk = rk;
-          c->dispatch_row([&](auto lgnx) {
-            constexpr int LGNX = decltype(lgnx)::value, RPWMAX = row_rpw<T>(LGNX, 2);
-            if constexpr (RPWMAX > 0) {
-              c->template dispatch_rpw<RPWMAX, LGNX>(slices, [&](auto rpw_) {
-                constexpr int RPW = decltype(rpw_)::value;
-                // (lds_apart keeps two FULL-height groups off one CU; shorter groups are meant to share)
-                const size_t lds = RPW == RPWMAX ? c->lds_apart(c->ldsX(RPW, 2), c->row_groups(gs, RPW)) : c->ldsX(RPW, 2);
-                CMBL_LAUNCH_NT(c, K_ADJ_X, row_nt(RPW), (k_adj_x<T, LGNX, RPW>), dim3((unsigned)c->row_groups(gs, RPW)), lds, st, x);
-              });
-            } else fail(ERR_SHAPE, "row tile does not fit LDS (Nx too large for this precision)");
-          });
-        }
-      }
-    join(K);
+    run_chains(K, slices, B, t0, h, [&](const Stage& s, const Chain& ch) {
+      const long som = ch.s0 * mpl;
+      AdjYArgs<T> a{};
+      a.H = H.as<cx<T>>() + som; a.Wx = Wx.as<cx<T>>() + som; a.Wy = Wy.as<cx<T>>() + som; a.ph = ph(s.rk.t, ch.phi);
+      a.twY = c->twY.template as<cx<T>>(); a.ly = c->ly.template as<T>();
+      a.Nx = c->Nx; a.P = P; a.t = s.rk.t;
+      a.pf = c->col_prefetch(c->Nx / tile.C, ch.ns, K);
+      c->launch_col(K_ADJ_Y, tile, true, ch.ns, ch.st, [](auto r, auto nt, auto lgm) { return k_adj_y<T, r(), nt(), lgm()>; }, a);
+      c->template launch_row<2>(K_ADJ_X, slices, ch.ns, ch.st, 1, true, [](auto lgnx, auto rpw) { return k_adj_x<T, lgnx(), rpw()>; }, adj_x_args(s, ch, out));
+    }, [] {});
   }
 
   // delta flow (src/flowops.jl:48,63): state (f [map], df [F, QU-Fourier], dphi [F, S0]); f and df updated in place, dphi written.
@@ -1529,53 +1533,25 @@ struct Flow : FlowApi, LensOps<T> {
     if (!a_ready) c->y_r2c(f, a_cur, slices);
     if (!h_ready) c->template x_pass<1>(df, H.as<cx<T>>(), slices);
     const int K = groups(P, B, true);
-    const long gs = slices / K;
     const auto tile = c->tileY_delta(slices);
     const double t0 = forward_primal ? 1.0 : 0.0, h = (forward_primal ? -1.0 : 1.0) / n;
     c->template x_pass<2>(a_cur, Gx.as<cx<T>>(), slices);                // later d/dx passes ride along with the previous stage's row launch
-    tc_host.resize(2 * (size_t)nst);
-    fork(K);
-    int it = 0;
-    for (int step = 0; step < n; ++step)
-      for (int stage = 1; stage <= 4; ++stage, ++it) {
-        const bool last = step == n - 1 && stage == 4;
-        const RKCoef<T> rk = coef(step, stage, t0, h, last);
-        tc_host[2 * it] = rk.t;
-        tc_host[2 * it + 1] = (T)((stage == 1 || stage == 4 ? 1.0 : 2.0) * h / 6);   // RK4 weights (src/numerical_algorithms.jl:20)
-        for (int g = 0; g < K; ++g) {
-          hipStream_t st = gstream(g);
-          const long so = g * gs, sp = so * pl, spm = so * mpl, sm = so * np;
-          DeltaYArgs<T> d{};
-          FlowYArgs<T>& a = d.f;
-          a.A = a_cur + spm; a.Gx = Gx.as<cx<T>>() + spm; a.Anext = a_nxt + spm; a.y0 = f + sm; a.y0r = f + sm; a.acc = acc.as<T>() + sm; a.ph = ph(rk.t, phi_off(g, K, B));
-          a.twY = c->twY.template as<cx<T>>(); a.ly = c->ly.template as<T>();
-          a.Nx = c->Nx; a.P = P; a.rk = rk;
-          d.H = H.as<cx<T>>() + spm; d.Wx = Wx.as<cx<T>>() + spm; d.Wy = Wy.as<cx<T>>() + spm;
-          d.w1p = Wst.as<T>() + ((size_t)(2 * it) * slices + so) * np; d.w2p = d.w1p + (size_t)slices * np;
-          d.pf = c->col_prefetch(c->Nx / tile.C, gs, K);
-          c->dispatch_col(tile, [&](auto lgm, auto r, auto nt) {
-            constexpr int LGM = decltype(lgm)::value, R = decltype(r)::value, NT = decltype(nt)::value;
-            CMBL_LAUNCH_NT(c, K_DELTA_Y, NT, (k_delta_cols<T, R, NT, LGM>), dim3(c->Nx / tile.C, (unsigned)gs), c->ldsY(tile.C), st, d);
-          });
-          // delta-f row pass (RK update of df + next H) + d/dx of the next stage's f (a_nxt holds A_{s+1} after this column launch)
-          AdjXArgs<T> x{};
-          x.Wx = d.Wx; x.Wy = d.Wy; x.Y0 = df + sp; x.acc = Yacc.as<cx<T>>() + sp; x.Hnext = H.as<cx<T>>() + spm;
-          x.twX = c->twX.template as<cx<T>>(); x.lx_r = c->lx_r.template as<T>(); x.Nyh = c->Nyh; x.rk = rk;
-          GradXArgs<T> gx{a_nxt + spm, Gx.as<cx<T>>() + spm, x.twX, c->dlx_over_Nx, c->Nyh};
-          c->dispatch_row([&](auto lgnx) {
-            constexpr int LGNX = decltype(lgnx)::value, RPWMAX = row_rpw<T>(LGNX, 2);
-            if constexpr (RPWMAX > 0) {
-              c->template dispatch_rpw<RPWMAX, LGNX>(2 * slices, [&](auto rpw_) {          // adjoint part + d/dx part: twice the row groups
-                constexpr int RPW = decltype(rpw_)::value;
-                const int nb_adj = (int)c->row_groups(gs, RPW);
-                CMBL_LAUNCH_NT(c, K_DELTA_ROWS, row_nt(RPW), (k_delta_rows<T, LGNX, RPW>), dim3((unsigned)(nb_adj + (last ? 0 : nb_adj))), c->ldsX(RPW, 2), st, x, gx, nb_adj);
-              });
-            } else fail(ERR_SHAPE, "row tile does not fit LDS (Nx too large for this precision)");
-          });
-        }
-        std::swap(a_cur, a_nxt);
-      }
-    join(K);
+    fill_tc(t0, h);
+    run_chains(K, slices, B, t0, h, [&](const Stage& s, const Chain& ch) {
+      const long spm = ch.s0 * mpl;
+      DeltaYArgs<T> d{};
+      d.f = flow_y_args(s, ch, a_cur, a_nxt, f, P);
+      d.H = H.as<cx<T>>() + spm; d.Wx = Wx.as<cx<T>>() + spm; d.Wy = Wy.as<cx<T>>() + spm;
+      d.w1p = Wst.as<T>() + ((size_t)(2 * s.it) * slices + ch.s0) * np; d.w2p = d.w1p + (size_t)slices * np;
+      d.pf = c->col_prefetch(c->Nx / tile.C, ch.ns, K);
+      c->launch_col(K_DELTA_Y, tile, true, ch.ns, ch.st, [](auto r, auto nt, auto lgm) { return k_delta_cols<T, r(), nt(), lgm()>; }, d);
+      // delta-f row pass (RK update of df + next H) + d/dx of the next stage's f (a_nxt holds A_{s+1} after this column launch): twice the row
+      // groups, of the operation and -- but for the last stage -- of the launch
+      const AdjXArgs<T> x = adj_x_args(s, ch, df);
+      const GradXArgs<T> gx{a_nxt + spm, Gx.as<cx<T>>() + spm, x.twX, c->dlx_over_Nx, c->Nyh};
+      c->template launch_row<2>(K_DELTA_ROWS, 2 * slices, ch.ns, ch.st, s.rk.last ? 1 : 2, false, [](auto lgnx, auto rpw) { return k_delta_rows<T, lgnx(), rpw()>; }, x, gx,
+                                Ctx<T>::ROW_GROUPS);
+    }, [&] { std::swap(a_cur, a_nxt); });
     dphi_finish(dphi, P, B, nst, alias_quirk, tail);
   }
 

@@ -11,11 +11,8 @@ void Ctx<T>::y_lens(bool transposed, const LensTab<T>& tab, const T* in, cx<T>* 
   CMBL_REQUIRE(!generic, ERR_STATE, "fused column pass called on the any-size path");
   CMBL_REQUIRE((long)Ny * Nx < (1L << 31), ERR_SHAPE, "map too large for the 32-bit pixel indices of the lensing table");
   const TileY t = tileY(slices, false);
-  dispatch_col(t, [&](auto lgm, auto r, auto nt) {
-    constexpr int LGM = decltype(lgm)::value, R = decltype(r)::value, NT = decltype(nt)::value;
-    if (transposed) CMBL_LAUNCH_NT(this, K_LENS_Y, NT, (k_y_lens<T, R, NT, LGM, 1>), dim3(Nx / t.C, (unsigned)slices), ldsY(t.C, false), stream, tab, in, mixed, twY.template as<cx<T>>(), Nx);
-    else CMBL_LAUNCH_NT(this, K_LENS_Y, NT, (k_y_lens<T, R, NT, LGM, 0>), dim3(Nx / t.C, (unsigned)slices), ldsY(t.C, false), stream, tab, in, mixed, twY.template as<cx<T>>(), Nx);
-  });
+  if (transposed) launch_col(K_LENS_Y, t, false, slices, stream, [](auto r, auto nt, auto lgm) { return k_y_lens<T, r(), nt(), lgm(), 1>; }, tab, in, mixed, twY.template as<cx<T>>(), Nx);
+  else launch_col(K_LENS_Y, t, false, slices, stream, [](auto r, auto nt, auto lgm) { return k_y_lens<T, r(), nt(), lgm(), 0>; }, tab, in, mixed, twY.template as<cx<T>>(), Nx);
 }
 
 #define CMBL_INSTANTIATE_LENSOP(T) template void Ctx<T>::y_lens(bool, const LensTab<T>&, const T*, cx<T>*, long);

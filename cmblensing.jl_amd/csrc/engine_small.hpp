@@ -74,14 +74,7 @@ void Flow<T>::small_flow_delta(T* f, cx<T>* df, cx<T>* dphi, int P, int B, bool 
   Wst.ensure(sizeof(T) * (size_t)nst * 2 * slices * np);
   U5.ensure(sizeof(T) * 5 * B * np); F5.ensure(sizeof(cx<T>) * 5 * B * pl); tcbuf.ensure(sizeof(T) * 2 * nst);
   const double t0 = forward_primal ? 1.0 : 0.0, h = (forward_primal ? -1.0 : 1.0) / n;
-  tc_host.resize(2 * (size_t)nst);
-  int it = 0;
-  for (int step = 0; step < n; ++step)
-    for (int stage = 1; stage <= 4; ++stage, ++it) {                      // the (t_s, c_s) table of the quadrature, as Flow::flow_delta fills it
-      const RKCoef<T> rk = coef(step, stage, t0, h, step == n - 1 && stage == 4);
-      tc_host[2 * it] = rk.t;
-      tc_host[2 * it + 1] = (T)((stage == 1 || stage == 4 ? 1.0 : 2.0) * h / 6);
-    }
+  fill_tc(t0, h);
   SmallDeltaArgs<T> d{};
   d.a = small_args(*this, f, f, P, forward_primal ? 2 * n : 0, forward_primal ? -1 : 1);
   d.df = df; d.wst = Wst.as<T>(); d.slices = slices;

@@ -214,6 +214,72 @@ def test_lenseflow_ops(camb, prec, Ny, Nx, P, B, Bphi, n):
 
 
 @pytest.mark.parametrize("prec", ["f32", "f64"])
+@pytest.mark.parametrize("Ny,Nx,P,B,Bphi", [(64, 128, 2, 1, 1),      # K = 2, one slice per chain
+                                            (128, 64, 3, 1, 1),      # K = 3
+                                            (64, 64, 2, 2, 2),       # K = 2 over batch slots, each chain with its own phi slot (phi_off != 0)
+                                            (64, 64, 2, 4, 1)])      # K = 2, two slots per chain, one phi shared by all
+def test_fused_launch_chains_give_identical_results(camb, prec, Ny, Nx, P, B, Bphi):
+    """the launch chains of the fused power-of-two flows (Flow::groups; forced on at these small sizes with slice_streams_min_pix = 0, and the
+    one-launch small-map flows off) against one launch over all slices: the same kernels on the same data, bit for bit -- the column tile and the
+    row-group height follow the slices of the whole operation, not of a chain.  Non-square maps, so that an Nx / Ny or plane / mplane mix-up in a
+    chain's offsets cannot cancel.  Two wrong runs could agree with each other: the chained results are also held to the oracle."""
+    C = _pkg()
+    tT, nT = DT[prec]
+    n = 7
+    oproj, simf, simp = sims(camb, Ny, Nx, P, B)
+    f = simf(1).astype(nT).astype(np.float64)
+    gl = O.rfft2(simf(11).astype(nT).astype(np.float64))
+    phi = simp(2, Bphi).astype(nT).astype(np.float64)
+    delta = O.rfft2(simf(7)).astype(np.complex64 if prec == "f32" else np.complex128).astype(np.complex128)
+    OL = OLenseFlow(oproj, phi, n)
+    fe = OL.apply(f).astype(nT).astype(np.float64)
+    p = C.ProjLambert(Ny, Nx, 2.0, tT)
+    p.set_option("small_flow", 0)
+    p.set_option("slice_streams_min_pix", 0)
+    F = lambda a, b: C.Field(p, p.tensor(a), b)
+    res = {}
+    for K in (1, 4):
+        p.set_option("slice_streams", K)
+        L = C.LenseFlow(p, n)(F(phi, C.MAP))
+        dphi, df, _ = L.gradient(C.FLOW_FWD, F(fe, C.MAP), F(delta, C.FOURIER))
+        res[K] = [(L * F(f, C.MAP)).arr.clone(), L.ldiv(F(f, C.MAP)).arr.clone(), (L.adjoint * F(gl, C.FOURIER)).arr.clone(), dphi.arr.clone(), df.arr.clone()]
+    names = ("L*f", "L\\f", "L'g", "dphi", "df")
+    for name, a, b in zip(names, res[4], res[1]):
+        assert torch.equal(a, b), name
+    _, odf, odp = OL.grad_apply(fe, delta)
+    tol = TOL[prec]
+    for name, a, want, t in zip(names, res[4], (OL.apply(f), OL.inv(f), OL.adj(gl), odp, odf), (tol["flow"], tol["flow"], tol["adj"], tol["grad"], tol["adj"])):
+        close(name, a.cpu().numpy(), want, t)
+
+
+def test_fused_flow_launch_counts(camb):
+    """the launches of the three fused flows at 64 x 128 QU, n = 7, pinned per kernel class: one column and one row launch per RK stage (4 n = 28)
+    and the passes that open a flow.  One launch chain (slice_streams = 1: chains multiply every count).  The numbers were counted on MI355X with
+    the library of the commit BEFORE the stage driver and the launchers were shared, not with the code under test.  Only the classes of the flows
+    themselves: the conversions around them add layout / x_fft launches that are not the subject."""
+    C = _pkg()
+    Ny, Nx = 64, 128
+    _, simf, simp = sims(camb, Ny, Nx, 2, 1)
+    f, phi = simf(1).astype(np.float32), simp(2, 1).astype(np.float32)
+    delta = O.rfft2(simf(7).astype(np.float64)).astype(np.complex64)
+    p = C.ProjLambert(Ny, Nx, 2.0, torch.float32)
+    p.set_option("slice_streams", 1)
+    p.set_option("small_flow", 0)
+    L = C.LenseFlow(p, 7)(C.Field(p, p.tensor(phi), C.MAP))
+    ff, g = C.Field(p, p.tensor(f), C.MAP), C.Field(p, p.tensor(delta), C.FOURIER)
+    for what, op, want in (("L*f", lambda: L * ff, {"flow_y_fwd": 28, "x_grad": 28, "y_r2c": 1}),
+                           ("L'g", lambda: L.adjoint * g, {"adj_y": 28, "adj_x": 28}),
+                           ("gradient", lambda: L.gradient(C.FLOW_FWD, ff, g), {"delta_cols": 28, "delta_rows": 28, "x_grad": 1})):
+        p.prof_reset(); p.prof_enable(True)
+        op()
+        p.prof_enable(False)
+        tab = p.prof_table()
+        got = {k: tab.get(k, (0, 0))[1] for k in want}
+        print(what, {k: v[1] for k, v in tab.items()})
+        assert got == want, (what, got, want)
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
 @pytest.mark.parametrize("Ny,Nx,P,B,Bphi", [(128, 128, 1, 1, 1), (64, 128, 2, 1, 1), (128, 64, 3, 1, 1), (64, 64, 2, 2, 2), (64, 64, 2, 2, 1)])
 @pytest.mark.parametrize("mode", ["fwd", "inv"])
 @pytest.mark.parametrize("n", [7, 10])
