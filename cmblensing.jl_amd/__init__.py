@@ -19,5 +19,5 @@ from .drivers import (quadratic_estimate, MAP_joint, MAP_joint_step, hmc_step, s
 from . import rng                                                         # noqa: F401
 from .chainfile import load_chains, Chain, Chains                         # noqa: F401
 from .theta import (set_theta, logpdf_mixed_theta, logpdf_mixed_theta_grid, theta_ops_device, grid_and_sample, gibbs_sample_theta, findbin, bandpower_rescale,   # noqa: F401
-                    BinRescaledCov, use_bandpowers)
+                    BinRescaledCov, use_bandpowers, grad_theta_logpdf, grad_theta_logpdf_mixed)
 from .muse import CMBLensingMuseProblem                                   # noqa: F401

@@ -409,6 +409,22 @@ int cmbl_dataset_theta_ops(cmbl_dataset* ds, double r, double Aphi, const double
   });
 }
 
+int cmbl_grad_theta_logpdf(cmbl_dataset* ds, const void* f, const void* phi, int B, double r, double Aphi, const double* amps_host, int namps, int want,
+                           double* grad_host) {
+  return guard([&] {
+    NOTNULL(ds); NOTNULL(f); NOTNULL(phi); NOTNULL(grad_host); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1");
+    BY_DTYPE(ds->ctx, do_grad_theta, ds, f, phi, B, r, Aphi, amps_host, namps, want, grad_host);
+  });
+}
+int cmbl_grad_theta_logpdf_mixed(cmbl_dataset* ds, cmbl_flow* L, const void* fo, const void* phio, int B, double r, double Aphi, const double* amps_host,
+                                 int namps, int want, double* lp_host, double* grad_host) {
+  return guard([&] {
+    NOTNULL(ds); NOTNULL(L); NOTNULL(fo); NOTNULL(phio); NOTNULL(lp_host); NOTNULL(grad_host); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1");
+    SAME_CTX(ds, L);
+    BY_DTYPE(ds->ctx, do_grad_theta_mixed, ds, L, fo, phio, B, r, Aphi, amps_host, namps, want, lp_host, grad_host);
+  });
+}
+
 int cmbl_hmc_step(cmbl_dataset* ds, cmbl_flow* L, const void* fo, const void* phio, const void* mass, const void* white_p, const double* log_u_host,
                   const uint64_t* seeds_host, uint64_t step, int nleap, double eps, int always_accept, int alias_quirk, int B,
                   void* phio_out, double* dH_host, int* accept_host) {

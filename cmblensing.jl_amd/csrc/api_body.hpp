@@ -161,6 +161,28 @@ void do_lpm_theta(cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* 
 template <typename T> void do_theta_ops(cmbl_dataset* dsh, double r, double aphi, const double* amps, int namps, int which, void* out, double* sums) {
   typed<Dataset<T>>(dsh).theta_readback(r, aphi, amps, namps, which, (T*)out, sums);
 }
+template <typename T>
+void do_grad_theta(cmbl_dataset* dsh, const void* f, const void* phi, int B, double r, double aphi, const double* amps, int namps, int want, double* grad) {
+  Dataset<T>& ds = typed<Dataset<T>>(dsh);
+  Ctx<T>* c = ds.c;
+  const long n = ds.fsize(B);
+  ds.cvt.ensure(sizeof(cx<T>) * (n + B * c->plane()));
+  cx<T>* fF = ds.cvt.template as<cx<T>>(); cx<T>* pF = fF + n;
+  c->ref2F((const cx<T>*)f, fF, (long)ds.P * B);
+  c->ref2F((const cx<T>*)phi, pF, B);
+  ds.grad_theta_logpdf(fF, pF, B, r, aphi, amps, namps, want, grad);
+}
+template <typename T>
+void do_grad_theta_mixed(cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, int B, double r, double aphi, const double* amps, int namps, int want,
+                         double* lp, double* grad) {
+  Dataset<T>& ds = typed<Dataset<T>>(dsh); Flow<T>& L = typed<Flow<T>>(Lh);
+  Ctx<T>* c = ds.c;
+  const long pl = c->plane();
+  ds.cvt.ensure(sizeof(cx<T>) * 2 * B * pl);
+  cx<T>* pF = ds.cvt.template as<cx<T>>(); cx<T>* gF = pF + (long)B * pl;
+  c->ref2F((const cx<T>*)phio, pF, B);
+  ds.grad_theta_logpdf_mixed(L, (const T*)fo, pF, gF, B, r, aphi, amps, namps, want, lp, grad);
+}
 
 template <typename T> Drivers<T>& drivers_of(cmbl_dataset* dsh, cmbl_flow* Lh) {
   auto& p = dsh->drv[Lh->p.get()];

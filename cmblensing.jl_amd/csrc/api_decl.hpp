@@ -74,6 +74,8 @@ namespace cmbl {
   X(T, do_theta_model, (cmbl_dataset* dsh, const ThetaModelArgs& a)) \
   X(T, do_lpm_theta, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, int B, int ntheta, const double* r, const double* aphi, const double* amps, int namps, double* lp)) \
   X(T, do_theta_ops, (cmbl_dataset* dsh, double r, double aphi, const double* amps, int namps, int which, void* out, double* sums)) \
+  X(T, do_grad_theta, (cmbl_dataset* dsh, const void* f, const void* phi, int B, double r, double aphi, const double* amps, int namps, int want, double* grad)) \
+  X(T, do_grad_theta_mixed, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, int B, double r, double aphi, const double* amps, int namps, int want, double* lp, double* grad)) \
   X(T, do_hmc,(cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, const void* mass, const void* white_p, const double* log_u, const uint64_t* seeds, uint64_t step, int nleap, double eps, int always, int quirk, int B, void* phio_out, double* dH, int* accept)) \
   X(T, do_map_step, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* phi, const void* fstart, const void* hinv, double amax, double atol, double cg_tol, int cg_maxit, int quirk, int B, void* f_out, void* phi_out, double* logpdf, double* alpha, int* ncg, int* nls)) \
   X(T, do_qe, (cmbl_dataset* dsh, int which, const double* Cf, const double* Cft, const double* Cn, const double* TF, const double* Cphi, int wiener, const double* AL_in, void* phiqe_out, double* AL_out, int B)) \

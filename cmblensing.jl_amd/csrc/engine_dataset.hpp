@@ -363,6 +363,13 @@ struct Dataset : DatasetApi {
     read_logpdf(lp, B, 0);
   }
 
+  // d/dfhat = D' \ g_f lives in `w` only between the two delta flows.  grad_theta_logpdf_mixed asks for a copy (QU Fourier, F layout) by setting
+  // ghat_out for the duration of its call; nobody else pays for it
+  cx<T>* ghat_out = nullptr;
+  void keep_ghat(const cx<T>* w, long n) {
+    if (ghat_out) CMBL_HIP(hipMemcpyAsync(ghat_out, w, sizeof(cx<T>) * n, hipMemcpyDeviceToDevice, c->stream));
+  }
+
   // logpdf(Mixed(ds); f°, phi°) and optionally its gradient.  fo: map (reference layout == internal), phio: F layout S0.
   // gfo (map) / gphio (F) may be nullptr for value only.
   // Fused form (power-of-two maps).  Launches outside the four flows: phi prior (1), precompute (4), the y pass of f° (1), unmix + Cf^-1
@@ -406,6 +413,7 @@ struct Dataset : DatasetApi {
       ch.ch.push(opref(OP_D_INV, true));
       c->template x_pw<PP, true>(w, L.hbuf_ensure(sl), ch, B);
     });
+    keep_ghat(w, n);
     // pullback through fhat = L \ f° : delta flow t 0->1 from (fhat, w, 0); the epilogue forms d/dphi° = G' \ (dphi1 + dphi2 - Cphi^-1 phi)
     const DphiTail<T> tail{dphi1.template as<cx<T>>(), cpip, op(OP_G_INV).d[0]};
     L.flow_delta(fhat.template as<T>(), w, gphio_F, P, B, false, quirk, true, &L.A3, true, &tail);
@@ -436,6 +444,7 @@ struct Dataset : DatasetApi {
     c->harm(w, w, P, B, 0, nullptr, false, true, false);
     c->lincomb1((T*)w, (const T*)w, (const T*)cfif, 1.0, -1.0, 2 * n / B, B);
     apply(OP_D_INV, w, w, B, true, false, true);
+    keep_ghat(w, n);
     // pullback through fhat = L \ f° : delta flow t 0->1 from (fhat, w, 0)
     L.flow_delta(fhat.template as<T>(), w, dphi2.template as<cx<T>>(), P, B, false, quirk);
     // d/df° in f°'s basis (QU map)
@@ -458,6 +467,10 @@ struct Dataset : DatasetApi {
     DevBuf bidx;                             // int32, F layout: one bin-index plane per band
     DevBuf ops;                              // T, F layout: the scratch operator sets pinv(Cf) (np), pinv(D) (np), pinv(Cphi), pinv(G)
     DevBuf part, sums, amps;                 // partial sums [3][nblk], their totals [3], the amplitude vectors of a grid call
+    // the θ-gradient (k_theta_grad): each band's modes sorted by bin (int32), the chunks of those lists (ThChunk), per amplitude its first
+    // chunk (int32, namps + 1); per call the per-mode band terms, the partial sums of both stages, the result [nbatch][2 + namps], ĝ, ∇f°
+    DevBuf glist, gchunks, gampchunk, gcontrib, gpart, gcpart, gout, ghat, gfo;
+    int nchunks = 0;
   } th;
   T* th_op(int which) {
     T* o = th.ops.template as<T>(); const long pl = c->plane();
@@ -509,12 +522,33 @@ struct Dataset : DatasetApi {
     th.set = false;                            // a second install replaces the first; a failed one leaves none
     th.planes.ensure(sizeof(double) * h.size());
     CMBL_HIP(hipMemcpyAsync(th.planes.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream));
+    th.nchunks = 0;
     if (nbands) {
       std::vector<int32_t> hb((size_t)nbands * pl);
       th_toF(band_idx, hb.data(), nbands);
       th.bidx.ensure(sizeof(int32_t) * hb.size());
       CMBL_HIP(hipMemcpyAsync(th.bidx.p, hb.data(), sizeof(int32_t) * hb.size(), hipMemcpyHostToDevice, c->stream));
-      CMBL_HIP(hipStreamSynchronize(c->stream));   // hb goes away
+      // the per-bin sums of the θ-gradient: per band the modes that lie in a bin, sorted by (bin, mode), cut into chunks of at most TH_CHUNK
+      // entries that never straddle a bin; the chunks of one amplitude are consecutive (as ClBins orders its modes, kernels_cl.hpp)
+      std::vector<int32_t> list; std::vector<ThChunk> chunks; std::vector<int32_t> ampchunk;
+      for (int k = 0, off = 0; k < nbands; off += band_nbins[k], ++k) {
+        std::vector<std::vector<int32_t>> bins(band_nbins[k]);
+        for (long j = 0; j < pl; ++j) { const int32_t i = hb[(size_t)k * pl + j]; if (i < band_nbins[k]) bins[i].push_back((int32_t)j); }
+        for (int i = 0; i < band_nbins[k]; ++i) {
+          ampchunk.push_back((int32_t)chunks.size());
+          for (size_t s = 0; s < bins[i].size(); s += TH_CHUNK)
+            chunks.push_back(ThChunk{(int)(list.size() + s), (int)std::min<size_t>(TH_CHUNK, bins[i].size() - s), k, off + i});
+          list.insert(list.end(), bins[i].begin(), bins[i].end());
+        }
+      }
+      ampchunk.push_back((int32_t)chunks.size());
+      th.nchunks = (int)chunks.size();
+      th.glist.ensure(sizeof(int32_t) * std::max<size_t>(1, list.size())); th.gchunks.ensure(sizeof(ThChunk) * std::max<size_t>(1, chunks.size()));
+      th.gampchunk.ensure(sizeof(int32_t) * ampchunk.size());
+      if (!list.empty()) CMBL_HIP(hipMemcpyAsync(th.glist.p, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, c->stream));
+      if (!chunks.empty()) CMBL_HIP(hipMemcpyAsync(th.gchunks.p, chunks.data(), sizeof(ThChunk) * chunks.size(), hipMemcpyHostToDevice, c->stream));
+      CMBL_HIP(hipMemcpyAsync(th.gampchunk.p, ampchunk.data(), sizeof(int32_t) * ampchunk.size(), hipMemcpyHostToDevice, c->stream));
+      CMBL_HIP(hipStreamSynchronize(c->stream));   // hb and the lists go away
     }
     CMBL_HIP(hipStreamSynchronize(c->stream));     // ... and h
     th.ops.ensure(sizeof(T) * (2 * np + 2) * pl);
@@ -529,8 +563,7 @@ struct Dataset : DatasetApi {
   }
   // the operators of one θ into the scratch sets and the three sums into th.sums (device).  r / aphi NaN: not named.  amps_dev: this θ's
   // amplitude vectors on the device, or nullptr (ones)
-  void theta_eval(double r, double aphi, const double* amps_dev) {
-    CMBL_REQUIRE(th.set, ERR_STATE, "no θ model has been installed on this data set (cmbl_dataset_theta_model)");
+  ThetaDev theta_dev() const {
     const long pl = c->plane();
     const double* d = th.planes.template as<double>();
     ThetaDev m{};
@@ -538,10 +571,20 @@ struct Dataset : DatasetApi {
     m.cphi0 = d + 5 * th.np * pl; m.nphi = m.cphi0 + pl; m.g0inv = m.nphi + pl; m.guser = th.has_g ? m.g0inv + pl : nullptr;
     for (int k = 0; k < TH_MAXBANDS; ++k) { m.bidx[k] = k < th.nbands ? th.bidx.template as<int>() + (size_t)k * pl : nullptr; m.bmask[k] = th.bmask[k]; m.bnb[k] = th.bnb[k]; m.boff[k] = th.boff[k]; }
     m.nbands = th.nbands; m.np = th.np; m.Nx = c->Nx; m.Ny = c->Ny; m.Nyh = c->Nyh; m.pl = pl; m.s2len = th.s2len; m.aphi0 = th.aphi0;
+    return m;
+  }
+  ThetaPoint theta_point(double r, double aphi, const double* amps_dev) const {
     ThetaPoint t{};
     t.r_named = !std::isnan(r); t.s = (t.r_named ? r : th.r0) / th.r0;
     t.g_theta = !std::isnan(aphi) && !th.has_g; t.aphi = std::isnan(aphi) ? th.aphi0 : aphi;
     t.amps = amps_dev;
+    return t;
+  }
+  void theta_eval(double r, double aphi, const double* amps_dev) {
+    CMBL_REQUIRE(th.set, ERR_STATE, "no θ model has been installed on this data set (cmbl_dataset_theta_model)");
+    const long pl = c->plane();
+    const ThetaDev m = theta_dev();
+    const ThetaPoint t = theta_point(r, aphi, amps_dev);
     const int nblk = (int)std::min<long>(TH_MAXBLK, (pl + NTP - 1) / NTP);
     double* part = th.part.template as<double>();
     if (th.np == 5) CMBL_LAUNCH(c, K_PWFLAT, (k_theta_ops<T, true>), dim3((unsigned)nblk), 0, c->stream, m, t, th_op(OP_CF_INV), th_op(OP_D_INV), th_op(OP_CPHI_INV), th_op(OP_G_INV), part);
@@ -561,25 +604,31 @@ struct Dataset : DatasetApi {
     CMBL_HIP(hipStreamSynchronize(c->stream));     // the caller's array may go away
     return th.amps.template as<double>();
   }
+  // While one of these lives, the four θ-dependent operator sets of the data set point at the scratch sets; they and logdet_sum are put back
+  // on every way out
+  struct ThetaScratchOps {
+    static constexpr int ids[4] = {OP_CF_INV, OP_D_INV, OP_CPHI_INV, OP_G_INV};
+    struct Saved { int nplanes, kind; const T* d[5]; };
+    Dataset* ds; Saved s[4]; double logdet;
+    explicit ThetaScratchOps(Dataset* ds_) : ds(ds_), logdet(ds_->logdet_sum) {
+      const long pl = ds->c->plane();
+      for (int i = 0; i < 4; ++i) {
+        Op& o = ds->ops[ids[i]];
+        s[i].nplanes = o.nplanes; s[i].kind = o.kind; for (int k = 0; k < 5; ++k) s[i].d[k] = o.d[k];
+        const int n = i < 2 ? ds->th.np : 1;
+        o.nplanes = n; o.kind = n == 5 ? 2 : 1;
+        for (int k = 0; k < 5; ++k) o.d[k] = k < n ? ds->th_op(ids[i]) + (size_t)k * pl : nullptr;
+      }
+    }
+    ThetaScratchOps(const ThetaScratchOps&) = delete;
+    ~ThetaScratchOps() { for (int i = 0; i < 4; ++i) { Op& o = ds->ops[ids[i]]; o.nplanes = s[i].nplanes; o.kind = s[i].kind; for (int k = 0; k < 5; ++k) o.d[k] = s[i].d[k]; } ds->logdet_sum = logdet; }
+  };
   // lp[i * B + b] = logpdf(Mixed(ds); f°_b, phi°_b, θ_i) (src/dataset.jl:84-87).  The four θ-dependent operator sets and logdet_sum of the data set
   // point at the scratch sets while the grid runs and are put back on every way out.
   void logpdf_mixed_theta(Flow<T>& L, const T* fo, const cx<T>* phio_F, int B, int ntheta, const double* r, const double* aphi, const double* amps_host,
                           int namps, double* lp) {
     const double* ad = theta_amps(amps_host, namps, ntheta);
-    static constexpr int ids[4] = {OP_CF_INV, OP_D_INV, OP_CPHI_INV, OP_G_INV};
-    struct Saved { int nplanes, kind; const T* d[5]; };
-    struct Restore {
-      Dataset* ds; Saved s[4]; double logdet;
-      ~Restore() { for (int i = 0; i < 4; ++i) { Op& o = ds->ops[ids[i]]; o.nplanes = s[i].nplanes; o.kind = s[i].kind; for (int k = 0; k < 5; ++k) o.d[k] = s[i].d[k]; } ds->logdet_sum = logdet; }
-    } keep{this, {}, logdet_sum};
-    for (int i = 0; i < 4; ++i) { const Op& o = ops[ids[i]]; keep.s[i].nplanes = o.nplanes; keep.s[i].kind = o.kind; for (int k = 0; k < 5; ++k) keep.s[i].d[k] = o.d[k]; }
-    const long pl = c->plane();
-    for (int i = 0; i < 4; ++i) {
-      Op& o = ops[ids[i]];
-      const int n = i < 2 ? th.np : 1;
-      o.nplanes = n; o.kind = n == 5 ? 2 : 1;
-      for (int k = 0; k < 5; ++k) o.d[k] = k < n ? th_op(ids[i]) + (size_t)k * pl : nullptr;
-    }
+    const ThetaScratchOps keep(this);
     for (int i = 0; i < ntheta; ++i) {
       theta_eval(r[i], aphi[i], ad ? ad + (size_t)i * namps : nullptr);
       double s[3];
@@ -598,6 +647,71 @@ struct Dataset : DatasetApi {
     double s[3];
     theta_sums(s);
     if (sums_host) for (int k = 0; k < 3; ++k) sums_host[k] = s[k];
+  }
+
+  // ---- the θ-gradient (k_theta_grad): grad[b][2 + namps] = (d/dr, d/dAphi, d/d amplitudes in install order) per slot; what `want` leaves out is 0 ----
+  // a derivative is taken with respect to a parameter that θ names; the arguments are checked before anything is uploaded or enqueued
+  // (a model installed, then want / NaN / NULL, then the amplitude count in theta_amps)
+  const double* theta_grad_args(double r, double aphi, const double* amps_host, int namps, int want, int B) {
+    CMBL_REQUIRE(th.set, ERR_STATE, "no θ model has been installed on this data set (cmbl_dataset_theta_model)");
+    CMBL_REQUIRE(want > 0 && want < 8, ERR_ARG, "theta gradient: want is a non-empty mask of CMBL_THETA_R, CMBL_THETA_APHI, CMBL_THETA_AMPS");
+    CMBL_REQUIRE(!(want & TH_WANT_R) || !std::isnan(r), ERR_ARG, "theta gradient: the derivative with respect to r needs r named in θ (not NaN)");
+    CMBL_REQUIRE(!(want & TH_WANT_APHI) || !std::isnan(aphi), ERR_ARG, "theta gradient: the derivative with respect to Aphi needs Aphi named in θ (not NaN)");
+    CMBL_REQUIRE(!(want & TH_WANT_AMPS) || (amps_host && namps != 0), ERR_ARG, "theta gradient: the derivative with respect to the amplitudes needs amps_host (and a model with bands)");
+    CMBL_REQUIRE(B <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
+    return theta_amps(amps_host, namps, 1);
+  }
+  // grad_host is laid out with the CALLER's amplitude count: rows of 2 + th.namps doubles when the amplitudes were given, of 2 when they were
+  // not (amps_dev == nullptr: a θ that names no band, whatever the model holds)
+  template <bool MIXED> void theta_grad_run(const ThetaFields<T>& fl, double r, double aphi, const double* amps_dev, int want, int B, double* grad_host) {
+    const long pl = c->plane();
+    const int nblk = (int)std::min<long>(TH_MAXBLK, (pl + NTP - 1) / NTP), nout = 2 + (amps_dev ? th.namps : 0);
+    th.gpart.ensure(sizeof(double) * 2 * TH_MAXBLK * MAXBATCH); th.gout.ensure(sizeof(double) * (2 + th.namps) * MAXBATCH);
+    if (want & TH_WANT_AMPS) {
+      th.gcontrib.ensure(sizeof(double) * (size_t)B * th.nbands * pl);
+      th.gcpart.ensure(sizeof(double) * (size_t)B * std::max(1, th.nchunks));
+    }
+    const ThetaDev m = theta_dev();
+    const ThetaPoint t = theta_point(r, aphi, amps_dev);
+    double *part = th.gpart.template as<double>(), *contrib = th.gcontrib.template as<double>(), *cpart = th.gcpart.template as<double>();
+    const dim3 grid((unsigned)nblk, (unsigned)B);
+    if (th.np == 5) CMBL_LAUNCH(c, K_PWFLAT, (k_theta_grad<T, true, MIXED>), grid, 0, c->stream, m, t, fl, want, th.r0, part, contrib);
+    else CMBL_LAUNCH(c, K_PWFLAT, (k_theta_grad<T, false, MIXED>), grid, 0, c->stream, m, t, fl, want, th.r0, part, contrib);
+    if ((want & TH_WANT_AMPS) && th.nchunks > 0)
+      CMBL_LAUNCH(c, K_REDUCE, k_theta_bins, dim3((unsigned)th.nchunks, (unsigned)B), 0, c->stream, th.gchunks.template as<ThChunk>(), th.glist.template as<int>(),
+                  (const double*)contrib, th.nbands, pl, cpart);
+    CMBL_LAUNCH(c, K_REDUCE, k_theta_grad_sum, dim3((unsigned)nout, (unsigned)B), 0, c->stream, (const double*)part, nblk, (const double*)cpart, th.nchunks,
+                th.gampchunk.template as<int>(), want, th.gout.template as<double>());
+    CMBL_HIP(hipMemcpyAsync(grad_host, th.gout.p, sizeof(double) * (size_t)nout * B, hipMemcpyDeviceToHost, c->stream));
+    CMBL_HIP(hipStreamSynchronize(c->stream));
+  }
+  // ∇θ logpdf(ds; f, phi, θ) at fixed fields: f harmonic, phi Fourier with one plane per slot, both F layout.  No lensing operator, no data term
+  void grad_theta_logpdf(const cx<T>* f_h, const cx<T>* phi_F, int B, double r, double aphi, const double* amps_host, int namps, int want, double* grad_host) {
+    const double* ad = theta_grad_args(r, aphi, amps_host, namps, want, B);
+    theta_grad_run<false>(ThetaFields<T>{f_h, phi_F, nullptr, nullptr, nullptr}, r, aphi, ad, want, B, grad_host);
+  }
+  // logpdf(Mixed(ds); f°, phi°, θ) and its θ-gradient at one θ: the operators of θ go to the scratch sets (as in logpdf_mixed_theta), the
+  // library's own gradient of logpdf(Mixed) runs on them -- leaving f in fh, phi in phiF, d/dphi° in gphio_F and, through ghat_out, a copy
+  // of d/dfhat -- and one pass forms the explicit, the cross and the log-determinant terms from them
+  void grad_theta_logpdf_mixed(Flow<T>& L, const T* fo, const cx<T>* phio_F, cx<T>* gphio_F, int B, double r, double aphi, const double* amps_host,
+                               int namps, int want, double* lp, double* grad_host) {
+    const double* ad = theta_grad_args(r, aphi, amps_host, namps, want, B);
+    const long n = fsize(B);
+    th.ghat.ensure(sizeof(cx<T>) * n); th.gfo.ensure(sizeof(T) * (long)P * B * c->npix());
+    double s[3];
+    {
+      const ThetaScratchOps keep(this);
+      struct Unhook { Dataset* ds; ~Unhook() { ds->ghat_out = nullptr; } } unhook{this};
+      theta_eval(r, aphi, ad);
+      theta_sums(s);
+      logdet_sum = s[0] + th.logdet_cn;
+      ghat_out = th.ghat.template as<cx<T>>();
+      logpdf_mixed(L, fo, phio_F, lp, th.gfo.template as<T>(), gphio_F, B, false);
+    }
+    for (int b = 0; b < B; ++b) lp[b] -= s[1] + s[2];
+    cx<T>* gh = th.ghat.template as<cx<T>>();
+    c->harm(gh, gh, P, B, 0, nullptr, false, true, false);                  // QU Fourier -> harmonic
+    theta_grad_run<true>(ThetaFields<T>{fh.template as<cx<T>>(), phiF.template as<cx<T>>(), gh, phio_F, gphio_F}, r, aphi, ad, want, B, grad_host);
   }
 };
 

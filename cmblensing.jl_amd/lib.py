@@ -67,6 +67,8 @@ SIGNATURES = {
     "cmbl_dataset_theta_model": [_vp, _pd, _ci, _pd, _ci, _pci, _vp, _pci, _pd, _pd, _cd, _cd, _pd, _cd, _pd, _pd, _cd],
     "cmbl_logpdf_mixed_theta": [_vp, _vp, _vp, _vp, _ci, _ci, _pd, _pd, _pd, _ci, _pd],
     "cmbl_dataset_theta_ops": [_vp, _cd, _cd, _pd, _ci, _ci, _vp, _pd],
+    "cmbl_grad_theta_logpdf": [_vp, _vp, _vp, _ci, _cd, _cd, _pd, _ci, _ci, _pd],
+    "cmbl_grad_theta_logpdf_mixed": [_vp, _vp, _vp, _vp, _ci, _cd, _cd, _pd, _ci, _ci, _pd, _pd],
     "cmbl_hmc_step": [_vp, _vp, _vp, _vp, _vp, _vp, _pd, _pu64, _u64, _ci, _cd, _ci, _ci, _ci, _vp, _pd, _pci],
     "cmbl_quadratic_estimate": [_vp, _ci, _pd, _pd, _pd, _pd, _pd, _ci, _pd, _vp, _pd, _ci],
     "cmbl_map_joint_step": [_vp, _vp, _vp, _vp, _vp, _cd, _cd, _cd, _ci, _ci, _ci, _vp, _vp, _pd, _pd, _pci, _pci],

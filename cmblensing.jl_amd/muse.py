@@ -6,7 +6,8 @@ mirrors, method for method:
 
     logLike(d, z, θ)        = logpdf(ds; z..., θ, d)                         (:44-46)
     ∇θ_logLike(d, z, θ)     = gradient of the above w.r.t. θ                   (:51-53; ForwardDiff over θ in the reference -- third-party
-                              AD, unpinned; here central differences of the device logpdf, step `fd_step` relative)
+                              AD, unpinned; here central differences of the device logpdf, step `fd_step` relative, or with
+                              grad="device" the exact derivative from one theta.grad_theta_logpdf call)
     sample_x_z(rng, θ)      = simulate(rng, ds_for_sims; θ) -> (x = d, z = (f, ϕ)) (:55-65)
     ẑ_at_θ(d, zguess, θ)    = MAP_joint(θ, ds with d, ϕ start; fstart)          (:67-72)
 θ is a dict over the dataset's parameters (r, Aϕ, bandpower amplitude vectors: theta.py); `θ_fixed` entries are merged in (:30).
@@ -19,7 +20,10 @@ from . import theta as TH
 
 
 class CMBLensingMuseProblem:
-    def __init__(self, ds, theta_fixed=None, MAP_joint_kwargs=None, base_seed=0, fd_step=1e-3):
+    def __init__(self, ds, theta_fixed=None, MAP_joint_kwargs=None, base_seed=0, fd_step=1e-3, grad="fd"):
+        if grad not in ("fd", "device"):
+            raise ValueError(f'grad must be "fd" or "device", got {grad!r}')
+        self.grad = grad
         self.ds, self.theta_fixed = ds, dict(theta_fixed or {})
         self.MAP_joint_kwargs = {"nsteps": 5, **(MAP_joint_kwargs or {})}
         self.base_seed, self.fd_step = int(base_seed), float(fd_step)
@@ -40,8 +44,14 @@ class CMBLensingMuseProblem:
         return self.ds.logpdf(z["f"], z["phi"], d=d)
 
     def grad_theta_logLike(self, d, z, theta):
-        """∂ logLike / ∂θ, same structure as θ; central differences with a relative step"""
+        """∂ logLike / ∂θ, same structure as θ, summed over the batch slots.  grad="fd": central differences with a relative step;
+        grad="device": the exact derivative from one `theta.grad_theta_logpdf` call (the data term does not depend on θ, so `d` plays no part;
+        the data set is not moved)"""
         th = self.standardize_theta(theta)
+        if self.grad == "device":
+            at = {k: (float(v) if np.ndim(v) == 0 else v) for k, v in self.merge(th).items()}
+            g = TH.grad_theta_logpdf(self.ds, z["f"], z["phi"], at)
+            return {k: np.asarray(g[k].sum(axis=0)).reshape(v.shape) for k, v in th.items()}
         out = {}
         for k, v in th.items():
             g = np.zeros(v.shape)

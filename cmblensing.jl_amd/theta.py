@@ -17,7 +17,7 @@ import ctypes
 import numpy as np
 import torch
 
-from .engine import LenseFlow, MAP, FOURIER, _ptr
+from .engine import LenseFlow, MAP, FOURIER, HARMONIC, _ptr
 from .lib import check
 from .sim import HarmOp, _pinv
 
@@ -201,6 +201,72 @@ def logpdf_mixed_theta_grid(ds, fo, po, thetas):
     ds.L.invalidate()
     check(ds.lib.cmbl_logpdf_mixed_theta(ds._h, ds.L._h, _ptr(fo.arr), _ptr(po.arr), B, n, _dp(r), _dp(A), _dp(amps), 0 if amps is None else amps.shape[1], _dp(lp)))
     return lp
+
+
+WANT_R, WANT_APHI, WANT_AMPS = 1, 2, 4          # CMBL_THETA_R, _APHI, _AMPS
+
+
+def _theta_grad_call(ds, theta, B):
+    """what the two θ-gradient calls share: the model, the row of θ, the `want` mask of the parameters θ names and the output array"""
+    _install_theta_model(ds)
+    theta = {k: v for k, v in dict(theta).items() if v is not None}
+    r, A, amps = _theta_rows(ds, [theta])
+    want = (WANT_R if "r" in theta else 0) | (WANT_APHI if "Aphi" in theta else 0) | (WANT_AMPS if amps is not None else 0)
+    if not want:
+        raise ValueError("the θ-gradient needs a θ that names at least one parameter")
+    namps = 0 if amps is None else amps.shape[1]
+    return theta, float(r[0]), float(A[0]), amps, namps, want, np.zeros((B, 2 + namps), dtype=np.float64)
+
+
+def _theta_grad_dict(ds, theta, grad):
+    """rows of [d/dr, d/dAϕ, bands concatenated in install order] -> {name: (B,) or (B, nbins)} for the parameters θ names"""
+    out = {}
+    if "r" in theta:
+        out["r"] = grad[:, 0].copy()
+    if "Aphi" in theta:
+        out["Aphi"] = grad[:, 1].copy()
+    cb, off = ds.host.get("Cfs_bands"), 2
+    for name in (cb.names if cb is not None else []):
+        nb = cb.bands[name][2]
+        if name in theta:
+            out[name] = grad[:, off:off + nb].copy()
+        off += nb
+    return out
+
+
+def grad_theta_logpdf(ds, f, phi, theta):
+    """∂/∂θ logpdf(ds; f, ϕ, θ) at fixed fields, per batch slot: {name: (B,) for r and Aϕ, (B, nbins) for a bandpower amplitude vector}, for
+    the parameters `theta` (a dict as `set_theta` takes it) names -- what the reference gets by automatic differentiation for MUSE's
+    ∇θ_logLike (ext/CMBLensingMuseInferenceExt.jl:52-54).  One library call (cmbl_grad_theta_logpdf): a kernel differentiates the formulas of
+    the θ operators in forward mode; no lensing operator is involved, the data term does not depend on θ.  The model is installed as
+    `logpdf_mixed_theta_grid` does; `ds.ops`, `ds.host`, `ds.theta`, `ds.logdet_sum` and `ds.logdet_mix` are not touched."""
+    f, phi = f.to(HARMONIC), phi.to(FOURIER)
+    B = f.arr.shape[0]
+    if phi.arr.shape[0] != B:
+        if phi.arr.shape[0] != 1:
+            raise ValueError(f"grad_theta_logpdf: {phi.arr.shape[0]} planes of ϕ for {B} slots of f")
+        phi = type(phi)(phi.proj, phi.arr.expand(B, *phi.arr.shape[1:]).contiguous(), FOURIER)
+    theta, r, A, amps, namps, want, grad = _theta_grad_call(ds, theta, B)
+    fa, pa = f.arr.contiguous(), phi.arr.contiguous()
+    check(ds.lib.cmbl_grad_theta_logpdf(ds._h, _ptr(fa), _ptr(pa), B, r, A, _dp(amps), namps, want, _dp(grad)))
+    return _theta_grad_dict(ds, theta, grad)
+
+
+def grad_theta_logpdf_mixed(ds, fo, po, theta):
+    """(logpdf(Mixed(ds); f°, ϕ°, θ) (B,), its θ-gradient {name: (B,) or (B, nbins)}) at one θ, in ONE library call
+    (cmbl_grad_theta_logpdf_mixed): the operators of θ are made on the device as in `logpdf_mixed_theta_grid`, the library's gradient of
+    logpdf(Mixed) runs on them, and one more pass forms, next to the explicit derivative, −⟨ĝ, ∂D/∂r f⟩ − ∂logdet(D₀⁻¹D)/∂r for r and
+    −⟨gϕ°, ∂lnG/∂Aϕ ϕ°⟩ − ∂logdet G/∂Aϕ for Aϕ.  Those two terms are 10³–10⁴ times the result and nearly cancel: the result is as accurate as
+    they are.  The value is bit for bit the grid's at that θ.  The data set stays at the θ it had."""
+    if not isinstance(ds.L, LenseFlow):
+        raise ValueError(f"grad_theta_logpdf_mixed: the library's gradient of logpdf(Mixed) is defined for a LenseFlow in ds.L, not {type(ds.L).__name__}")
+    fo, po = fo.to(MAP), po.to(FOURIER)
+    B = fo.arr.shape[0]
+    theta, r, A, amps, namps, want, grad = _theta_grad_call(ds, theta, B)
+    lp = np.empty(B, dtype=np.float64)
+    ds.L.invalidate()
+    check(ds.lib.cmbl_grad_theta_logpdf_mixed(ds._h, ds.L._h, _ptr(fo.arr), _ptr(po.arr), B, r, A, _dp(amps), namps, want, _dp(lp), _dp(grad)))
+    return lp, _theta_grad_dict(ds, theta, grad)
 
 
 def theta_ops_device(ds, which, r=None, Aphi=None, **bands):

@@ -598,6 +598,40 @@ int cmbl_logpdf_mixed_theta(cmbl_dataset* ds, cmbl_flow* L, const void* fo, cons
                             const double* Aphi_host, const double* amps_host, int namps, double* lp_host);
 int cmbl_dataset_theta_ops(cmbl_dataset* ds, double r, double Aphi, const double* amps_host, int namps, int which, void* out_dev, double* sums_host);
 
+/* ---- the θ-gradient on the device: what ∇θ_logLike of the MUSE adapter (ext/CMBLensingMuseInferenceExt.jl:52-54) gets by automatic differentiation of
+ *      logpdf(ds; z..., θ, d), and the same for logpdf(Mixed(ds); f°, phi°, θ).  θ, the model and the NaN / NULL conventions are those of
+ *      cmbl_logpdf_mixed_theta; a cmbl_dataset_theta_model must have been installed (else CMBL_ERR_STATE).  One pointwise pass per batch slot evaluates the
+ *      very formulas of the operator kernel on a value with tangents (forward mode: r, Aphi and one amplitude per band, since a mode lies in one bin per
+ *      band), so the derivative is that of the operators as defined: pinv keeps its discontinuity (tangent 0 where the value is replaced by 0), a skipped
+ *      log term contributes 0.  The fields are read once in the context's precision, all sums are double, in two stages and a fixed order; the per-bin
+ *      sums run over per-band mode lists sorted by bin at install, cut into chunks that never straddle a bin -- no atomics: equal calls give bit-identical
+ *      output and a slot's numbers do not depend on the other slots.  The data term does not depend on θ: Cn, the mask and the beam play no part.
+ *   grad_host: nbatch rows of 2 + namps doubles, with the namps of THIS call (rows of 2 when amps_host is NULL, whatever bands the model holds):
+ *      d/dr, d/dAphi, then the amplitudes of the bands concatenated in install order.  want: a mask of
+ *      CMBL_THETA_R, CMBL_THETA_APHI, CMBL_THETA_AMPS; what it leaves out is not computed and written as 0.  The derivative with respect to a parameter that
+ *      θ does not name (r or Aphi NaN, amps_host NULL), or an empty mask, is CMBL_ERR_ARG; another namps than the model's Σ nbins (0 with amps_host NULL) is
+ *      CMBL_ERR_SHAPE.  Only scalars cross to the host; nothing is allocated after the first call.  Both calls synchronise.
+ *   cmbl_grad_theta_logpdf: ∂/∂θ logpdf(ds; f, phi, θ) at fixed fields.  f: HARMONIC (Ny/2+1, Nx, npol, nbatch), phi: FOURIER, one plane per slot.
+ *        ∂/∂θ_k = ½ Σ λ [u† (∂Cf/∂θ_k) u / (Ny Nx) − tr(pinv(Cf) ∂Cf/∂θ_k)],  u = pinv(Cf) f,  plus the same with (phi, Cphi) for Aphi.
+ *      No lensing operator is involved and the data set's operators are not read.
+ *   cmbl_grad_theta_logpdf_mixed: lp_host[b] = logpdf(Mixed(ds); f°_b, phi°_b, θ) (bit for bit what cmbl_logpdf_mixed_theta gives at that θ) and its
+ *      θ-gradient; fo, phio as for cmbl_grad_logpdf_mixed, L a LenseFlow.  The operators of θ go to the scratch sets as in cmbl_logpdf_mixed_theta,
+ *      cmbl_grad_logpdf_mixed's own code runs on them (whichever path the context takes, alias_quirk off: the true gradient), and with f = D \ (L \ f°),
+ *      phi = G \ phi°, ĝ = ∂lp/∂(L \ f°) (copied device-to-device between the two delta flows, only in this call) and gphi° = ∂lp/∂phi°:
+ *        d/dr = ∂lp/∂r − ⟨ĝ, (∂D/∂r) f⟩ − ∂/∂r logdet(D(r0)⁻¹ D),   d/dAphi = ∂lp/∂Aphi − ⟨gphi°, (∂lnG/∂Aphi) phi°⟩ − ∂/∂Aphi logdet G   (the last two
+ *        vanish with a fixed G),   d/dA = ∂lp/∂A (the amplitudes enter neither D nor G).
+ *      For r and Aphi the last two terms are 10³–10⁴ times the result and nearly cancel: the accuracy of the result is that of the terms.
+ *      gphi° is the library's, i.e. the RK4 delta flow -- the transpose of the continuous flow, not the derivative of the discrete forward flow; the
+ *      two meet as nsteps⁻⁴.  d/dAphi is therefore not exactly the derivative of the lp_host returned with it: with 7 steps the two differ by about
+ *      1e-8 of the size of the terms (8e-6 on a result of 1.0 at 32 x 32 QU), as differences of cmbl_logpdf_mixed_theta show; r, the amplitudes and
+ *      cmbl_grad_theta_logpdf do not involve gphi° and carry no such term.
+ *      The data set is put back as it was on every way out, an error included.  L's phi is overwritten. */
+enum { CMBL_THETA_R = 1, CMBL_THETA_APHI = 2, CMBL_THETA_AMPS = 4 };
+int cmbl_grad_theta_logpdf(cmbl_dataset* ds, const void* f, const void* phi, int nbatch, double r, double Aphi, const double* amps_host, int namps,
+                           int want, double* grad_host);
+int cmbl_grad_theta_logpdf_mixed(cmbl_dataset* ds, cmbl_flow* L, const void* fo, const void* phio, int nbatch, double r, double Aphi,
+                                 const double* amps_host, int namps, int want, double* lp_host, double* grad_host);
+
 /* ---- loop bodies of the reference's drivers, for hosts that are neither Julia (which keeps src/maximization.jl:116-233 and
  *      src/sampling.jl:388-464 itself on top of the entry points above) nor Python (cmblensing.jl_amd/drivers.py).  Control flow on the
  *      host inside the library, every field operation one of the launches above; both return when their host outputs are final.

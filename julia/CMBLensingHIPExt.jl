@@ -521,6 +521,33 @@ function hip_theta_ops!(out, hd::HIPDataSet, which::Integer, r::Float64, Aϕ::Fl
               hd.h, r, Aϕ, isnothing(amps) ? C_NULL : amps, isnothing(amps) ? 0 : length(amps), which, devptr(out), sums))
     sums
 end
+# the θ-gradient at one θ (∇θ_logLike of ext/CMBLensingMuseInferenceExt.jl:52-54 without automatic differentiation).  r, Aϕ: NaN = "not named in θ";
+# amps: the amplitude vectors concatenated, or nothing; want: a mask of 1 (r), 2 (Aϕ), 4 (amplitudes).  -> (2 + length(amps), nbatch) matrix with rows
+# d/dr, d/dAϕ, d/d amplitudes; what `want` leaves out is 0
+function hip_grad_theta_logpdf(hd::HIPDataSet, f::Field, ϕ::Field, r::Float64, Aϕ::Float64, amps::Union{Nothing,Vector{Float64}}=nothing;
+                               want::Integer=(isnan(r) ? 0 : 1) | (isnan(Aϕ) ? 0 : 2) | (isnothing(amps) ? 0 : 4))
+    fh, ϕl = harm(f), Fourier(ϕ)
+    B, na = nbatch(fh), isnothing(amps) ? 0 : length(amps)
+    g = Matrix{Cdouble}(undef, 2 + na, B)
+    a, b = fh.arr, ϕl.arr
+    GC.@preserve a b g amps chk(ccall((:cmbl_grad_theta_logpdf, lib), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}),
+              hd.h, devptr(a), devptr(b), B, r, Aϕ, isnothing(amps) ? C_NULL : amps, na, want, g))
+    g
+end
+# -> (logpdf(Mixed(ds); f°, ϕ°, θ) per slot, the same matrix for its θ-gradient)
+function hip_grad_theta_logpdf_mixed(hd::HIPDataSet, f°::Field, ϕ°::Field, r::Float64, Aϕ::Float64, amps::Union{Nothing,Vector{Float64}}=nothing;
+                                     want::Integer=(isnan(r) ? 0 : 1) | (isnan(Aϕ) ? 0 : 2) | (isnothing(amps) ? 0 : 4))
+    fo, po = Ł(f°), Fourier(ϕ°)
+    B, na = nbatch(fo), isnothing(amps) ? 0 : length(amps)
+    lp, g = Vector{Cdouble}(undef, B), Matrix{Cdouble}(undef, 2 + na, B)
+    a, b = fo.arr, po.arr
+    GC.@preserve a b lp g amps chk(ccall((:cmbl_grad_theta_logpdf_mixed, lib), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+              hd.h, hd.L.h, devptr(a), devptr(b), B, r, Aϕ, isnothing(amps) ? C_NULL : amps, na, want, lp, g))
+    hd.L.cached = nothing
+    lp, g
+end
 
 # ---- reductions and random fields (optional: the generic Julia broadcasts on ROCArrays work too) ------------------------------
 # restricted to device-backed flat-sky fields: CPU fields and other projections keep the reference's own `dot`
