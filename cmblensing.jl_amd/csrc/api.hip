@@ -340,6 +340,15 @@ int cmbl_wiener_cg(cmbl_dataset* ds, cmbl_flow* L, const void* d, const void* fs
 int cmbl_lensop_from_lenseflow(cmbl_flow* L, cmbl_lensop** out) { return lensop_view(L, LENSOP_FLOW, out); }
 int cmbl_lensop_from_bilinear(cmbl_bilinear* L, cmbl_lensop** out) { return lensop_view(L, LENSOP_BILINEAR, out); }
 int cmbl_lensop_from_powerlens(cmbl_powerlens* L, cmbl_lensop** out) { return lensop_view(L, LENSOP_POWERLENS, out); }
+int cmbl_lensop_identity(cmbl_ctx* ctx, cmbl_lensop** out) {
+  return guard([&] {
+    NOTNULL(ctx); NOTNULL(out);
+    auto h = std::make_unique<cmbl_lensop>();
+    h->ctx = ctx; h->kind = LENSOP_IDENTITY; h->h = nullptr;
+    BY_DTYPE(ctx, do_lensop_identity, h.get());
+    *out = h.release();
+  });
+}
 int cmbl_lensop_destroy(cmbl_lensop* op) { return guard([&] { delete op; }); }
 
 int cmbl_gradientf_logpdf_op(cmbl_dataset* ds, cmbl_lensop* L, const void* f, const void* d, int zero_d, void* out, int B) {
@@ -364,6 +373,13 @@ int cmbl_grad_logpdf_op(cmbl_dataset* ds, cmbl_lensop* L, const void* f, const v
     NOTNULL(ds); NOTNULL(L); NOTNULL(f); NOTNULL(phi); NOTNULL(lp); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1");
     SAME_CTX_OP(ds, L);
     BY_DTYPE(ds->ctx, do_grad_lp_op, ds, L, f, phi, d, lp, gf, gphi, B, quirk);
+  });
+}
+
+int cmbl_nolensing_logpdf(cmbl_dataset* ds, const void* f, const void* d, double* lp_host, void* gf_out, int B) {
+  return guard([&] {
+    NOTNULL(ds); NOTNULL(f); NOTNULL(lp_host); CMBL_REQUIRE(B >= 1, ERR_SHAPE, "nbatch >= 1");
+    BY_DTYPE(ds->ctx, do_nolens_logpdf, ds, f, d, lp_host, gf_out, B);
   });
 }
 

@@ -62,6 +62,7 @@ template <typename T> void do_logdet(cmbl_ctx* ctx, const void* d, int nplanes, 
 template <typename T> LensOps<T>& lensop_of(cmbl_lensop* v) {
   if (v->kind == LENSOP_FLOW) return typed<Flow<T>>(static_cast<cmbl_flow*>(v->h));
   if (v->kind == LENSOP_BILINEAR) return typed<Bilinear<T>>(static_cast<cmbl_bilinear*>(v->h));
+  if (v->kind == LENSOP_IDENTITY) return *static_cast<NoLens<T>*>(v->h);
   return typed<PowerLens<T>>(static_cast<cmbl_powerlens*>(v->h));
 }
 // the data of a call in the F layout: `d` (reference layout, converted into dF) or, d == NULL, what the data set holds
@@ -128,6 +129,23 @@ void do_grad_lp_op(cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void
   ds.grad_logpdf(L, fF, pF, dd, lp, gf ? gF : nullptr, gphi ? gpF : nullptr, B, quirk != 0);
   if (gf) c->F2ref(gF, (cx<T>*)gf, (long)ds.P * B);
   if (gphi) c->F2ref(gpF, (cx<T>*)gphi, B);
+  CMBL_HIP(hipStreamSynchronize(c->stream));
+}
+// the identity for the L slot (cmbl_lensop_identity): the view owns its NoLens<T>
+template <typename T> void do_lensop_identity(cmbl_lensop* h) {
+  h->own = std::make_shared<NoLens<T>>(C<T>(h->ctx));
+  h->h = h->own.get();
+}
+template <typename T>
+void do_nolens_logpdf(cmbl_dataset* dsh, const void* f, const void* d, double* lp, void* gf, int B) {
+  Dataset<T>& ds = typed<Dataset<T>>(dsh);
+  Ctx<T>* c = ds.c;
+  const long n = ds.fsize(B);
+  ds.cvt.ensure(sizeof(cx<T>) * 3 * n);
+  cx<T>* fF = ds.cvt.template as<cx<T>>(); cx<T>* dF = fF + n; cx<T>* gF = dF + n;
+  c->ref2F((const cx<T>*)f, fF, (long)ds.P * B);
+  ds.nolens_logpdf(fF, data_of(ds, d, dF, B), lp, gf ? gF : nullptr, B);
+  if (gf) c->F2ref(gF, (cx<T>*)gf, (long)ds.P * B);
   CMBL_HIP(hipStreamSynchronize(c->stream));
 }
 template <typename T>

@@ -38,8 +38,10 @@ struct cmbl_clbins { std::unique_ptr<cmbl::ClBins> p; };
 struct cmbl_flow { cmbl_ctx* ctx; std::unique_ptr<cmbl::FlowApi> p; };
 struct cmbl_bilinear { cmbl_ctx* ctx; std::unique_ptr<cmbl::BilinearApi> p; };
 struct cmbl_powerlens { cmbl_ctx* ctx; std::unique_ptr<cmbl::PowerLensApi> p; };
-enum { LENSOP_FLOW = 0, LENSOP_BILINEAR = 1, LENSOP_POWERLENS = 2 };
-struct cmbl_lensop { cmbl_ctx* ctx; int kind; void* h; };                    // non-owning view: h is the cmbl_flow / cmbl_bilinear / cmbl_powerlens of `kind`
+enum { LENSOP_FLOW = 0, LENSOP_BILINEAR = 1, LENSOP_POWERLENS = 2, LENSOP_IDENTITY = 3 };
+// non-owning view: h is the cmbl_flow / cmbl_bilinear / cmbl_powerlens of `kind`.  LENSOP_IDENTITY has no handle behind it: h is the NoLens<T> that
+// `own` keeps alive (made by do_lensop_identity, deleter and all)
+struct cmbl_lensop { cmbl_ctx* ctx; int kind; void* h; std::shared_ptr<void> own; };
 struct cmbl_projector { cmbl_ctx* ctx; std::unique_ptr<cmbl::ProjectorApi> p; };
 struct cmbl_eqds { cmbl_ctx* ctx; std::unique_ptr<cmbl::EqDatasetApi> p; };
 struct cmbl_dataset {
@@ -70,6 +72,8 @@ namespace cmbl {
   X(T, do_gradf_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void* d, int zero_d, void* out, int B)) \
   X(T, do_cg_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* d, const void* fstart, double tol, int maxit, void* f_out, double* hist, int* nit, int B)) \
   X(T, do_grad_lp_op, (cmbl_dataset* dsh, cmbl_lensop* Lh, const void* f, const void* phi, const void* d, double* lp, void* gf, void* gphi, int B, int quirk)) \
+  X(T, do_lensop_identity, (cmbl_lensop* h)) \
+  X(T, do_nolens_logpdf, (cmbl_dataset* dsh, const void* f, const void* d, double* lp, void* gf, int B)) \
   X(T, do_lpm, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, double* lp, void* gfo, void* gphio, int B, int quirk)) \
   X(T, do_theta_model, (cmbl_dataset* dsh, const ThetaModelArgs& a)) \
   X(T, do_lpm_theta, (cmbl_dataset* dsh, cmbl_flow* Lh, const void* fo, const void* phio, int B, int ntheta, const double* r, const double* aphi, const double* amps, int namps, double* lp)) \

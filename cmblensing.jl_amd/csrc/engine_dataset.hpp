@@ -3,6 +3,7 @@
 #pragma once
 #include "engine.hpp"
 #include "engine_cg.hpp"
+#include "engine_nolens.hpp"
 #include "kernels_theta.hpp"
 
 namespace cmbl {
@@ -218,6 +219,7 @@ struct Dataset : DatasetApi {
     t2.ensure(sizeof(cx<T>) * n);
     cx<T>* r = t2.template as<cx<T>>();
     Flow<T>* flow = fused() ? L.as_flow() : nullptr;
+    if (f_h && fused() && L.as_identity()) { nolens_adjoint(f_h, dd, B, out, B); return; }   // L = I: the flow-free form, Cf^-1 f included
     if (f_h && flow) {
       model_adjoint(*flow, f_h, dd, B, r, B);
     } else {
@@ -300,8 +302,105 @@ struct Dataset : DatasetApi {
     }
     return cg.finish(v, f_out, hist, st.done, 6, 4, 5);
   }
+  // ---- the no-lensing model d = M B f + n (NoLensingDataSet, src/dataset.jl:37-47, 68-73; L = I in the slot) -------------------------------
+  // out = A f [+ B'M'Cn^-1 d] = B'M'Cn^-1 (d - M B f) - Cf^-1 f  (harmonic F; dd == nullptr: d = 0; out must not alias f_h), the fused form of
+  // gradientf_logpdf (src/dataset.jl:76-80) with the flows taken out of model_adjoint.  With a pixel mask five launches: EB -> beam -> QU with
+  // ifft_x (Hermitian rows projected, as in lens_from_harmonic), mask, Fourier mask / residual / Cn^-1 / Fourier mask', mask', beam' + QU -> EB +
+  // the prior term (PwNlAp); without one a single flat launch (PwNlDiag).  Returns where the partials of f'(out) were left (PART_CG_PAP).
+  DotOut nolens_adjoint(const cx<T>* f_h, const cx<T>* dd, int dB, cx<T>* out, int B) {
+    const long sl = (long)P * B;
+    DotOut pap{};
+    by_pol([&](auto pp) {
+      constexpr int PP = decltype(pp)::value;
+      const ModeGeom<T> g = c->geom();
+      if (!has(OP_MPIX)) {
+        PwNlDiag<T, PP> nd{g, {}, {}, opref(OP_CN_INV), opref(OP_CF_INV), dd, dB, f_h, out};
+        nd.pre.push(opref(OP_B)); nd.pre.push(opref(OP_MF));
+        nd.post.push(opref(OP_MF, true)); nd.post.push(opref(OP_B, true));
+        pap = c->pw_flat(nd, B, Ctx<T>::PART_CG_PAP);
+        return;
+      }
+      m1.ensure(sizeof(cx<T>) * sl * c->mplane());
+      cx<T>* m = m1.template as<cx<T>>();
+      PwChain<T, PP> b1{g, {}, 0, 1, nullptr, T(0), nullptr, T(1)};
+      b1.ch.push(opref(OP_B));
+      c->template x_pw<PP, true>(f_h, m, b1, B, true);                                  // beam, EB -> QU, ifft_x, Hermitian rows projected
+      c->y_mask(m, m, ops[OP_MPIX].d[0], sl);                                           // pixel mask
+      PwResid<T, PP> rs{g, {}, {}, opref(OP_CN_INV), dd, dB, T(-1), nullptr};
+      rs.pre.push(opref(OP_MF)); rs.post.push(opref(OP_MF, true));
+      c->template x_pw<PP, false>(m, m, rs, B, false, Ctx<T>::PART_QN);                 // Fourier mask, residual, Cn^-1, Fourier mask'; the sign of the gradient
+      c->y_mask(m, m, ops[OP_MPIX].d[0], sl);                                           // pixel mask'
+      PwNlAp<T, PP> ap{g, {}, opref(OP_CF_INV), f_h, out};
+      ap.post.push(opref(OP_B, true));
+      pap = c->template x_pw<PP, false>(m, nullptr, ap, B, false, Ctx<T>::PART_CG_PAP); // fft_x, QU -> EB, beam', - Cf^-1 f, stored; partials of f'(out)
+    });
+    return pap;
+  }
+  // The fused iteration of the Wiener filter without the flows: wiener_cg_fused with model_adjoint + PwCgAp replaced by nolens_adjoint, whose last
+  // launch leaves A p and the partials of p'Ap.  Per iteration 7 launches with a pixel mask, 3 without.  The scalar block (CgScal), the start
+  // (cg_problem, PwCgStart, k_cg_init), the flag mirror and the end (CgSolver::finish) are those of wiener_cg_fused.
+  int wiener_cg_nolens(LensOps<T>& L, const cx<T>* dd, const cx<T>* fstart, double tol, int maxit, cx<T>* f_out, double* hist, int B) {
+    const auto v = cg_problem(L, dd, fstart, maxit, 7, B);
+    cx<T>*x = v.x, *r = v.r, *p = v.p, *Ap = v.Ap, *bx = v.bx;
+    cg_rzfin.ensure(sizeof(double) * MAXBATCH);
+    CgScal st;
+    st.res = v.sd; st.best = v.sd + 2 * MAXBATCH;
+    st.hist = v.hist;
+    st.done = v.si; st.better = v.si + 2; st.nan = v.si + 4; st.nh = v.si + 5;
+    hipStream_t sm = c->stream;
+    const ModeGeom<T> g = c->geom();
+    const double sc = c->dot_scale();
+    by_pol([&](auto pp) {
+      constexpr int PP = decltype(pp)::value;
+      const DotOut o = c->pw_flat(PwCgStart<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, bx}, B, Ctx<T>::PART_CG_RZ);
+      CMBL_LAUNCH(c, K_CG, (k_cg_init<T>), dim3(1), 0, sm, st, o, sc, B);
+    });
+    cg.flags.post(0, st.done, 6, sm);
+    int par = 0;
+    if (cg.flags.wait(0)[4] == 0) {                                         // a NaN start residual is reported below
+      for (int it = 2; it <= maxit; ++it) {
+        const DotOut oA = nolens_adjoint(p, nullptr, B, Ap, B);             // A p = -B'M'Cn^-1 M B p - Cf^-1 p ; partials of p'Ap
+        by_pol([&](auto pp) {
+          constexpr int PP = decltype(pp)::value;
+          const DotOut oR = c->pw_flat(PwCgXr<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, Ap, st, par, oA, sc}, B, Ctx<T>::PART_CG_RZ);   // alpha ; x, r
+          const double* rzf = nullptr;                                      // (B > 16: see wiener_cg_fused)
+          if (B > 16) { double* const o1[1] = {cg_rzfin.as<double>()}; c->finish_parts(&oR, o1, 1, B); rzf = o1[0]; }
+          c->pw_flat(PwCgP<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, bx, st, par, tol, oR, sc, rzf}, B);                                 // beta, stop test ; p, best iterate
+        });
+        par ^= 1;
+        cg.flags.post(it & 1, st.done, 6, sm);
+        if (it > 2 && cg.flags.wait((it - 1) & 1)[it & 1] != 0) break;      // previous iteration's flags: it left `done` at parity (it - 2) & 1
+      }
+    }
+    return cg.finish(v, f_out, hist, st.done, 6, 4, 5);
+  }
+  // logpdf(ds; f) of the no-lensing model per batch slot, -1/2 [ f'Cf^-1 f + (M B f - d)'Cn^-1 (M B f - d) + logdet_sum ] with logdet_sum = logdet Cf +
+  // logdet Cn (src/dataset.jl:68-73, src/distributions.jl:11-15), and with gf_h its gradient B'M'Cn^-1 (d - M B f) - Cf^-1 f (src/dataset.jl:76-80)
+  // from the same pass through data space.  The sums are formed on the device in double, in a fixed order, and read back once (read_logpdf).
+  // Any size, either form of the noise operator.  Reads nothing of phi: OP_CPHI_INV, OP_D*, OP_G_INV need not be set.
+  void nolens_logpdf(const cx<T>* f_h, const cx<T>* dd, double* lp, cx<T>* gf_h, int B) {
+    const long n = fsize(B);
+    CMBL_REQUIRE(B <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
+    t1.ensure(sizeof(cx<T>) * n); t2.ensure(sizeof(cx<T>) * n); t3.ensure(sizeof(cx<T>) * n); qdev.ensure(sizeof(double) * 3 * MAXBATCH);
+    cx<T>*z = t1.template as<cx<T>>(), *cfif = t2.template as<cx<T>>(), *w = t3.template as<cx<T>>();
+    double* qd = qdev.template as<double>();
+    CMBL_HIP(hipMemsetAsync(qd + MAXBATCH, 0, sizeof(double), c->stream));   // the slot of phi'Cphi^-1 phi: this model has none
+    apply(OP_B, f_h, z, B);                                                  // z = M B f - d
+    apply_M(z, B, false);
+    c->lincomb1((T*)z, (const T*)z, (const T*)dd, 1.0, -1.0, 2 * n / B, B);
+    apply_cn_inv(z, w, B);                    c->dot_F_dev(z, w, P, B, qd + 2 * MAXBATCH);
+    apply(OP_CF_INV, f_h, cfif, B);           c->dot_F_dev(f_h, cfif, P, B, qd);
+    if (gf_h) {
+      apply_M(w, B, true);
+      apply(OP_B, w, w, B, true, false, false, nullptr, 0, (T)-1);
+      c->lincomb1((T*)gf_h, (const T*)w, (const T*)cfif, 1.0, -1.0, 2 * n / B, B);
+    }
+    read_logpdf(lp, B, 0);
+  }
+
   int wiener_cg(LensOps<T>& L, const cx<T>* dd, const cx<T>* fstart, double tol, int maxit, cx<T>* f_out, double* hist, int B) {
     if (Flow<T>* flow = fused() ? L.as_flow() : nullptr) return wiener_cg_fused(*flow, dd, fstart, tol, maxit, f_out, hist, B);
+    if (fused() && L.as_identity()) return wiener_cg_nolens(L, dd, fstart, tol, maxit, f_out, hist, B);
     const auto v = cg_problem(L, dd, fstart, maxit, 6, B);
     cg.solve(v, cg_A(L, B), [&](const cx<T>* r, cx<T>* z, double* rz) { apply(OP_PRECOND_INV, r, z, B); c->dot_F_dev(r, z, P, B, rz); }, tol);
     return cg.finish(v, f_out, hist, v.si, 4, 1, 2);

@@ -370,6 +370,58 @@ template <typename T, int P> struct PwCgStart {
     }
   }
 };
+// The no-lensing model d = M B f + n (NoLensingDataSet, src/dataset.jl:37-47, 68-73): A p = -B'M'Cn^-1 M B p - Cf^-1 p without a flow, so the
+// product and p'Ap leave the launch that ends the data-space part and PwCgAp is not launched.
+//   PwNlAp  (rows): v = fft_x(Mpix' w) in QU Fourier -> QU -> EB -> post chain (beam') -> A p = that - Cf^-1 p, stored in the F layout; partials
+//                   of p'Ap (sum 0).  The sign of the gradient rides in w (PwResid's scale).
+//   PwNlDiag (flat): no pixel mask, every factor is diagonal (or the IEB block) in the harmonic basis, so the whole product is one pass and needs
+//                   no QU rotation:  A p = -post(Cn^-1 (pre(p) - d)) - Cf^-1 p  with pre = Mf B, post = B'Mf'; partials of p'Ap (sum 0).
+//                   p is taken as the spectrum of a real map (no Hermitian projection: nothing here goes through c2r).
+// d != nullptr in PwNlDiag (and PwResid before PwNlAp): the same launches give gradientf_logpdf(f, d)   (src/dataset.jl:76-80)
+template <typename T, int P> struct PwNlAp {
+  static constexpr int NACC = 1;
+  using Local = NoLocal;
+  ModeGeom<T> g; HarmChain<T> post; OpRef<T> Cfinv;
+  const cx<T>* p; cx<T>* Ap;
+  __device__ __forceinline__ Local prologue(int, int, double*) const { return {}; }
+  __device__ __forceinline__ void operator()(const Local&, int b, long i, int ky, cx<T> (&v)[P], SumAccRt<T>* acc, int mode) const {
+    T c = 0, s = 0;
+    if (P >= 2) { c = g.cos2[i]; s = g.sin2[i]; }
+    rot_qu2eb<T, P>(v, c, s);
+    chain_apply<T, P>(post, i, v);
+    cx<T> w[P], pp[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) { w[q] = p[((long)b * P + q) * g.plane + i]; pp[q] = w[q]; }
+    op_apply<T, P>(Cfinv, i, w);
+    const T lam = g.lam[ky];
+#pragma unroll
+    for (int q = 0; q < P; ++q) { v[q] = v[q] - w[q]; Ap[((long)b * P + q) * g.plane + i] = v[q]; acc[0].add(mode, dot_term<T, P>(pp, v, q, lam)); }
+  }
+};
+template <typename T, int P> struct PwNlDiag {
+  static constexpr int NACC = 1;
+  using Local = NoLocal;
+  ModeGeom<T> g; HarmChain<T> pre, post; OpRef<T> Cninv, Cfinv;
+  const cx<T>* d; int dB;                     // data (harmonic F), nullable; dB = 1: one data set for all batch slots
+  const cx<T>* p; cx<T>* Ap;
+  __device__ __forceinline__ Local prologue(int, int, double*) const { return {}; }
+  __device__ __forceinline__ void operator()(const Local&, int b, long i, int ky, SumAccRt<T>* acc, int mode) const {
+    cx<T> v[P], w[P], pp[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) { v[q] = p[((long)b * P + q) * g.plane + i]; w[q] = v[q]; pp[q] = v[q]; }
+    chain_apply<T, P>(pre, i, v);
+    if (d) {
+#pragma unroll
+      for (int q = 0; q < P; ++q) v[q] = v[q] - d[((long)(dB == 1 ? 0 : b) * P + q) * g.plane + i];
+    }
+    op_apply<T, P>(Cninv, i, v);
+    chain_apply<T, P>(post, i, v);
+    op_apply<T, P>(Cfinv, i, w);
+    const T lam = g.lam[ky];
+#pragma unroll
+    for (int q = 0; q < P; ++q) { v[q] = T(-1) * v[q] - w[q]; Ap[((long)b * P + q) * g.plane + i] = v[q]; acc[0].add(mode, dot_term<T, P>(pp, v, q, lam)); }
+  }
+};
 template <typename T>
 __global__ __launch_bounds__(NTP) void k_cg_init(CgScal s, DotOut d, double scale, int B) {
   __shared__ double scratch[NTP / 64 + 2];

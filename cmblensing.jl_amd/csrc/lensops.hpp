@@ -1,5 +1,6 @@
 // What Dataset<T> needs of a lensing operator in its `L` slot (load_sim(L = ...), src/dataset.jl:223, 306, 333): implemented by Flow<T>
-// (LenseFlow, engine.hpp), Bilinear<T> (engine_bilinear.hpp) and PowerLens<T> (PowerLens / Taylens, engine_powerlens.hpp).  Fields are in the
+// (LenseFlow, engine.hpp), Bilinear<T> (engine_bilinear.hpp), PowerLens<T> (PowerLens / Taylens, engine_powerlens.hpp) and NoLens<T> (the identity
+// of load_nolensing_sim, engine_nolens.hpp).  Fields are in the
 // internal layouts: maps [slice][x][y], Fourier planes in the F layout, QU.  An action the reference does not define for an operator is
 // announced by its has_* member and refused with ERR_ARG by the default body: nothing is approximated.
 #pragma once
@@ -15,6 +16,8 @@ struct LensOps {
   virtual const char* op_name() const = 0;
   // the LenseFlow behind this operator, for the fused forms of Dataset<T> that only it has; nullptr for every other operator
   virtual Flow<T>* as_flow() { return nullptr; }
+  // true for NoLens<T> alone (L = I, src/dataset.jl:343): Dataset<T> then runs its flow-free forms (nolens_adjoint, wiener_cg_nolens)
+  virtual bool as_identity() const { return false; }
   // the operator has its phi (ERR_STATE otherwise) and takes B batch slots of f against it (ERR_SHAPE otherwise)
   virtual void op_check(int B) const = 0;
   // phi in the ABI's layout (basis MAP / FOURIER / HARMONIC), nb planes; the operators that refuse a batched phi fail with ERR_SHAPE

@@ -11,6 +11,7 @@ import torch
 
 from .engine import Field, MAP, FOURIER, HARMONIC
 from .sim import noise_from_white
+from .nolensing import NoLensingDataSet
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -274,7 +275,10 @@ def MAP_joint_step(ds, phi, fstart=None, alpha_prev=1.0, alpha_tol=1e-4, alpha_m
 
 
 def MAP_joint(ds, nsteps=20, phi_start=None, fstart=None, **kw):
-    """`MAP_joint(ds; nsteps, fstart)` (src/maximization.jl:116-233) at the dataset's current θ: returns (f, ϕ, history)."""
+    """`MAP_joint(ds; nsteps, fstart)` (src/maximization.jl:116-233) at the dataset's current θ: returns (f, ϕ, history).  Of a `NoLensingDataSet` it is
+    the Wiener filter, returned as (f, None) (:235; `cg_tol`, `cg_nsteps` and `fstart` are read)."""
+    if isinstance(ds, NoLensingDataSet):                    # MAP_joint(θ, ds::NoLensingDataSet) = (argmaxf_logpdf(I, θ, ds), nothing)  (src/maximization.jl:235)
+        return ds.argmaxf_logpdf(fstart=fstart, tol=kw.get("cg_tol", 1e-1), nsteps=kw.get("cg_nsteps", 500))[0], None
     ds._flow("MAP_joint")                                   # refused up front with another operator in ds.L (no pullback of L \ f)
     proj = ds.proj
     B = ds.d.arr.shape[0]
@@ -446,7 +450,11 @@ def MAP_joint_step_native(ds, phi, fstart=None, alpha_prev=1.0, alpha_tol=1e-4, 
 
 
 def sample_f(ds, phi, white_f, white_n, fstart=None, tol=1e-1, nsteps=500):
-    """`sample_f` (src/maximization.jl:56-62)"""
+    """`sample_f` (src/maximization.jl:56-62).  A `NoLensingDataSet` takes phi = None."""
+    if isinstance(ds, NoLensingDataSet):
+        fs = ds._draw_f(white_f)
+        df, hist = ds.argmaxf_logpdf(d=ds.d - (ds.mean(fs) + noise_from_white(ds, white_n)), fstart=fstart, tol=tol, nsteps=nsteps)
+        return fs + df, hist
     proj, h = ds.proj, ds.host
     raw = lambda w, op: Field(proj, proj.diag_apply(op.sqrt().p, proj.rfft(proj.tensor(w)), HARMONIC, HARMONIC), HARMONIC)
     fs, ns = raw(white_f, h["Cf"]), noise_from_white(ds, white_n)

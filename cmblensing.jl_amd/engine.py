@@ -788,6 +788,28 @@ class Taylens(PowerLens):
         raise NotImplementedError("the reference defines no adjoint of Taylens (src/taylens.jl)")
 
 
+class IdentityLens(_LensOp):
+    """The identity in the `L` slot: `L = lensed_data ? LenseFlow : I` of `load_nolensing_sim` (src/dataset.jl:341-352), the operator of a
+    `NoLensingDataSet` (`cmbl_lensop_identity`).  `L * f`, `L.ldiv(f)`, `L.adjoint * g` and `L.adjoint.ldiv(g)` return the field unchanged, in the MAP
+    basis like the other operators' results; `L(ϕ)` takes any ϕ and returns itself.  In a `BaseDataSet` it behaves like a `BilinearLens` without a
+    pullback: the Wiener filter, `gradientf_logpdf` and `grad_logpdf(want_phi=False)` work, what needs the gradient with respect to ϕ is refused."""
+    _destroy = "cmbl_lensop_destroy"
+
+    def __init__(self, proj):
+        self.proj, self._phi = proj, None
+        self._open(proj.lib, "cmbl_lensop_identity", proj._h)
+
+    def _view(self):
+        return self._h                       # the handle IS the `cmbl_lensop` the `cmbl_*_op` entry points take
+
+    def __call__(self, phi):
+        return self
+
+    def _apply(self, mode, f, basis_out=None, *extra, **kw):
+        self.proj._check(f.arr, f.basis)
+        return f.to(MAP if basis_out is None else basis_out)
+
+
 def antilensing(L):
     """`antilensing(L)` (src/powerlens.jl:32-38): a new operator of the same kind and order that lenses by -ϕ (by -d after `set_deflection`)."""
     A = type(L)(L.proj, L.order)
@@ -809,29 +831,20 @@ def _check_lens_slot(proj, L, allow_factory):
         return
     if allow_factory and callable(L):
         return
-    raise TypeError(f"the L slot of a data set takes a lensing operator (LenseFlow, BilinearLens, PowerLens, Taylens) on its projection, "
+    raise TypeError(f"the L slot of a data set takes a lensing operator (LenseFlow, BilinearLens, PowerLens, Taylens, IdentityLens) on its projection, "
                     f"or a callable proj -> operator; got {type(L).__name__}")
 
 
-class BaseDataSet(_Handle):
-    """`BaseDataSet` at fiducial θ (src/dataset.jl:37-57) with the operators resident on the device.
-
-    ops: dict name -> real planes (numpy/torch, reference layout):
-        'Cf_inv','Cn_inv','B','Mf','D','D_inv','precond_inv' : (P or 5, Nx, Nyh)   harmonic basis
-        'Cphi_inv','G_inv' : (1, Nx, Nyh) ;  'Mpix' : (Nx, Ny) optional
-        'Cn_inv_pix' : (P or 1, Nx, Ny) optional -- pinv(V) of a noise covariance Cn = Diagonal(V) in the I/QU map basis (0 where V is 0 or
-        infinite).  While set it IS the noise operator (`CMBL_OP_CN_INV_PIX`) and 'Cn_inv' is not read; `set_op("Cn_inv_pix", None)` clears it.
-    d: harmonic-basis data (B,P,Nx,Nyh); logdet_sum: logdet Cf + logdet Cϕ + logdet Cn.
-    """
+class _DataSetOps(_Handle):
+    """What `BaseDataSet` and `NoLensingDataSet` (nolensing.py) share: the `cmbl_dataset` handle, its operators and data on the device, the Python
+    compositions of M and M', and the two calls that take the operator of the `L` slot as a `cmbl_lensop` view."""
     _destroy = "cmbl_dataset_destroy"
     _ids = dict(Cf_inv=OP_CF_INV, Cn_inv=OP_CN_INV, B=OP_B, Mf=OP_MF, D=OP_D, D_inv=OP_D_INV,
                 precond_inv=OP_PRECOND_INV, Cphi_inv=OP_CPHI_INV, G_inv=OP_G_INV, Mpix=OP_MPIX, Cn_inv_pix=OP_CN_INV_PIX)
 
-    def __init__(self, proj, P, ops, d=None, logdet_sum=0.0, nsteps=7, L=None):
-        self.proj, self.P = proj, int(P)
-        _check_lens_slot(proj, L, allow_factory=True)               # before anything is created on the device
-        self._open(proj.lib, "cmbl_dataset_create", proj._h, self.P)
-        self.L = LenseFlow(proj, nsteps) if L is None else L
+    def _load(self, ops, d, logdet_sum):
+        """the operators, the data and the logdet sum of a freshly opened handle"""
+        proj = self.proj
         self.ops = {}
         for k, v in ops.items():
             if v is None:
@@ -844,34 +857,26 @@ class BaseDataSet(_Handle):
         if d is not None:
             self.set_data(d)
         self.logdet_sum = float(logdet_sum)
-        self.logdet_mix = 0.0          # logdet(D,θ) + logdet(G,θ) of the mixed parametrisation (src/dataset.jl:86); 0 at fiducial θ
-        # ϕ-gradients: False = the mathematically consistent δϕ velocity (default), True = the reference exactly as written, with
-        # the in-place aliasing of src/lenseflow.jl:198-200 (differs by ~3e-4).  Every driver (MAP_joint, MAP_marg,
-        # hmc_step, sample_joint) takes `alias_quirk=None` = this dataset-level setting.  CMBL_REFERENCE_EXACT=1 flips the default
-        # (and starts every context with plain working-precision sums, the reference's `sum_accuracy_mode`).
-        self.alias_quirk = reference_exact()
-        check(self.lib.cmbl_dataset_set_logdet(self._h, self.logdet_sum))
 
-    @property
-    def L(self):
-        """The lensing operator of the data set (`load_sim(L = ...)`, src/dataset.jl:223, 306, 333): a `LenseFlow` by default; any `_LensOp` on
-        `ds.proj`, or a callable `proj -> _LensOp` (`BilinearLens`, `lambda p: PowerLens(p, 4)`), may be assigned.  Anything else raises at once."""
-        return self._L
+    def _gradientf(self, L, f, d, zero_d):
+        f = f.to(HARMONIC)
+        B = f.arr.shape[0]
+        out = self.proj.empty(HARMONIC, self.P, B)
+        dd = None if d is None else d.to(HARMONIC).arr
+        check(self.lib.cmbl_gradientf_logpdf_op(self._h, L._view(), _ptr(f.arr), _ptr(dd), 1 if zero_d else 0, _ptr(out), B))
+        return Field(self.proj, out, HARMONIC)
 
-    @L.setter
-    def L(self, op):
-        if not isinstance(op, _LensOp) and callable(op):
-            _check_lens_slot(self.proj, op, allow_factory=True)
-            op = op(self.proj)
-        _check_lens_slot(self.proj, op, allow_factory=False)
-        self._L = op
-
-    def _flow(self, what):
-        """the `LenseFlow` in the slot, for what the reference defines with it alone"""
-        if not isinstance(self._L, LenseFlow):
-            raise NotImplementedError(f"{what} needs the gradient of logpdf(Mixed(ds)), a pullback of `L \\ f`: src/bilinearlens.jl (:165-171) has a "
-                                      f"rule for `L * f` alone, and PowerLens / Taylens have no inverse -- use a LenseFlow in ds.L, not {type(self._L).__name__}")
-        return self._L
+    def _wiener(self, L, d, fstart, tol, nsteps):
+        dd = self.d if d is None else d.to(HARMONIC)
+        B = dd.arr.shape[0]
+        out = self.proj.empty(HARMONIC, self.P, B)
+        hist = (ctypes.c_double * (nsteps * B))()
+        nit = ctypes.c_int(0)
+        fs = None if fstart is None else fstart.to(HARMONIC).arr
+        check(self.lib.cmbl_wiener_cg_op(self._h, L._view(), _ptr(dd.arr), _ptr(fs), float(tol), int(nsteps), _ptr(out),
+                                         hist, ctypes.byref(nit), B))
+        h = np.array(hist[: nit.value * B]).reshape(nit.value, B)
+        return Field(self.proj, out, HARMONIC), [(i + 1, h[i]) for i in range(nit.value)]
 
     def set_logdet(self, logdet_sum):
         self.logdet_sum = float(logdet_sum)
@@ -923,6 +928,69 @@ class BaseDataSet(_Handle):
             self._mask_full = (key, self.ops["Mpix"].reshape(1, 1, self.proj.Nx, self.proj.Ny).expand(*key).contiguous())
         return Field(self.proj, self.proj.map_fma(m.arr, self._mask_full[1]), MAP).to(HARMONIC)
 
+    def _mask(self, f):
+        """M = Mfourier * Mpix (src/dataset.jl:279-285) on a Field; returns HARMONIC"""
+        if "Mpix" in self.ops:
+            m = f.to(MAP)
+            key = tuple(m.arr.shape)
+            if getattr(self, "_mask_full", (None, None))[0] != key:
+                self._mask_full = (key, self.ops["Mpix"].reshape(1, 1, self.proj.Nx, self.proj.Ny).expand(*key).contiguous())
+            f = Field(self.proj, self.proj.map_fma(m.arr, self._mask_full[1]), MAP)
+        return self._apply("Mf", f)
+
+    def set_data(self, d):
+        d = d if isinstance(d, Field) else Field(self.proj, self.proj.tensor(d), HARMONIC)
+        d = d.to(HARMONIC)
+        self.d = d
+        check(self.lib.cmbl_dataset_set_data(self._h, _ptr(d.arr), d.arr.shape[0]))
+
+
+class BaseDataSet(_DataSetOps):
+    """`BaseDataSet` at fiducial θ (src/dataset.jl:37-57) with the operators resident on the device.
+
+    ops: dict name -> real planes (numpy/torch, reference layout):
+        'Cf_inv','Cn_inv','B','Mf','D','D_inv','precond_inv' : (P or 5, Nx, Nyh)   harmonic basis
+        'Cphi_inv','G_inv' : (1, Nx, Nyh) ;  'Mpix' : (Nx, Ny) optional
+        'Cn_inv_pix' : (P or 1, Nx, Ny) optional -- pinv(V) of a noise covariance Cn = Diagonal(V) in the I/QU map basis (0 where V is 0 or
+        infinite).  While set it IS the noise operator (`CMBL_OP_CN_INV_PIX`) and 'Cn_inv' is not read; `set_op("Cn_inv_pix", None)` clears it.
+    d: harmonic-basis data (B,P,Nx,Nyh); logdet_sum: logdet Cf + logdet Cϕ + logdet Cn.
+    """
+
+    def __init__(self, proj, P, ops, d=None, logdet_sum=0.0, nsteps=7, L=None):
+        self.proj, self.P = proj, int(P)
+        _check_lens_slot(proj, L, allow_factory=True)               # before anything is created on the device
+        self._open(proj.lib, "cmbl_dataset_create", proj._h, self.P)
+        self.L = LenseFlow(proj, nsteps) if L is None else L
+        self._load(ops, d, logdet_sum)
+        self.logdet_mix = 0.0          # logdet(D,θ) + logdet(G,θ) of the mixed parametrisation (src/dataset.jl:86); 0 at fiducial θ
+        # ϕ-gradients: False = the mathematically consistent δϕ velocity (default), True = the reference exactly as written, with
+        # the in-place aliasing of src/lenseflow.jl:198-200 (DESIGN.md Q1; differs by ~3e-4).  Every driver (MAP_joint, MAP_marg,
+        # hmc_step, sample_joint) takes `alias_quirk=None` = this dataset-level setting.  CMBL_REFERENCE_EXACT=1 flips the default
+        # (and starts every context with plain working-precision sums, the reference's `sum_accuracy_mode`).
+        self.alias_quirk = reference_exact()
+        check(self.lib.cmbl_dataset_set_logdet(self._h, self.logdet_sum))
+
+    @property
+    def L(self):
+        """The lensing operator of the data set (`load_sim(L = ...)`, src/dataset.jl:223, 306, 333): a `LenseFlow` by default; any `_LensOp` on
+        `ds.proj`, or a callable `proj -> _LensOp` (`BilinearLens`, `lambda p: PowerLens(p, 4)`), may be assigned.  Anything else raises at once."""
+        return self._L
+
+    @L.setter
+    def L(self, op):
+        if not isinstance(op, _LensOp) and callable(op):
+            _check_lens_slot(self.proj, op, allow_factory=True)
+            op = op(self.proj)
+        _check_lens_slot(self.proj, op, allow_factory=False)
+        self._L = op
+
+    def _flow(self, what):
+        """the `LenseFlow` in the slot, for what the reference defines with it alone"""
+        if not isinstance(self._L, LenseFlow):
+            raise NotImplementedError(f"{what} needs the gradient of logpdf(Mixed(ds)), a pullback of `L \\ f`: src/bilinearlens.jl (:165-171) has a "
+                                      f"rule for `L * f` alone, and PowerLens / Taylens have no inverse -- use a LenseFlow in ds.L, not {type(self._L).__name__}")
+        return self._L
+
     def gradientphi_logpdf(self, f, phi, d=None, alias_quirk=None):
         """∂/∂ϕ logpdf(ds; f, ϕ, d) at fixed f -- what `gradient(ϕ -> logpdf(dsθ; f=f_wf, ϕ, dsθ.d), ϕ)` evaluates in MAP_marg
         (src/maximization.jl:301): the δ-flow pullback of L(ϕ)*f (src/flowops.jl:40-54) applied to ∂/∂f̃ = B'M'Cn⁻¹(d − MBLf),
@@ -959,16 +1027,6 @@ class BaseDataSet(_Handle):
         L._phi = phi                                    # the library set the operator's ϕ from this very plane
         return (np.array(lp[:]), None if gf is None else Field(self.proj, gf, HARMONIC), None if gp is None else Field(self.proj, gp, FOURIER))
 
-    def _mask(self, f):
-        """M = Mfourier * Mpix (src/dataset.jl:279-285) on a Field; returns HARMONIC"""
-        if "Mpix" in self.ops:
-            m = f.to(MAP)
-            key = tuple(m.arr.shape)
-            if getattr(self, "_mask_full", (None, None))[0] != key:
-                self._mask_full = (key, self.ops["Mpix"].reshape(1, 1, self.proj.Nx, self.proj.Ny).expand(*key).contiguous())
-            f = Field(self.proj, self.proj.map_fma(m.arr, self._mask_full[1]), MAP)
-        return self._apply("Mf", f)
-
     def mean(self, f, phi):
         """μ = M·B·L(ϕ)·f (src/dataset.jl:59-66)"""
         ft = self.L(phi) * f.to(MAP)
@@ -985,36 +1043,14 @@ class BaseDataSet(_Handle):
         q2 = phi.dot(cp)
         return -0.5 * (q1 + q2 + q3 + self.logdet_sum)
 
-    def set_data(self, d):
-        d = d if isinstance(d, Field) else Field(self.proj, self.proj.tensor(d), HARMONIC)
-        d = d.to(HARMONIC)
-        self.d = d
-        check(self.lib.cmbl_dataset_set_data(self._h, _ptr(d.arr), d.arr.shape[0]))
-
     def gradientf_logpdf(self, f, phi, d=None, zero_d=False):
         """src/dataset.jl:76-80.  phi = None: the operator as it was last set (`set_phi` / `set_deflection`)"""
-        f = f.to(HARMONIC)
-        L = self.L if phi is None else self.L(phi)
-        B = f.arr.shape[0]
-        out = self.proj.empty(HARMONIC, self.P, B)
-        dd = None if d is None else d.to(HARMONIC).arr
-        check(self.lib.cmbl_gradientf_logpdf_op(self._h, L._view(), _ptr(f.arr), _ptr(dd), 1 if zero_d else 0, _ptr(out), B))
-        return Field(self.proj, out, HARMONIC)
+        return self._gradientf(self.L if phi is None else self.L(phi), f, d, zero_d)
 
     def argmaxf_logpdf(self, phi, d=None, fstart=None, tol=1e-1, nsteps=500):
         """Wiener filter (src/maximization.jl:17-42): returns (f [HARMONIC], history [(i, res_per_batch)]).  phi = None: the operator as it
         was last set (`set_phi` / `set_deflection`)."""
-        L = self.L if phi is None else self.L(phi)
-        dd = self.d if d is None else d.to(HARMONIC)
-        B = dd.arr.shape[0]
-        out = self.proj.empty(HARMONIC, self.P, B)
-        hist = (ctypes.c_double * (nsteps * B))()
-        nit = ctypes.c_int(0)
-        fs = None if fstart is None else fstart.to(HARMONIC).arr
-        check(self.lib.cmbl_wiener_cg_op(self._h, L._view(), _ptr(dd.arr), _ptr(fs), float(tol), int(nsteps), _ptr(out),
-                                         hist, ctypes.byref(nit), B))
-        h = np.array(hist[: nit.value * B]).reshape(nit.value, B)
-        return Field(self.proj, out, HARMONIC), [(i + 1, h[i]) for i in range(nit.value)]
+        return self._wiener(self.L if phi is None else self.L(phi), d, fstart, tol, nsteps)
 
     def logpdf_mixed(self, fo, phio):
         """logpdf(Mixed(ds); f°, ϕ°) (src/dataset.jl:84-87)"""

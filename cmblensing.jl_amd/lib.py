@@ -58,10 +58,12 @@ SIGNATURES = {
     "cmbl_lensop_from_lenseflow": [_vp, _pvp],
     "cmbl_lensop_from_bilinear": [_vp, _pvp],
     "cmbl_lensop_from_powerlens": [_vp, _pvp],
+    "cmbl_lensop_identity": [_vp, _pvp],
     "cmbl_lensop_destroy": [_vp],
     "cmbl_gradientf_logpdf_op": [_vp, _vp, _vp, _vp, _ci, _vp, _ci],
     "cmbl_wiener_cg_op": [_vp, _vp, _vp, _vp, _cd, _ci, _vp, _pd, _pci, _ci],
     "cmbl_grad_logpdf_op": [_vp, _vp, _vp, _vp, _vp, _pd, _vp, _vp, _ci, _ci],
+    "cmbl_nolensing_logpdf": [_vp, _vp, _vp, _pd, _vp, _ci],
     "cmbl_logpdf_mixed": [_vp, _vp, _vp, _vp, _pd, _ci],
     "cmbl_grad_logpdf_mixed": [_vp, _vp, _vp, _vp, _pd, _vp, _vp, _ci, _ci],
     "cmbl_dataset_theta_model": [_vp, _pd, _ci, _pd, _ci, _pci, _vp, _pci, _pd, _pd, _cd, _cd, _pd, _cd, _pd, _pd, _cd],

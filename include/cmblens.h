@@ -534,7 +534,7 @@ int cmbl_wiener_cg(cmbl_dataset* ds, cmbl_flow* L, const void* d, const void* fs
                    void* f_out, double* res_hist_host, int* nit_host, int nbatch);
 /* ---- any lensing operator in the L slot of a data set (load_sim(L = ...), src/dataset.jl:223, 306, 333; src/bilinearlens.jl:10-17) --------
  * A cmbl_lensop is a typed, NON-OWNING view of an operator handle: destroying the view leaves the operator untouched, and the operator must
- * outlive its views.  The operator and the data set must live on the same context (CMBL_ERR_ARG).  What the reference does not define for an
+ * outlive its views (cmbl_lensop_identity is the exception: there is no operator handle behind it).  The operator and the data set must live on the same context (CMBL_ERR_ARG).  What the reference does not define for an
  * operator is refused with CMBL_ERR_ARG and a message, never approximated: the adjoint of a Taylens (so cmbl_gradientf_logpdf_op /
  * cmbl_wiener_cg_op with it, src/taylens.jl:51), the pullback with respect to phi of a PowerLens / Taylens (gphi_out, src/powerlens.jl).
  * Through a view of a LenseFlow the first two calls run the very code of cmbl_gradientf_logpdf / cmbl_wiener_cg, bit for bit.
@@ -542,6 +542,13 @@ int cmbl_wiener_cg(cmbl_dataset* ds, cmbl_flow* L, const void* d, const void* fs
 int cmbl_lensop_from_lenseflow(cmbl_flow* L, cmbl_lensop** out);
 int cmbl_lensop_from_bilinear(cmbl_bilinear* L, cmbl_lensop** out);
 int cmbl_lensop_from_powerlens(cmbl_powerlens* L, cmbl_lensop** out);
+/* The identity for the L slot: `L = lensed_data ? LenseFlow : I` of load_nolensing_sim (src/dataset.jl:341-352), the operator of NoLensingDataSet,
+ * d = M B f + n (src/dataset.jl:37-47, 68-73).  The one view that owns what is behind it; cmbl_lensop_destroy frees it.  It has no phi (a phi handed
+ * to cmbl_grad_logpdf_op is ignored by the operator) and no pullback with respect to one: cmbl_grad_logpdf_op with a gphi_out is CMBL_ERR_ARG.
+ * cmbl_gradientf_logpdf_op and cmbl_wiener_cg_op take it as any other view; on power-of-two maps with the option "fused_harm" and a
+ * Fourier-diagonal noise operator they run without any flow (csrc/kernels_harm.hpp PwNlAp / PwNlDiag): per CG iteration 7 launches with a
+ * pixel mask and 3 without; otherwise the composition around device copies. */
+int cmbl_lensop_identity(cmbl_ctx* ctx, cmbl_lensop** out);
 int cmbl_lensop_destroy(cmbl_lensop* op);            /* the operator itself is untouched */
 /* gradientf_logpdf (src/dataset.jl:76-80) and argmaxf_logpdf (src/maximization.jl:17-42): layouts and semantics of cmbl_gradientf_logpdf /
  * cmbl_wiener_cg.  The operator is used as it was last set (set_phi / set_deflection); CMBL_ERR_STATE before either. */
@@ -555,6 +562,13 @@ int cmbl_wiener_cg_op(cmbl_dataset* ds, cmbl_lensop* L, const void* d, const voi
  * alias_quirk is read by the LenseFlow view only.  Synchronises the context's stream. */
 int cmbl_grad_logpdf_op(cmbl_dataset* ds, cmbl_lensop* L, const void* f, const void* phi, const void* d,
                         double* lp_host, void* gf_out, void* gphi_out, int nbatch, int alias_quirk);
+
+/* logpdf(ds; f) of a NoLensingDataSet (src/dataset.jl:68-73, src/distributions.jl:11-15) per batch slot to lp_host:
+ *   -1/2 [ f'Cf^-1 f + (M B f - d)'Cn^-1 (M B f - d) + logdet_sum ],   logdet_sum (cmbl_dataset_set_logdet) = logdet Cf + logdet Cn here,
+ * and with gf_out != NULL its gradient gradientf_logpdf = B'M'Cn^-1 (d - M B f) - Cf^-1 f (src/dataset.jl:76-80) from the same pass.  f, gf_out
+ * HARMONIC; d = NULL uses ds.d.  Reads CMBL_OP_CF_INV, the noise operator, CMBL_OP_B, CMBL_OP_MF and CMBL_OP_MPIX alone: the operators of phi and
+ * of the mixing need not be set.  Any map size.  Synchronises the context's stream. */
+int cmbl_nolensing_logpdf(cmbl_dataset* ds, const void* f, const void* d, double* lp_host, void* gf_out /*NULL: value only*/, int nbatch);
 
 /* logpdf(Mixed(ds); f°, phi°) and its gradient (src/dataset.jl:84-117, src/maximization.jl:178):
  * fo MAP, phio FOURIER; gfo MAP, gphio FOURIER.  L's phi is overwritten with G \ phi°. */

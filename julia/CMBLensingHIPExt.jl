@@ -26,7 +26,7 @@
 module CMBLensingHIPExt
 
 using CMBLensing, AMDGPU, Adapt, LinearAlgebra, Random, Zygote
-using CMBLensing: FlowOpWithAdjoint, ImplicitOp, BaseDataSet, DataSet, Mixed, Field, BaseField, ProjLambert, Map, Fourier, EBFourier, IEBFourier,
+using CMBLensing: FlowOpWithAdjoint, ImplicitOp, BaseDataSet, NoLensingDataSet, DataSet, Mixed, Field, BaseField, ProjLambert, Map, Fourier, EBFourier, IEBFourier,
                   QUFourier, IQUFourier, Ł, Ð, BlockDiagIEB, LazyBinaryOp, FieldTuple, batch_length, batch, unbatch, nan2zero, diag
 import CMBLensing: precompute!!, getϕ, gradientf_logpdf, argmaxf_logpdf, logpdf
 import Base: *, \, adjoint
@@ -445,6 +445,92 @@ function argmaxf_logpdf(hd::HIPDataSet, Ω::NamedTuple, d=hd.ds.d; fstart=nothin
               hd.h, L.h, devptr(a), isnothing(fs) ? C_NULL : devptr(fs), get(conjgrad_kwargs, :tol, 1e-1), nsteps, devptr(o), hist, nit, B))
     history = [(i=i, res=(B == 1 ? hist[i] : batch(hist[(i-1)*B+1:i*B]))) for i in 1:nit[]]
     out, history
+end
+
+# ---- NoLensingDataSet (src/dataset.jl:37-47, 68-73): d = M B f + n, the identity in the L slot (cmbl_lensop_identity) --------------------
+"""
+    HIPNoLensingDataSet(ds::NoLensingDataSet)
+
+`ds` at its current θ with its Fourier-diagonal operators resident in the library: `gradientf_logpdf`, `argmaxf_logpdf(I, ...)` (the
+Wiener filter; `MAP_joint(θ, ds)` is it, src/maximization.jl:235) and `logpdf` run inside libcmblens_hip, on power-of-two maps without
+any flow.  Nothing about ϕ is uploaded.
+"""
+mutable struct HIPNoLensingDataSet{DS<:NoLensingDataSet} <: DataSet
+    ds :: DS
+    h  :: Ptr{Cvoid}
+    id :: Ptr{Cvoid}                                                      # the cmbl_lensop of the identity
+end
+Base.getproperty(d::HIPNoLensingDataSet, k::Symbol) = k in (:ds, :h, :id) ? getfield(d, k) : getproperty(getfield(d, :ds), k)
+function HIPNoLensingDataSet(ds::NoLensingDataSet)
+    ctx = hip_ctx(ds.d.metadata)
+    h, id = Ref{Ptr{Cvoid}}(), Ref{Ptr{Cvoid}}()
+    chk(ccall((:cmbl_dataset_create, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}), ctx.h, size(ds.d.arr, 3), h))
+    chk(ccall((:cmbl_lensop_identity, lib), Cint, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}), ctx.h, id))
+    hd = HIPNoLensingDataSet(ds, h[], id[])
+    finalizer(hd) do x
+        ccall((:cmbl_lensop_destroy, lib), Cint, (Ptr{Cvoid},), getfield(x, :id))
+        ccall((:cmbl_dataset_destroy, lib), Cint, (Ptr{Cvoid},), getfield(x, :h))
+    end
+    Cf, Cn = ds.Cf, ds.Cn
+    set_op!(h[], ctx, OP_CF_INV, pinv(Cf));  set_op!(h[], ctx, OP_CN_INV, pinv(Cn));  set_op!(h[], ctx, OP_B, ds.B)
+    set_op!(h[], ctx, OP_PRECOND_INV, pinv(pinv(Cf) + ds.B̂' * ds.M̂' * pinv(ds.Cn̂) * ds.M̂ * ds.B̂))
+    M = ds.M
+    if M isa LazyBinaryOp                                                  # M = Mfourier * Mpix, as in upload!(::HIPDataSet)
+        set_op!(h[], ctx, OP_MF, M.X)
+        m = Map(diag(M.Y)).arr[:, :, 1, 1]
+        GC.@preserve m chk(ccall((:cmbl_dataset_set_op, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint), h[], OP_MPIX, devptr(m), 1))
+        keepalive(ctx, m)
+    else
+        set_op!(h[], ctx, OP_MF, M)
+    end
+    a = harm(ds.d).arr
+    GC.@preserve a chk(ccall((:cmbl_dataset_set_data, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint), h[], devptr(a), nbatch(ds.d)))
+    keepalive(ctx, a)
+    chk(ccall((:cmbl_dataset_set_logdet, lib), Cint, (Ptr{Cvoid}, Cdouble), h[], logdet(Cf) + logdet(Cn)))
+    hd
+end
+# src/dataset.jl:76-80 with L = I:  B'M'Cn⁻¹(d − M B f) − Cf⁻¹ f
+function gradientf_logpdf(hd::HIPNoLensingDataSet; f, θ=(;), d=hd.ds.d)
+    fh, dh = harm(f), harm(d)
+    out = similar(fh)
+    zero_d = all(iszero, dh.arr) ? 1 : 0
+    a, b, o = fh.arr, dh.arr, out.arr
+    GC.@preserve a b o chk(ccall((:cmbl_gradientf_logpdf_op, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint),
+                                 hd.h, hd.id, devptr(a), devptr(b), zero_d, devptr(o), nbatch(fh)))
+    keepalive(hip_ctx(fh.metadata), a, b)
+    out
+end
+# src/maximization.jl:17-42 with L = I; returns (f, history) like the reference
+function argmaxf_logpdf(hd::HIPNoLensingDataSet, Ω::NamedTuple, d=hd.ds.d; fstart=nothing, preconditioner=:diag,
+                        conjgrad_kwargs=(tol=1e-1, nsteps=500), offset=false)
+    dh = harm(d)
+    out = similar(dh)
+    nsteps = get(conjgrad_kwargs, :nsteps, 500)
+    B = nbatch(dh)
+    hist = Vector{Cdouble}(undef, nsteps * B)
+    nit = Ref{Cint}(0)
+    fs = isnothing(fstart) ? nothing : harm(fstart).arr
+    a, o = dh.arr, out.arr
+    GC.@preserve a o fs hist chk(ccall((:cmbl_wiener_cg_op, lib), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cint}, Cint),
+              hd.h, hd.id, devptr(a), isnothing(fs) ? C_NULL : devptr(fs), get(conjgrad_kwargs, :tol, 1e-1), nsteps, devptr(o), hist, nit, B))
+    history = [(i=i, res=(B == 1 ? hist[i] : batch(hist[(i-1)*B+1:i*B]))) for i in 1:nit[]]
+    out, history
+end
+CMBLensing.MAP_joint(θ, hd::HIPNoLensingDataSet; kwargs...) = (argmaxf_logpdf(hd, (; θ); kwargs...)[1], nothing)       # src/maximization.jl:235
+# logpdf(ds; f) (src/dataset.jl:68-73) and, with `grad = true`, (logpdf, gradientf_logpdf) from one pass
+function logpdf(hd::HIPNoLensingDataSet; f, θ=(;), d=hd.ds.d, grad=false)
+    fh, dh = harm(f), harm(d)
+    B = nbatch(fh)
+    lp = Vector{Cdouble}(undef, B)
+    g = grad ? similar(fh) : nothing
+    a, b = fh.arr, dh.arr
+    ga = grad ? g.arr : nothing
+    GC.@preserve a b ga lp chk(ccall((:cmbl_nolensing_logpdf, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cvoid}, Cint),
+                                     hd.h, devptr(a), devptr(b), lp, grad ? devptr(ga) : C_NULL, B))
+    T = real(eltype(fh))
+    v = B == 1 ? T(lp[1]) : batch(T.(lp))
+    grad ? (v, g) : v
 end
 
 # logpdf(Mixed(ds); f°, ϕ°[, θ]) (src/dataset.jl:84-87) and its gradient: unmix (G \ ϕ°, precompute, D \ (L \ f°)), the three
