@@ -138,10 +138,25 @@ struct Dataset : DatasetApi {
     r.kind = o.kind; r.transpose = transpose ? 1 : 0;
     return r;
   }
-  template <typename Fn> void by_pol(Fn&& fn) const {
-    if (P == 1) fn(std::integral_constant<int, 1>{}); else if (P == 2) fn(std::integral_constant<int, 2>{}); else fn(std::integral_constant<int, 3>{});
-  }
+  template <typename Fn> void by_pol(Fn&& fn) const { cmbl::by_pol(P, fn); }
   DevBuf m1;                                 // mixed-layout scratch of the data-space part
+  // The harmonic chains of the model on either side of Cn^-1:  pre = [B,] Mf  and  post = Mf' [, B']
+  void model_chains(HarmChain<T>& pre, HarmChain<T>& post, bool beam) const {
+    if (beam) pre.push(opref(OP_B));
+    pre.push(opref(OP_MF)); post.push(opref(OP_MF, true));
+    if (beam) post.push(opref(OP_B, true));
+  }
+  // The middle of a pass through data space with a pixel mask, in place on `m` (mixed layout, QU, the beam applied): pixel mask; one row pass with
+  // the Fourier mask, scale * (. - d), Cn^-1, the quadratic form and the Fourier mask'; pixel mask'.  store == false: the value alone, the pass
+  // ends with the quadratic form and m keeps the masked input.  Returns where the partials of the quadratic form were left (PART_QN).
+  template <int PP> DotOut masked_core(cx<T>* m, const cx<T>* dd, int dB, T scale, bool store, int B) {
+    c->y_mask(m, m, ops[OP_MPIX].d[0], (long)P * B);                                    // pixel mask
+    PwResid<T, PP> rs{c->geom(), {}, {}, opref(OP_CN_INV), dd, dB, scale, nullptr};
+    model_chains(rs.pre, rs.post, false);
+    const DotOut qn = c->template x_pw<PP, false>(m, store ? m : nullptr, rs, B, false, Ctx<T>::PART_QN);
+    if (store) c->y_mask(m, m, ops[OP_MPIX].d[0], (long)P * B);                         // pixel mask'
+    return qn;
+  }
   // From rfft_y(L f) in `a_ftil` (mixed, left intact) to  w = scale * B'M' Cn^-1 (M B L f - d):  w in QU Fourier to `w_F` (F layout) and
   // ifft_x(w) to L.H (mixed), ready for an adjoint / delta flow with h_ready.  Returns where the
   // partial sums of (MBLf - d)' Cn^-1 (MBLf - d) were left.  value_only: stop after the quadratic form.  dd == nullptr: d = 0.   (src/dataset.jl:59-66,76-80)
@@ -158,19 +173,14 @@ struct Dataset : DatasetApi {
         PwChain<T, PP> b1{g, {}, 1, 1, nullptr, T(0), nullptr, T(1)};
         b1.ch.push(opref(OP_B));
         c->template x_pw<PP, false>(a_ftil, m, b1, B);                                  // beam
-        c->y_mask(m, m, ops[OP_MPIX].d[0], sl);                                         // pixel mask
-        PwResid<T, PP> rs{g, {}, {}, opref(OP_CN_INV), dd, dB, T(1), nullptr};
-        rs.pre.push(opref(OP_MF)); rs.post.push(opref(OP_MF, true));
-        qn = c->template x_pw<PP, false>(m, value_only ? nullptr : m, rs, B, false, Ctx<T>::PART_QN);   // Fourier mask, residual, Cn^-1, quadratic form, Fourier mask'
+        qn = masked_core<PP>(m, dd, dB, T(1), !value_only, B);                          // mask, Fourier mask / residual / Cn^-1 / quadratic form / Fourier mask', mask'
         if (value_only) return;
-        c->y_mask(m, m, ops[OP_MPIX].d[0], sl);                                         // pixel mask'
         PwChain<T, PP> b2{g, {}, 1, 1, nullptr, T(0), w_F, scale};
         b2.ch.push(opref(OP_B, true));
         c->template x_pw<PP, false>(m, H, b2, B);                                       // beam', w stored, ifft_x(w) -> H
       } else {
         PwResid<T, PP> rs{g, {}, {}, opref(OP_CN_INV), dd, dB, scale, value_only ? nullptr : w_F};
-        rs.pre.push(opref(OP_B)); rs.pre.push(opref(OP_MF));
-        rs.post.push(opref(OP_MF, true)); rs.post.push(opref(OP_B, true));
+        model_chains(rs.pre, rs.post, true);
         qn = c->template x_pw<PP, false>(a_ftil, H, rs, B, false, Ctx<T>::PART_QN);
       }
     });
@@ -218,10 +228,10 @@ struct Dataset : DatasetApi {
     const long n = fsize(B);
     t2.ensure(sizeof(cx<T>) * n);
     cx<T>* r = t2.template as<cx<T>>();
-    Flow<T>* flow = fused() ? L.as_flow() : nullptr;
-    if (f_h && fused() && L.as_identity()) { nolens_adjoint(f_h, dd, B, out, B); return; }   // L = I: the flow-free form, Cf^-1 f included
-    if (f_h && flow) {
-      model_adjoint(*flow, f_h, dd, B, r, B);
+    const Form fm = form(L);
+    if (f_h && fm == FORM_IDENTITY) { nolens_adjoint(f_h, dd, B, out, B); return; }          // L = I: the flow-free form, Cf^-1 f included
+    if (f_h && fm == FORM_FLOW) {
+      model_adjoint(*L.as_flow(), f_h, dd, B, r, B);
     } else {
       if (f_h) {
         mean(L, f_h, r, B);
@@ -244,63 +254,32 @@ struct Dataset : DatasetApi {
     }
   }
 
-  // conjugate_gradient (src/numerical_algorithms.jl:73-134) driving argmaxf_logpdf (src/maximization.jl:17-42).
-  // a0 = gradientf(f=0,d=0) is identically zero for this linear model (all operators finite), so it is not evaluated.
-  // The scalars (res, alpha, beta, best residual, history, stop flag) live on the device; the loop, its storage and its end are CgSolver's (engine_cg.hpp).
-  DevBuf qdev, cg_rzfin;
+  // conjugate_gradient (src/numerical_algorithms.jl:73-134) driving argmaxf_logpdf (src/maximization.jl:17-42).  a0 = gradientf(f=0,d=0) is identically
+  // zero for this linear model (all operators finite), so it is not evaluated.  The scalars live on the device; both forms of the loop, their storage
+  // and their end are CgSolver's (engine_cg.hpp).  Which form runs, here and in gradientf: the fused ones need fused() and the LenseFlow or the identity.
+  enum Form { FORM_COMPOSED, FORM_FLOW, FORM_IDENTITY };
+  Form form(LensOps<T>& L) const { return !fused() ? FORM_COMPOSED : L.as_flow() ? FORM_FLOW : L.as_identity() ? FORM_IDENTITY : FORM_COMPOSED; }
+  DevBuf qdev;
   CgSolver<T> cg;
-  // What the two forms of the iteration share on top of the solver: b = -gradientf(f=0, d) = -L'B'M'Cn^-1 d, the start iterate x and r = b - A x
-  // with A = gradientf(., d = 0): both sides carry the sign of the gradient.  nd: doubles per slot of the scalar block (CgState 6, CgScal 7).
+  // What the forms of the iteration share on top of the solver: b = -gradientf(f=0, d) = -L'B'M'Cn^-1 d, the start iterate x and r = b - A x
+  // with A = gradientf(., d = 0): both sides carry the sign of the gradient.  Block: the scalar block of the form (CgStateBlock / CgScalBlock).
   auto cg_A(LensOps<T>& L, int B) { return [this, &L, B](const cx<T>* p, cx<T>* Ap, double* pAp) { gradientf(L, p, nullptr, Ap, B); if (pAp) c->dot_F_dev(p, Ap, P, B, pAp); }; }
-  typename CgSolver<T>::Vecs cg_problem(LensOps<T>& L, const cx<T>* dd, const cx<T>* fstart, int maxit, int nd, int B) {
+  template <typename Block> typename CgSolver<T>::Vecs cg_problem(LensOps<T>& L, const cx<T>* dd, const cx<T>* fstart, int maxit, int B) {
     CMBL_REQUIRE(B <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
-    const auto v = cg.begin(fsize(B), B, maxit, nd);
+    const auto v = cg.template begin<Block>(fsize(B), B, maxit);
     std::vector<double> mone(B, -1.0);
     gradientf(L, nullptr, dd, v.b, B);
     c->lincomb((T*)v.b, (T*)v.b, nullptr, mone.data(), nullptr, v.nr, B);
     cg.start(v, fstart, cg_A(L, B));
     return v;
   }
-  // Fused form of the same iteration (a LenseFlow on a power-of-two map): per iteration the two flows, 7 launches between them (basis change + ifft_x,
-  // c2r, beam, mask, Fourier mask / Cn^-1 / Fourier mask', mask', beam' + ifft_x) and 3 after them (A p and p'Ap -> alpha; x, r, r'z ->
-  // beta and the stop test; p and the best iterate).  Every scalar is produced by the launch that produced its sum.
-  int wiener_cg_fused(Flow<T>& L, const cx<T>* dd, const cx<T>* fstart, double tol, int maxit, cx<T>* f_out, double* hist, int B) {
-    const auto v = cg_problem(L, dd, fstart, maxit, 7, B);
-    cx<T>*x = v.x, *r = v.r, *p = v.p, *Y = v.z, *Ap = v.Ap, *bx = v.bx;
-    cg_rzfin.ensure(sizeof(double) * MAXBATCH);
-    CgScal st;
-    st.res = v.sd; st.best = v.sd + 2 * MAXBATCH;
-    st.hist = v.hist;
-    st.done = v.si; st.better = v.si + 2; st.nan = v.si + 4; st.nh = v.si + 5;
-    hipStream_t sm = c->stream;
-    const ModeGeom<T> g = c->geom();
-    const double sc = c->dot_scale();
-    by_pol([&](auto pp) {
-      constexpr int PP = decltype(pp)::value;
-      const DotOut o = c->pw_flat(PwCgStart<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, bx}, B, Ctx<T>::PART_CG_RZ);
-      CMBL_LAUNCH(c, K_CG, (k_cg_init<T>), dim3(1), 0, sm, st, o, sc, B);
-    });
-    cg.flags.post(0, st.done, 6, sm);
-    int par = 0;
-    if (cg.flags.wait(0)[4] == 0) {                                         // a NaN start residual is reported below
-      for (int it = 2; it <= maxit; ++it) {
-        model_adjoint(L, p, nullptr, B, Y, B);                              // Y = -L'B'M'Cn^-1 M B L p
-        by_pol([&](auto pp) {
-          constexpr int PP = decltype(pp)::value;
-          const DotOut oA = c->pw_flat(PwCgAp<T, PP>{g, opref(OP_CF_INV), Y, p, Ap}, B, Ctx<T>::PART_CG_PAP);                // A p = Y - Cf^-1 p
-          const DotOut oR = c->pw_flat(PwCgXr<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, Ap, st, par, oA, sc}, B, Ctx<T>::PART_CG_RZ);   // alpha ; x, r
-          // beta, stop test ; p, best iterate.  Every block needs r'z of ALL slots (`all(res < bestres)`, :111): up to 16 slots it adds
-          // their partials itself in its prologue; beyond that one small launch finishes them first (O(B) instead of O(B^2) per block)
-          const double* rzf = nullptr;
-          if (B > 16) { double* const o1[1] = {cg_rzfin.as<double>()}; c->finish_parts(&oR, o1, 1, B); rzf = o1[0]; }
-          c->pw_flat(PwCgP<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, bx, st, par, tol, oR, sc, rzf}, B);
-        });
-        par ^= 1;
-        cg.flags.post(it & 1, st.done, 6, sm);
-        if (it > 2 && cg.flags.wait((it - 1) & 1)[it & 1] != 0) break;      // previous iteration's flags: it left `done` at parity (it - 2) & 1
-      }
-    }
-    return cg.finish(v, f_out, hist, st.done, 6, 4, 5);
+  // A p = -L'B'M'Cn^-1 M B L p - Cf^-1 p of the fused iteration with a LenseFlow; returns the partials of p'Ap.  The two flows, 7 launches between
+  // them (basis change + ifft_x, c2r, beam, mask, Fourier mask / Cn^-1 / Fourier mask', mask', beam' + ifft_x) and one after.  Y: scratch.
+  DotOut flow_Ap(Flow<T>& L, const cx<T>* p, cx<T>* Y, cx<T>* Ap, int B) {
+    model_adjoint(L, p, nullptr, B, Y, B);                                  // Y = -L'B'M'Cn^-1 M B L p
+    DotOut oA{};
+    by_pol([&](auto pp) { oA = c->pw_flat(PwCgAp<T, decltype(pp)::value>{c->geom(), opref(OP_CF_INV), Y, p, Ap}, B, Ctx<T>::PART_CG_PAP); });   // A p = Y - Cf^-1 p
+    return oA;
   }
   // ---- the no-lensing model d = M B f + n (NoLensingDataSet, src/dataset.jl:37-47, 68-73; L = I in the slot) -------------------------------
   // out = A f [+ B'M'Cn^-1 d] = B'M'Cn^-1 (d - M B f) - Cf^-1 f  (harmonic F; dd == nullptr: d = 0; out must not alias f_h), the fused form of
@@ -315,8 +294,7 @@ struct Dataset : DatasetApi {
       const ModeGeom<T> g = c->geom();
       if (!has(OP_MPIX)) {
         PwNlDiag<T, PP> nd{g, {}, {}, opref(OP_CN_INV), opref(OP_CF_INV), dd, dB, f_h, out};
-        nd.pre.push(opref(OP_B)); nd.pre.push(opref(OP_MF));
-        nd.post.push(opref(OP_MF, true)); nd.post.push(opref(OP_B, true));
+        model_chains(nd.pre, nd.post, true);
         pap = c->pw_flat(nd, B, Ctx<T>::PART_CG_PAP);
         return;
       }
@@ -325,85 +303,60 @@ struct Dataset : DatasetApi {
       PwChain<T, PP> b1{g, {}, 0, 1, nullptr, T(0), nullptr, T(1)};
       b1.ch.push(opref(OP_B));
       c->template x_pw<PP, true>(f_h, m, b1, B, true);                                  // beam, EB -> QU, ifft_x, Hermitian rows projected
-      c->y_mask(m, m, ops[OP_MPIX].d[0], sl);                                           // pixel mask
-      PwResid<T, PP> rs{g, {}, {}, opref(OP_CN_INV), dd, dB, T(-1), nullptr};
-      rs.pre.push(opref(OP_MF)); rs.post.push(opref(OP_MF, true));
-      c->template x_pw<PP, false>(m, m, rs, B, false, Ctx<T>::PART_QN);                 // Fourier mask, residual, Cn^-1, Fourier mask'; the sign of the gradient
-      c->y_mask(m, m, ops[OP_MPIX].d[0], sl);                                           // pixel mask'
+      masked_core<PP>(m, dd, dB, T(-1), true, B);                                       // mask, Fourier mask / residual / Cn^-1 / Fourier mask', mask'; the sign of the gradient
       PwNlAp<T, PP> ap{g, {}, opref(OP_CF_INV), f_h, out};
       ap.post.push(opref(OP_B, true));
       pap = c->template x_pw<PP, false>(m, nullptr, ap, B, false, Ctx<T>::PART_CG_PAP); // fft_x, QU -> EB, beam', - Cf^-1 f, stored; partials of f'(out)
     });
     return pap;
   }
-  // The fused iteration of the Wiener filter without the flows: wiener_cg_fused with model_adjoint + PwCgAp replaced by nolens_adjoint, whose last
-  // launch leaves A p and the partials of p'Ap.  Per iteration 7 launches with a pixel mask, 3 without.  The scalar block (CgScal), the start
-  // (cg_problem, PwCgStart, k_cg_init), the flag mirror and the end (CgSolver::finish) are those of wiener_cg_fused.
-  int wiener_cg_nolens(LensOps<T>& L, const cx<T>* dd, const cx<T>* fstart, double tol, int maxit, cx<T>* f_out, double* hist, int B) {
-    const auto v = cg_problem(L, dd, fstart, maxit, 7, B);
-    cx<T>*x = v.x, *r = v.r, *p = v.p, *Ap = v.Ap, *bx = v.bx;
-    cg_rzfin.ensure(sizeof(double) * MAXBATCH);
-    CgScal st;
-    st.res = v.sd; st.best = v.sd + 2 * MAXBATCH;
-    st.hist = v.hist;
-    st.done = v.si; st.better = v.si + 2; st.nan = v.si + 4; st.nh = v.si + 5;
-    hipStream_t sm = c->stream;
-    const ModeGeom<T> g = c->geom();
-    const double sc = c->dot_scale();
-    by_pol([&](auto pp) {
-      constexpr int PP = decltype(pp)::value;
-      const DotOut o = c->pw_flat(PwCgStart<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, bx}, B, Ctx<T>::PART_CG_RZ);
-      CMBL_LAUNCH(c, K_CG, (k_cg_init<T>), dim3(1), 0, sm, st, o, sc, B);
-    });
-    cg.flags.post(0, st.done, 6, sm);
-    int par = 0;
-    if (cg.flags.wait(0)[4] == 0) {                                         // a NaN start residual is reported below
-      for (int it = 2; it <= maxit; ++it) {
-        const DotOut oA = nolens_adjoint(p, nullptr, B, Ap, B);             // A p = -B'M'Cn^-1 M B p - Cf^-1 p ; partials of p'Ap
-        by_pol([&](auto pp) {
-          constexpr int PP = decltype(pp)::value;
-          const DotOut oR = c->pw_flat(PwCgXr<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, Ap, st, par, oA, sc}, B, Ctx<T>::PART_CG_RZ);   // alpha ; x, r
-          const double* rzf = nullptr;                                      // (B > 16: see wiener_cg_fused)
-          if (B > 16) { double* const o1[1] = {cg_rzfin.as<double>()}; c->finish_parts(&oR, o1, 1, B); rzf = o1[0]; }
-          c->pw_flat(PwCgP<T, PP>{g, opref(OP_PRECOND_INV), x, r, p, bx, st, par, tol, oR, sc, rzf}, B);                                 // beta, stop test ; p, best iterate
-        });
-        par ^= 1;
-        cg.flags.post(it & 1, st.done, 6, sm);
-        if (it > 2 && cg.flags.wait((it - 1) & 1)[it & 1] != 0) break;      // previous iteration's flags: it left `done` at parity (it - 2) & 1
-      }
-    }
-    return cg.finish(v, f_out, hist, st.done, 6, 4, 5);
+  // The value pass of a log-posterior:  z = mean(f) - d,  w = Cn^-1 z  and  Cf^-1 f,  with z'w in qdev[2] and f'Cf^-1 f in qdev[0], which stay on
+  // the device until read_logpdf.  mean_into(z, qdev) enqueues the model's mean of f into z (harmonic F) once the scratch is there.
+  struct ValuePass { cx<T>*w, *cfif; double* qd; };
+  template <typename MeanF> ValuePass value_pass(MeanF&& mean_into, const cx<T>* f_h, const cx<T>* dd, int B) {
+    const long n = fsize(B);
+    CMBL_REQUIRE(B <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
+    t1.ensure(sizeof(cx<T>) * n); t2.ensure(sizeof(cx<T>) * n); t3.ensure(sizeof(cx<T>) * n); qdev.ensure(sizeof(double) * 3 * MAXBATCH);
+    cx<T>*z = t1.template as<cx<T>>(), *cfif = t2.template as<cx<T>>(), *w = t3.template as<cx<T>>();
+    double* qd = qdev.template as<double>();
+    mean_into(z, qd);
+    c->lincomb1((T*)z, (const T*)z, (const T*)dd, 1.0, -1.0, 2 * n / B, B);
+    apply_cn_inv(z, w, B);                    c->dot_F_dev(z, w, P, B, qd + 2 * MAXBATCH);
+    apply(OP_CF_INV, f_h, cfif, B);           c->dot_F_dev(f_h, cfif, P, B, qd);
+    return {w, cfif, qd};
   }
   // logpdf(ds; f) of the no-lensing model per batch slot, -1/2 [ f'Cf^-1 f + (M B f - d)'Cn^-1 (M B f - d) + logdet_sum ] with logdet_sum = logdet Cf +
   // logdet Cn (src/dataset.jl:68-73, src/distributions.jl:11-15), and with gf_h its gradient B'M'Cn^-1 (d - M B f) - Cf^-1 f (src/dataset.jl:76-80)
   // from the same pass through data space.  The sums are formed on the device in double, in a fixed order, and read back once (read_logpdf).
   // Any size, either form of the noise operator.  Reads nothing of phi: OP_CPHI_INV, OP_D*, OP_G_INV need not be set.
   void nolens_logpdf(const cx<T>* f_h, const cx<T>* dd, double* lp, cx<T>* gf_h, int B) {
-    const long n = fsize(B);
-    CMBL_REQUIRE(B <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
-    t1.ensure(sizeof(cx<T>) * n); t2.ensure(sizeof(cx<T>) * n); t3.ensure(sizeof(cx<T>) * n); qdev.ensure(sizeof(double) * 3 * MAXBATCH);
-    cx<T>*z = t1.template as<cx<T>>(), *cfif = t2.template as<cx<T>>(), *w = t3.template as<cx<T>>();
-    double* qd = qdev.template as<double>();
-    CMBL_HIP(hipMemsetAsync(qd + MAXBATCH, 0, sizeof(double), c->stream));   // the slot of phi'Cphi^-1 phi: this model has none
-    apply(OP_B, f_h, z, B);                                                  // z = M B f - d
-    apply_M(z, B, false);
-    c->lincomb1((T*)z, (const T*)z, (const T*)dd, 1.0, -1.0, 2 * n / B, B);
-    apply_cn_inv(z, w, B);                    c->dot_F_dev(z, w, P, B, qd + 2 * MAXBATCH);
-    apply(OP_CF_INV, f_h, cfif, B);           c->dot_F_dev(f_h, cfif, P, B, qd);
+    const ValuePass q = value_pass([&](cx<T>* z, double* qd) {
+      CMBL_HIP(hipMemsetAsync(qd + MAXBATCH, 0, sizeof(double), c->stream)); // the slot of phi'Cphi^-1 phi: this model has none
+      apply(OP_B, f_h, z, B);                                                // z = M B f
+      apply_M(z, B, false);
+    }, f_h, dd, B);
     if (gf_h) {
-      apply_M(w, B, true);
-      apply(OP_B, w, w, B, true, false, false, nullptr, 0, (T)-1);
-      c->lincomb1((T*)gf_h, (const T*)w, (const T*)cfif, 1.0, -1.0, 2 * n / B, B);
+      apply_M(q.w, B, true);
+      apply(OP_B, q.w, q.w, B, true, false, false, nullptr, 0, (T)-1);
+      c->lincomb1((T*)gf_h, (const T*)q.w, (const T*)q.cfif, 1.0, -1.0, 2 * fsize(B) / B, B);
     }
     read_logpdf(lp, B, 0);
   }
 
+  // The Wiener filter in the form of form(L).  Fused (CgSolver::solve_fused): A p is flow_Ap with a LenseFlow, nolens_adjoint with the identity (7
+  // launches per iteration with a pixel mask, 3 without); the solver's z is free there and serves as flow_Ap's scratch.
   int wiener_cg(LensOps<T>& L, const cx<T>* dd, const cx<T>* fstart, double tol, int maxit, cx<T>* f_out, double* hist, int B) {
-    if (Flow<T>* flow = fused() ? L.as_flow() : nullptr) return wiener_cg_fused(*flow, dd, fstart, tol, maxit, f_out, hist, B);
-    if (fused() && L.as_identity()) return wiener_cg_nolens(L, dd, fstart, tol, maxit, f_out, hist, B);
-    const auto v = cg_problem(L, dd, fstart, maxit, 6, B);
-    cg.solve(v, cg_A(L, B), [&](const cx<T>* r, cx<T>* z, double* rz) { apply(OP_PRECOND_INV, r, z, B); c->dot_F_dev(r, z, P, B, rz); }, tol);
-    return cg.finish(v, f_out, hist, v.si, 4, 1, 2);
+    const Form fm = form(L);
+    if (fm == FORM_COMPOSED) {
+      const auto v = cg_problem<CgStateBlock>(L, dd, fstart, maxit, B);
+      cg.solve(v, cg_A(L, B), [&](const cx<T>* r, cx<T>* z, double* rz) { apply(OP_PRECOND_INV, r, z, B); c->dot_F_dev(r, z, P, B, rz); }, tol);
+      return cg.template finish<CgStateBlock>(v, f_out, hist);
+    }
+    const auto v = cg_problem<CgScalBlock>(L, dd, fstart, maxit, B);
+    cg.solve_fused(v, P, opref(OP_PRECOND_INV), tol, [&](const cx<T>* p, cx<T>* Ap) {
+      return fm == FORM_FLOW ? flow_Ap(*L.as_flow(), p, v.z, Ap, B) : nolens_adjoint(p, nullptr, B, Ap, B);
+    });
+    return cg.template finish<CgScalBlock>(v, f_out, hist);
   }
 
   // What grad_logpdf and the composed logpdf_mixed share, for nphi planes of phi (1, or one per slot):  z = M B L f - d with f~ = L f left in
@@ -411,18 +364,11 @@ struct Dataset : DatasetApi {
   // adjoint: w <- -B'M'Cn^-1 z = d/df~ (QU Fourier).  The prior terms are only handed out: each caller forms its own sums with them.
   struct Posterior { cx<T>*w, *cfif, *cpip; };
   Posterior posterior(LensOps<T>& L, const cx<T>* f_h, const cx<T>* phi_F, int nphi, const cx<T>* dd, bool adjoint, int B) {
-    const long n = fsize(B);
-    CMBL_REQUIRE(B <= MAXBATCH, ERR_ARG, "nbatch > 256 not supported in reductions");
-    ftil.ensure(sizeof(T) * (long)P * B * c->npix()); t1.ensure(sizeof(cx<T>) * n); t2.ensure(sizeof(cx<T>) * n); t3.ensure(sizeof(cx<T>) * n);
-    gphi.ensure(sizeof(cx<T>) * nphi * c->plane()); qdev.ensure(sizeof(double) * 3 * MAXBATCH);
-    cx<T>*z = t1.template as<cx<T>>(), *cfif = t2.template as<cx<T>>(), *w = t3.template as<cx<T>>(), *cpip = gphi.template as<cx<T>>();
-    double* qd = qdev.template as<double>();
-    mean(L, f_h, z, B, ftil.template as<T>());                              // leaves f~ = L f in ftil
-    c->lincomb1((T*)z, (const T*)z, (const T*)dd, 1.0, -1.0, 2 * n / B, B);
-    apply_cn_inv(z, w, B);                    c->dot_F_dev(z, w, P, B, qd + 2 * MAXBATCH);
-    apply(OP_CF_INV, f_h, cfif, B);           c->dot_F_dev(f_h, cfif, P, B, qd);
+    ftil.ensure(sizeof(T) * (long)P * B * c->npix()); gphi.ensure(sizeof(cx<T>) * nphi * c->plane());
+    const ValuePass q = value_pass([&](cx<T>* z, double*) { mean(L, f_h, z, B, ftil.template as<T>()); }, f_h, dd, B);   // leaves f~ = L f in ftil
+    cx<T>*w = q.w, *cfif = q.cfif, *cpip = gphi.template as<cx<T>>();
     apply(OP_CPHI_INV, phi_F, cpip, nphi, false, false, false, nullptr, 0, 1, 1);
-    c->dot_F_dev(phi_F, cpip, 1, nphi, qd + MAXBATCH);
+    c->dot_F_dev(phi_F, cpip, 1, nphi, q.qd + MAXBATCH);
     if (adjoint) {
       apply_M(w, B, true, true);
       apply(OP_B, w, w, B, true, true, true, nullptr, 0, (T)-1);

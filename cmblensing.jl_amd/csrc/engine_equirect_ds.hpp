@@ -215,7 +215,7 @@ struct EqDataset : EqDatasetApi {
   // res = dot(r, z), stop when all(res < tol), the best-res iterate is returned, a NaN residual is ERR_NAN.  Returns the length of the history.
   int wiener_cg(const void* dv, const void* fstart, double tol, int maxit, void* f_out, double* hist, int B) override {
     require(B, true, true); scratch(B); weights();
-    const auto v = cg.begin(azsize(B), B, maxit, 6);
+    const auto v = cg.template begin<CgStateBlock>(azsize(B), B, maxit);
     T* map = mp.template as<T>();                                            // b = B' M' Cn^-1 d
     CMBL_HIP(hipMemcpyAsync(map, dv, sizeof(T) * mapsize(B), hipMemcpyDeviceToDevice, c->stream));
     weigh_back(map, t1.template as<cx<T>>(), B);
@@ -223,7 +223,7 @@ struct EqDataset : EqDatasetApi {
     auto A = [&](const cx<T>* p, cx<T>* Ap, double* pAp) { hess(p, Ap, pAp, B); };
     cg.start(v, (const cx<T>*)fstart, A);
     cg.solve(v, A, [&](const cx<T>* r, cx<T>* z, double* rz) { apply1(EQDS_PRECOND_INV, false, T(1), r, z, r, rz, B); }, tol);
-    return cg.finish(v, (cx<T>*)f_out, hist, v.si, 4, 1, 2);
+    return cg.template finish<CgStateBlock>(v, (cx<T>*)f_out, hist);
   }
 };
 

@@ -16,7 +16,7 @@ struct LensOps {
   virtual const char* op_name() const = 0;
   // the LenseFlow behind this operator, for the fused forms of Dataset<T> that only it has; nullptr for every other operator
   virtual Flow<T>* as_flow() { return nullptr; }
-  // true for NoLens<T> alone (L = I, src/dataset.jl:343): Dataset<T> then runs its flow-free forms (nolens_adjoint, wiener_cg_nolens)
+  // true for NoLens<T> alone (L = I, src/dataset.jl:343): Dataset<T>::form is then FORM_IDENTITY, the flow-free forms (nolens_adjoint)
   virtual bool as_identity() const { return false; }
   // the operator has its phi (ERR_STATE otherwise) and takes B batch slots of f against it (ERR_SHAPE otherwise)
   virtual void op_check(int B) const = 0;

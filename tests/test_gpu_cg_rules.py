@@ -1,7 +1,7 @@
 """The data-dependent rules of the Wiener filter's conjugate gradient (src/numerical_algorithms.jl:106-125) in both hand-written forms of the
 iteration: `all(res < bestres)` replaces the best iterate and the stored best residual of ALL batch slots together; `all(res < tol)` stops the
 solve; what the host had enqueued past the stop changes nothing.
-  fused    : Dataset::wiener_cg_fused with PwCgStart / PwCgAp / PwCgXr / PwCgP and k_cg_init (a LenseFlow on a power-of-two map; the default)
+  fused    : CgSolver::solve_fused with PwCgStart / PwCgXr / PwCgP and k_cg_init around Dataset::flow_Ap (PwCgAp; a LenseFlow on a power-of-two map; the default)
   composed : CgSolver::solve with k_cg_start / alpha / xr / beta / p / keep_best (here: option fused_harm off, CMBL_NO_FUSED_HARM=1)
 on the three two-slot data sets of tests/_cg_rules_ref.py (32 x 32, I / P / IP, theta = 3', mask, no beam), whose slots disagree between the
 steps 10 and 14: tests/test_cg_rules_ref.py asserts every branch used here with its margin, on the CPU.  A per-slot or `any` rule, a best

@@ -1,6 +1,6 @@
 """The flat-sky NoLensingDataSet on the device (d = M B f + n; src/dataset.jl:37-47, 68-73, 341-352; src/maximization.jl:17-42, 56-62, 235) against
 the float64 oracle of tests/_nolensing_ref.py, in both forms of the engine:
-  fused    : Dataset::nolens_adjoint / wiener_cg_nolens with PwNlAp (pixel mask) or PwNlDiag (none) -- power-of-two maps, the default
+  fused    : Dataset::nolens_adjoint, in the Wiener filter inside CgSolver::solve_fused, with PwNlAp (pixel mask) or PwNlDiag (none) -- power-of-two maps, the default
   composed : the identity NoLens<T> in the L slot of the composed paths (here: option fused_harm off, CMBL_NO_FUSED_HARM=1; any-size maps always)
 Shapes (Ny, Nx): 32 x 32, 32 x 64, 64 x 32 (the smallest the fused kernels take, non-square both ways, Nyh = 17 / 33 leave a tail row group) in both
 forms, 24 x 40 composed; I / P / IP; f32 and f64; B = 2, and B = 17 at 32 x 32 P (the B > 16 branch of PwCgP).  tests/test_nolensing_ref.py pins

@@ -1,7 +1,7 @@
 """Time per conjugate-gradient iteration of the Wiener filter (argmaxf_logpdf, src/maximization.jl:17-42) with LenseFlow(7) and with BilinearLens in
 the L slot of a data set, from one process: 1024^2 QU fp32 and 2048^2 QU fp64, B = 1 and B = 8 data slots against one phi, pixel mask on.
 
-Variants, alternated, each repeated REPS times (median and spread = max - min of the repeats):
+Variants, alternated, each repeated REPS times (median, spread = max - min and [min, max] of the repeats):
   (i)   LenseFlow(7) through cmbl_wiener_cg
   (ii)  BilinearLens as a CG loop written here from operations the library exported before the `_op` entry points existed (L * f, L.adjoint * g,
         diag_apply, map_fma, dot, axpby): the baseline; this variant also runs on a checkout without them
@@ -128,7 +128,7 @@ def main():
             for name, _ in variants:
                 v = times[name]
                 med[name] = float(np.median(v))
-                print(f"  {name:58s} {med[name]:9.3f} ms   spread {max(v) - min(v):7.3f}   (k = {iters[name]} solves of {NLONG} and of {NSHORT} iterations)")
+                print(f"  {name:58s} {med[name]:9.3f} ms   spread {max(v) - min(v):7.3f}   [{min(v):.3f}, {max(v):.3f}]   (k ={iters[name]} solves of {NLONG} and of {NSHORT} iterations)")
             base = [k for k in med if k.startswith("(ii)")][0]
             for name in med:
                 if name != base:

@@ -3,10 +3,10 @@ NoLensingDataSet, src/dataset.jl:37-47) at 1024^2, fp32, border mask, QU and T+Q
 
   (i)   a BaseDataSet with a LenseFlow(7) at phi = 0: the only way to this answer before the identity existed (two identity flows per iteration)
   (ii)  a NoLensingDataSet, composed form: the identity NoLens<T> in the L slot, option fused_harm = 0
-  (iii) a NoLensingDataSet, fused form (the default): Dataset::wiener_cg_nolens, 7 launches per iteration
+  (iii) a NoLensingDataSet, fused form (the default): CgSolver::solve_fused around Dataset::nolens_adjoint, 7 launches per iteration
 
 A solve is fixed-length (tol = 0); the time per iteration is (T(nsteps = 60) - T(nsteps = 10)) / 50 after a warm-up of both lengths, the forms
-alternated, REPS repetitions each (median; spread = max - min).  The condition on (iii): not slower than (ii) by more than the spread.
+alternated, REPS repetitions each (median; spread = max - min; [min, max]).  The condition on (iii): not slower than (ii) by more than the spread.
 Form (i) needs nothing of the no-lensing feature, so the same file measures it on a commit that does not have it (there (ii) and (iii) are left out).
 
     python tools/gpu_nolensing_time.py        (prints its table; profiles/nolensing_cg_time.txt is a run of it)"""
@@ -77,7 +77,7 @@ def main():
         med = {}
         for k, v in times.items():
             med[k] = float(np.median(v))
-            print(f"  {k:44s} {med[k]:9.4f} ms   spread {max(v) - min(v):7.4f}")
+            print(f"  {k:44s} {med[k]:9.4f} ms   spread {max(v) - min(v):7.4f}   [{min(v):.4f}, {max(v):.4f}]")
         ks = list(med)
         if len(ks) == 3:
             print(f"  (iii) / (ii) = {med[ks[2]] / med[ks[1]]:.3f}      (i) / (iii) = {med[ks[0]] / med[ks[2]]:.2f}")
